@@ -12,6 +12,11 @@ Also: --workload gas (configs[2], 10k pods x 50k nodes x 8 cards), --workload de
 (configs[3]: 1M nodes x 64 rules, node-sharded over the ranks, violations all-gathered) and
 --workload c5 (configs[4]: 64k pods x 1M nodes TAS+GAS, node-sharded, per-pod top-k merge).
 
+A plain run sets up, warms up, times --steps steps and prints the line; --full adds the
+side measurements (CPU baseline, request latency, pipelined sub-record, per-kernel times,
+snapshot refresh times, multi-GPU node-sharded sub-record).  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.  See DESIGN.md §Measurement for the byte model.
 """
 import argparse
@@ -85,6 +90,55 @@ def load_traffic(name):
             return json.load(f).get(name)
     except (OSError, ValueError):
         return None
+
+
+# ------------------------------------------------------------------- --dump-outputs
+
+DUMP_BYTES = 64 << 20   # most that --dump-outputs writes
+DUMP_VALUES = 1 << 22   # values per sampled array (32 MB as float64)
+
+
+def sample_rows(n, row_len):
+    """Row indices (sorted) of a fixed, seeded sample of n rows of row_len values each that
+    holds at most DUMP_VALUES values; every row when they all fit."""
+    keep = max(1, DUMP_VALUES // max(row_len, 1))
+    if keep >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0xD0).choice(n, keep, replace=False))
+
+
+def valid_prefix(rows, lens, dtype):
+    """Integer list rows [r][n] of which the first lens[r] entries are written, as `dtype`
+    with -1 in every other place (those are never written)."""
+    out = rows.astype(dtype)
+    out[np.arange(rows.shape[1])[None, :] >= lens[:, None]] = -1
+    return out
+
+
+def index_dtype(n):
+    """float32 holds every index below n exactly up to 2^24."""
+    return np.float32 if n <= 1 << 24 else np.float64
+
+
+def popcount_rows(words_t, n):
+    """Set bits among the first n of every row of an int64 bitmap on the device (float64)."""
+    out = np.empty(words_t.shape[0], np.float64)
+    for lo in range(0, len(out), 256):
+        w = words_t[lo:lo + 256].cpu().numpy().view(np.uint64)
+        out[lo:lo + 256] = wl.unpack_bits(w, n).sum(axis=1)
+    return out
+
+
+def write_outputs(directory, rank, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy (rank r > 0 of a multi-GPU run
+    writes rank<r>_<name>.npy: its batch is its own)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise ValueError(f"--dump-outputs would write {total} bytes (limit {DUMP_BYTES})")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(directory, (f"rank{rank}_" if rank else "") + name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------- TAS
@@ -169,7 +223,7 @@ def bench_tas(args, world, rank):
     ctx.tas_snapshot_set_device(1, N, M, v_t, p_t, stream)
     torch.cuda.synchronize()
     snapshot_ms = (time.perf_counter() - t0) * 1e3
-    refresh = snapshot_refresh_ms(ctx, N, M, v_t, p_t, stream)
+    refresh = snapshot_refresh_ms(ctx, N, M, v_t, p_t, stream) if args.full else None
     rules_t = dev(batch.rules.view(np.uint8))
     off_t = dev(batch.rule_off)
     prio_t = dev(batch.prio.view(np.uint8))
@@ -179,7 +233,8 @@ def bench_tas(args, world, rank):
     # batch i + 1's prep and first blocks run under batch i's eval; D = 1 (default): every
     # step on the launch stream.  A pipelined run (PIPE_TAS streams) is reported beside it.
     D = max(1, args.pipeline)
-    depth = max(D, PIPE_TAS)
+    pipelined = D == 1 and PIPE_TAS > 1 and not args.no_pipelined
+    depth = max(D, PIPE_TAS if pipelined else 1)
     outs = [(torch.empty((P, pas_amd.w64(N)), dtype=torch.int64, device="cuda"),
              torch.empty((P, N), dtype=torch.int32, device="cuda"),
              torch.empty(P, dtype=torch.int32, device="cuda")) for _ in range(depth)]
@@ -195,19 +250,35 @@ def bench_tas(args, world, rank):
     # timed steps: two HIP events on the launch stream around all of them (events between
     # the steps would add ~10 us each to the wall)
     elapsed, span_ms = pipe.timed(args.steps, args.warmup, world)
-    # per-kernel breakdown from extra, untimed steps (events around every launch)
-    ctx.reset_timing()
-    ctx.set_timing(2)
-    n_detail = min(args.steps, 5)
-    for _ in range(n_detail):
-        step()
-    pipe.sync()
-    ctx.set_timing(0)
-    kern, launches = {}, {}
-    for kid in (_lib.PAS_K_TAS_PREP, _lib.PAS_K_TAS_EVAL):
-        ms, n = ctx.kernel_time(kid)
-        kern[_lib.KERNEL_NAMES[kid]] = ms / n_detail
-        launches[_lib.KERNEL_NAMES[kid]] = n // n_detail
+    if args.dump_outputs:
+        # the last timed step's output set: a seeded sample of pods with their pass rows (one
+        # value per node) and ordered lists, every pod's list length and pass count
+        pt, ot, lt = outs[(pipe.turn - 1) % D]
+        lens = lt.cpu().numpy()
+        rows = sample_rows(P, N)
+        rows_t = torch.from_numpy(rows).cuda()
+        write_outputs(args.dump_outputs, rank, {
+            "pods": rows.astype(np.float64),
+            "pass_rows": wl.unpack_bits(pt[rows_t].cpu().numpy().view(np.uint64), N)
+                           .astype(np.float32),
+            "order_rows": valid_prefix(ot[rows_t].cpu().numpy(), lens[rows], index_dtype(N)),
+            "order_len": lens.astype(np.float64),
+            "pass_count": popcount_rows(pt, N)})
+    kern = launches = None
+    if args.full:
+        # per-kernel breakdown from extra, untimed steps (events around every launch)
+        ctx.reset_timing()
+        ctx.set_timing(2)
+        n_detail = min(args.steps, 5)
+        for _ in range(n_detail):
+            step()
+        pipe.sync()
+        ctx.set_timing(0)
+        kern, launches = {}, {}
+        for kid in (_lib.PAS_K_TAS_PREP, _lib.PAS_K_TAS_EVAL):
+            ms, n = ctx.kernel_time(kid)
+            kern[_lib.KERNEL_NAMES[kid]] = ms / n_detail
+            launches[_lib.KERNEL_NAMES[kid]] = n // n_detail
     sum_len = int(len_t.sum().item())
     # algorithmic bytes per step: columns + presence + pass bitmaps +
     # ordered lists + lengths, plus the rule tables; divided by the span of the path
@@ -254,7 +325,7 @@ def bench_tas(args, world, rank):
             "kernel_ms": kernel_s * 1e3,
         },
     }
-    if D == 1 and PIPE_TAS > 1 and not args.no_pipelined:
+    if pipelined:
         el2, ms2 = StreamPipeline(stream, PIPE_TAS, launch).timed(args.steps, args.warmup, world,
                                                                   args.settle)
         out["pipelined"] = pipelined_record(PIPE_TAS, el2, ms2, P * N, world, args.steps,
@@ -436,8 +507,9 @@ def bench_gas(args, world, rank):
     # i + 1's prep kernels run under batch i's fit kernels (one scratch slot per stream); a
     # pipelined run (PIPE_GAS streams) is reported beside the D = 1 line
     D = max(1, args.pipeline)
-    depth = max(D, PIPE_GAS)
-    results = [torch.empty((P, ld), dtype=torch.int32, device="cuda") for _ in range(depth)]
+    run_pipelined = D == 1 and PIPE_GAS > 1 and not args.no_pipelined
+    depth = max(D, PIPE_GAS if run_pipelined else 1)
+    results =[torch.empty((P, ld), dtype=torch.int32, device="cuda") for _ in range(depth)]
     res_t = results[0]
 
     def launch(k, s):
@@ -448,23 +520,35 @@ def bench_gas(args, world, rank):
     settle_steps = distrib.settle(step, args.settle, sync=pipe.sync, world=world)
     elapsed, gpu_ms = pipe.timed(args.steps, args.warmup, world)
     gpu = {"ms_per_step": gpu_ms}
-    # the fit launches alone, from extra, untimed steps (span events around them)
-    ctx.reset_timing()
-    ctx.set_timing(1)
-    for _ in range(min(args.steps, 5)):
-        step()
-    pipe.sync()
-    ctx.set_timing(0)
+    if args.dump_outputs:
+        # the last timed step's result set: a seeded sample of pods with their result word per
+        # node, and every pod's number of fitting nodes (bit 31 of the word)
+        last = results[(pipe.turn - 1) % D][:, :N]
+        rows = sample_rows(P, N)
+        write_outputs(args.dump_outputs, rank, {
+            "pods": rows.astype(np.float64),
+            "result_rows": last[torch.from_numpy(rows).cuda()].cpu().numpy().astype(np.float64),
+            "fit_count": (last < 0).sum(dim=1).cpu().numpy().astype(np.float64)})
+    fit_ms = None
+    if args.full:
+        # the fit launches alone, from extra, untimed steps (span events around them)
+        ctx.reset_timing()
+        ctx.set_timing(1)
+        for _ in range(min(args.steps, 5)):
+            step()
+        pipe.sync()
+        ctx.set_timing(0)
+        k_ms, k_n = ctx.kernel_time(_lib.PAS_K_GAS_FIT)
+        fit_ms = k_ms / max(k_n, 1)
     pipelined = None
-    if D == 1 and PIPE_GAS > 1 and not args.no_pipelined:
+    if run_pipelined:
         pipelined = StreamPipeline(stream, PIPE_GAS, launch).timed(args.steps, args.warmup,
                                                                    world, args.settle)
     written = max(D, PIPE_GAS if pipelined else 1)  # result sets some step wrote
     assert all(torch.equal(r, res_t) for r in results[1:written]), "pipeline results differ"
-    k_ms, k_n = ctx.kernel_time(_lib.PAS_K_GAS_FIT)
     # the same batch into dense [P][N] rows (pas_gas_fit_device), untimed extra steps
     dense_ms = None
-    if ld != N:
+    if args.full and ld != N:
         dres_t = torch.empty((P, N), dtype=torch.int32, device="cuda")
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(3):
@@ -491,15 +575,14 @@ def bench_gas(args, world, rank):
         "config": {"settle_steps": settle_steps, "workload": "gas_fit (BASELINE configs[2])", "pods_per_gpu": P, "nodes": N,
                    "cards": K, "resources": Q, "result_row_pitch": ld, "pipeline_streams": D,
                    "dense_pitch_gpu_ms_per_step": dense_ms,
-                   "fit_fraction": float((res_t[:, :N].cpu().numpy().view(np.uint32) >> 31)
-                                         .mean())},
+                   "fit_fraction": (res_t[:, :N] < 0).sum().item() / (P * N)},  # bit 31 set
         "roofline": {"bound": "hbm",
                      "kernel": "gas fit path: gas_prep_kernel, gas_rank_prep_kernel, "
                                "gas_rfit_single_kernel, gas_rfit_closed_kernel, "
                                "gas_rfit_seq_kernel and gas_fit_generic_kernel (two HIP "
                                "events on the launch stream "
                                "around the timed steps)",
-                     "fit_launches_ms": k_ms / max(k_n, 1),
+                     "fit_launches_ms": fit_ms,
                      "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": load_traffic("gas_fit_kernel"), "algorithmic_bytes": alg_bytes,
@@ -572,7 +655,7 @@ def bench_deschedule(args, world, rank):
     ctx.tas_snapshot_set_device(1, n_local, M, v_t, p_t, stream)
     torch.cuda.synchronize()
     snapshot_ms = (time.perf_counter() - t0) * 1e3
-    refresh = snapshot_refresh_ms(ctx, n_local, M, v_t, p_t, stream)
+    refresh = snapshot_refresh_ms(ctx, n_local, M, v_t, p_t, stream) if args.full else None
     del v_t, p_t
     rules_t, off_t = dev(rules.view(np.uint8)), dev(off)
     viol_t = torch.empty((S, pas_amd.w64(n_local)), dtype=torch.int64, device="cuda")
@@ -604,6 +687,18 @@ def bench_deschedule(args, world, rank):
     ctx.set_timing(1)
     elapsed = timed_steps(step, args.steps, 0, world)
     ctx.set_timing(0)
+    if args.dump_outputs:
+        # per node (a seeded sample of them past DUMP_VALUES nodes): the strategies it violates
+        # in the gathered cluster bitmaps, as a mask with bit s for strategy s; the shard's
+        # add / remove label masks per node; the plan's total
+        bits = wl.unpack_bits(gathered["v"].cpu().numpy().view(np.uint64), N)
+        nodes, local = sample_rows(N, 1), sample_rows(n_local, 1)
+        write_outputs(args.dump_outputs, rank, {
+            "nodes": nodes.astype(np.float64), "shard_nodes": local.astype(np.float64),
+            "violation_masks": (1 << np.arange(S)).astype(np.float64) @ bits[:, nodes],
+            "label_add_masks": add_t.cpu().numpy()[local].astype(np.float64),
+            "label_remove_masks": rem_t.cpu().numpy()[local].astype(np.float64),
+            "label_total": total_t.cpu().numpy().astype(np.float64)})
     k_ms, k_n = ctx.kernel_time(_lib.PAS_K_TAS_VIOLATIONS)
     l_ms, l_n = ctx.kernel_time(_lib.PAS_K_TAS_LABELS)
     w = pas_amd.w64(n_local)
@@ -699,14 +794,27 @@ def bench_c5(args, world, rank):
         step()
     gpu = {}
     elapsed = timed_steps(step, args.steps, 0, world, gpu=gpu)
-    # the combined kernel alone, from extra untimed steps (events around the launch)
-    ctx.reset_timing()
-    ctx.set_timing(2)
-    n_detail = min(args.steps, 5)
-    for _ in range(n_detail):
-        step()
-    ctx.set_timing(0)
-    k_ms, k_n = ctx.kernel_time(_lib.PAS_K_TAS_GAS_TOPK)
+    if args.dump_outputs:
+        # the merged top-k lists (a seeded sample of pods past DUMP_VALUES entries) and every
+        # pod's list length
+        lens = result["len"].cpu().numpy()
+        rows = sample_rows(P, K)
+        write_outputs(args.dump_outputs, rank, {
+            "pods": rows.astype(np.float64),
+            "topk_nodes": valid_prefix(result["nodes"].cpu().numpy()[rows], lens[rows],
+                                       index_dtype(N)),
+            "topk_len": lens.astype(np.float64)})
+    topk_ms = None
+    if args.full:
+        # the combined kernel alone, from extra untimed steps (events around the launch)
+        ctx.reset_timing()
+        ctx.set_timing(2)
+        n_detail = min(args.steps, 5)
+        for _ in range(n_detail):
+            step()
+        ctx.set_timing(0)
+        k_ms, k_n = ctx.kernel_time(_lib.PAS_K_TAS_GAS_TOPK)
+        topk_ms = k_ms / max(k_n, 1)
     out = {
         "metric": "combined TAS+GAS per-pod top-k lists/sec, 64k pods x 1M nodes, node-sharded",
         "value": P * args.steps / elapsed,
@@ -722,7 +830,7 @@ def bench_c5(args, world, rank):
                                              "all-gathered and merged",
                    "step": "pas_tas_gas_topk_device (filter + fit along each pod's order until "
                            "k kept) + all-gather + pas_topk_merge_device",
-                   "topk_kernel_ms": k_ms / max(k_n, 1),
+                   "topk_kernel_ms": topk_ms,
                    "gpu_ms_per_step": gpu["ms_per_step"],
                    "mean_list_len": float(result["len"].float().mean().item())},
     }
@@ -854,9 +962,21 @@ def main():
                          "pas_tas_deschedule_device, one pass)")
     ap.add_argument("--no-request-latency", action="store_true",
                     help="skip the f2 request-latency leg of the TAS workload")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: snapshot refresh times, per-kernel times from "
+                         "extra steps, the pipelined sub-record, the CPU baseline, the request "
+                         "latency leg, the dense-pitch GAS comparison and, with --gpus N > 1, the "
+                         "node-sharded sub-record (each has a --no-... switch of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB; large outputs as a "
+                         "fixed, seeded sample)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_request_latency = True
+        args.no_pipelined = args.no_node_sharded = True
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # no launcher: start one child per GPU (fresh processes, nothing initialised here)

@@ -11,7 +11,7 @@ for L in "$@"; do
 done
 for i in $(seq "$N"); do
   for T in "${trees[@]}"; do
-    timeout -k 10 150 python3 "$T/bench.py" $A --no-cpu-baseline --no-request-latency > /tmp/ab_out.json 2>/tmp/ab_err.log || { cat /tmp/ab_err.log; exit 1; }
+    timeout -k 10 150 python3 "$T/bench.py" $A --full --no-cpu-baseline --no-request-latency > /tmp/ab_out.json 2>/tmp/ab_err.log || { cat /tmp/ab_err.log; exit 1; }
     tail -1 /tmp/ab_out.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d.get('roofline') or {}; print('$(basename $T)', round(d['ms_per_step'],4), round(r.get('kernel_ms',0),4), round(r.get('frac',0),4), {k: round(v,3) for k,v in (d['config'].get('kernel_ms_per_step') or {}).items()})"
   done
 done

@@ -5,7 +5,7 @@
 mkdir -p gpurun_out
 ( while sleep 45; do date +%T >> gpurun_out/g8_heartbeat.txt; done ) &
 HB=$!
-T0=$(date +%s); timeout -k 10 1080 python -u bench.py --gpus 8 --backend gloo \
+T0=$(date +%s); timeout -k 10 1080 python -u bench.py --gpus 8 --backend gloo --full \
     > gpurun_out/g8_gloo.json 2> gpurun_out/g8_gloo.err
 rc=$?; echo "wall_s=$(( $(date +%s) - T0 ))"
 kill $HB

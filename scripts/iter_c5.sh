@@ -16,7 +16,7 @@ for L in "$@"; do
 done
 for i in 1 2 3; do
   for D in "${T[@]}"; do
-    timeout -k 10 300 python3 "$D/bench.py" --workload c5 --steps 10 --warmup 2 --no-cpu-baseline \
+    timeout -k 10 300 python3 "$D/bench.py" --workload c5 --steps 10 --warmup 2 --full --no-cpu-baseline \
       > /tmp/c5.json 2>/tmp/c5.err || { tail /tmp/c5.err; exit 1; }
     tail -1 /tmp/c5.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); c=d['config']; print('$(basename $D)', round(d['ms_per_step'],4), 'kernel', round(c['topk_kernel_ms'],4), 'len', round(c['mean_list_len'],2))"
   done

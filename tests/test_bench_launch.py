@@ -65,13 +65,40 @@ import pytest  # noqa: E402
 
 
 @pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline line without the --full side measurements, and
+    --dump-outputs writes the last timed step's outputs: float arrays, consistent with each
+    other, within the size limit."""
+    import numpy as np
+    P, N = 64, 5000
+    r = _run(["--pods", str(P), "--nodes", str(N), "--steps", "2", "--warmup", "1", "--settle",
+              "0", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-4000:]
+    out = _json_lines(r.stdout)[0]
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    for key in ("cpu_baseline", "request_latency", "pipelined"):
+        assert key not in out
+    assert out["config"]["kernel_ms_per_step"] is None
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"pods", "pass_rows", "order_rows", "order_len", "pass_count"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    pods = got["pods"].astype(int)
+    assert got["pass_rows"].shape == got["order_rows"].shape == (len(pods), N)
+    assert got["order_len"].shape == got["pass_count"].shape == (P,)
+    assert np.array_equal(got["pass_rows"].sum(axis=1), got["pass_count"][pods])
+    assert np.array_equal((got["order_rows"] >= 0).sum(axis=1), got["order_len"][pods])
+    assert out["config"]["prioritize_entries_per_step"] == got["order_len"].sum()
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_multi_rank_bench_carries_node_sharded_record():
-    """`bench.py --gpus 2` of the headline workload: rank 0's line carries the node-sharded
-    sub-record (C5 top-k + C4 sweep over a node-sharded cluster, all-gathers across the
+    """`bench.py --gpus 2 --full` of the headline workload: rank 0's line carries the
+    node-sharded sub-record (C5 top-k + C4 sweep over a node-sharded cluster, all-gathers across the
     ranks).  Two ranks share the box's one GPU, so the collectives run over gloo here; the
     driver's 8-GPU node runs the same code over RCCL."""
-    r = _run(["--gpus", "2", "--backend", "gloo", "--pods", "256", "--nodes", "20000",
+    r = _run(["--gpus", "2", "--backend", "gloo", "--full", "--pods", "256", "--nodes", "20000",
               "--ns-pods", "1024", "--ns-nodes", "60000", "--steps", "3", "--warmup", "1",
               "--settle", "0.2", "--no-cpu-baseline", "--no-request-latency"], timeout=840)
     assert r.returncode == 0, r.stderr[-4000:]
