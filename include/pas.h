@@ -43,7 +43,8 @@ typedef enum pas_status {
   PAS_OK = 0,
   PAS_EINVAL = -1,     /* bad argument (shape, operator, null pointer) */
   PAS_ESTALE = -2,     /* generation mismatch between call and resident snapshot */
-  PAS_ENOTEXACT = -3,  /* a value is not representable as exact int64 milli */
+  PAS_ENOTEXACT = -3,  /* a value is not representable as exact int64 milli (or: integer part
+                          outside int64, pas_quantity_to_wide; top-k over a wide column) */
   PAS_EDEVICE = -4,    /* HIP runtime error */
   PAS_ENOMEM = -5,     /* device or host allocation failed */
   PAS_ENOSNAP = -6,    /* no snapshot uploaded yet */
@@ -119,6 +120,12 @@ int pas_quantity_to_scaled(const char* quantity, int32_t places, int64_t* out);
 /* The fewest decimal places (0..9) that hold the parsed value exactly: "1500u" -> 4,
  * "0.0005" -> 4, "1e-7" -> 7, "2k" -> 0, "1.5" -> 1. */
 int pas_quantity_decimals(const char* quantity, int32_t* places);
+/* The parsed value as the wide pair (whole, nano): value = whole + nano * 10^-9 with
+ * 0 <= nano < 10^9, whole = floor(value) ("-0.5" -> (-1, 500000000)).  ParseQuantity keeps at
+ * most 9 fractional digits, so every parsed quantity whose floor fits int64 converts exactly,
+ * at any precision and with no column-wide scale.  PAS_EINVAL if ParseQuantity would fail;
+ * PAS_ENOTEXACT only when the integer part is outside int64 (the int64Amount "1e19"). */
+int pas_quantity_to_wide(const char* quantity, int64_t* whole, uint32_t* nano);
 
 /* resource.ParseQuantity(quantity).AsInt64() with `ok` ignored, as the reference uses it
  * (gpuscheduler/utils.go:23, scheduler.go:155).  That is 0 — even for integral values —
@@ -176,6 +183,40 @@ int pas_tas_snapshot_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, in
 int pas_tas_snapshot_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
                                    int32_t n_cols, const int32_t* cols, const int64_t* d_v_milli,
                                    const uint64_t* d_present, void* hip_stream);
+
+/* Wide columns: columns whose values do not all fit int64 at one decimal scale (a byte
+ * counter past 9.22e15, 1e-7 next to 1e12, more than 18 significant digits).  Replaces
+ * columns cols[0 .. n_cols) of the resident snapshot with wide columns
+ *   whole [n_cols][n_nodes] int64, nano [n_cols][n_nodes] uint32, present [n_cols][W64]
+ * (pas_quantity_to_wide; ignored where not present).  The order of a wide column is the
+ * exact order of the pairs (whole signed, then nano unsigned; ties in ascending node index),
+ * and every rule compare against an integer target is exact:  v < t <=> whole < t,
+ * v == t <=> whole == t and nano == 0,  v > t <=> whole > t or (whole == t and nano != 0).
+ * Filter, prioritize, the deschedule sweep (both forms) and the request prioritize evaluate
+ * wide columns; the top-k entry points (pas_tas_topk_device, pas_tas_gas_topk_device) return
+ * PAS_ENOTEXACT while the resident snapshot holds a wide column (their merge keys are 64-bit).
+ * The contract is pas_tas_snapshot_update[_device]'s: gen_from is checked (PAS_ESTALE), the
+ * generation moves to gen_to in the same call, only these columns' orders are rebuilt; the
+ * _device form is asynchronous on hip_stream except for the copy of cols.  The host form
+ * rejects a nano >= 10^9 (PAS_EINVAL); the device form reads nano clamped to 999999999.
+ * pas_tas_snapshot_set[_device] makes every column narrow again; pas_tas_snapshot_update
+ * [_device] on a wide column makes it narrow at the column's recorded scale;
+ * pas_tas_snapshot_set_scale ignores its entries for wide columns.  The wide parts' storage is
+ * allocated when a first wide column arrives. */
+int pas_tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                 int32_t n_cols, const int32_t* cols, const int64_t* whole,
+                                 const uint32_t* nano, const uint64_t* present);
+int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                        int32_t n_cols, const int32_t* cols,
+                                        const int64_t* d_whole, const uint32_t* d_nano,
+                                        const uint64_t* d_present, void* hip_stream);
+/* Forget the resident TAS snapshot (its storage is kept): every call that checks a
+ * generation answers PAS_ENOSNAP until the next pas_tas_snapshot_set[_device].  For a
+ * binding that installs a snapshot in two steps (set, then the wide columns) and must not
+ * leave the first step's state behind when the second fails. */
+int pas_tas_snapshot_drop(pas_ctx* ctx);
+/* Number of wide columns of the resident snapshot (PAS_ENOSNAP without one). */
+int pas_tas_snapshot_wide_count(const pas_ctx* ctx, int32_t* n_wide);
 
 #define PAS_TAS_FILTER 1u      /* produce pass_out (MetricsExtender.filterNodes) */
 #define PAS_TAS_PRIORITIZE 2u  /* produce order_out/order_len (prioritizeNodesForRule) */

@@ -192,6 +192,12 @@ void free_tas(pas_ctx* ctx) {
   free_ptr(reinterpret_cast<void*&>(t.f1k));
   free_ptr(reinterpret_cast<void*&>(t.f32));
   free_ptr(reinterpret_cast<void*&>(t.scale_tab));
+  free_ptr(reinterpret_cast<void*&>(t.wide_flag));
+  free_ptr(reinterpret_cast<void*&>(t.nano));
+  free_ptr(reinterpret_cast<void*&>(t.sorted_nano));
+  free_ptr(reinterpret_cast<void*&>(t.f1k_nano));
+  free_ptr(reinterpret_cast<void*&>(t.f32_nano));
+  free_ptr(t.wide_sort_tmp);
   free_ptr(t.keys_a);
   free_ptr(t.keys_b);
   free_ptr(reinterpret_cast<void*&>(t.ids_a));
@@ -424,6 +430,75 @@ int pas_tas_snapshot_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen
                              pick_stream(ctx, hip_stream));
 }
 
+int pas_tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                 int32_t n_cols, const int32_t* cols, const int64_t* whole,
+                                 const uint32_t* nano, const uint64_t* present) {
+  if (!ctx) return PAS_EINVAL;
+  const char* fn = "pas_tas_snapshot_update_wide";
+  int rc = check_update(ctx, gen_from, n_cols, cols, whole, present, fn);
+  if (rc) return rc;
+  const int32_t N = ctx->tas.n_nodes;
+  if (n_cols > 0 && N > 0 && !nano) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  for (int64_t i = 0; i < (int64_t)n_cols * N; ++i)
+    if (nano[i] > 999999999u)
+      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": nano of column " +
+                                            std::to_string(cols[i / N]) + ", node " +
+                                            std::to_string(i % N) + " is not below 10^9");
+  if ((rc = activate(ctx))) return rc;
+  const size_t vb = sizeof(int64_t) * (size_t)n_cols * N;
+  const size_t nb = sizeof(uint32_t) * (size_t)n_cols * N;
+  const size_t pb = sizeof(uint64_t) * (size_t)n_cols * w64(N);
+  if ((rc = ensure_scratch(ctx, carve_size({vb, nb, pb})))) return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int64_t* d_v = cv.take<int64_t>((size_t)n_cols * N);
+  uint32_t* d_n = cv.take<uint32_t>((size_t)n_cols * N);
+  uint64_t* d_p = cv.take<uint64_t>((size_t)n_cols * w64(N));
+  hipStream_t s = ctx->stream;
+  if (vb) PAS_HIP(ctx, hipMemcpyAsync(d_v, whole, vb, hipMemcpyHostToDevice, s));
+  if (nb) PAS_HIP(ctx, hipMemcpyAsync(d_n, nano, nb, hipMemcpyHostToDevice, s));
+  if (pb) PAS_HIP(ctx, hipMemcpyAsync(d_p, present, pb, hipMemcpyHostToDevice, s));
+  if ((rc = tas_snapshot_update_wide(ctx, gen_to, n_cols, cols, d_v, d_n, d_p, s))) return rc;
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  return PAS_OK;
+}
+
+int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                        int32_t n_cols, const int32_t* cols,
+                                        const int64_t* d_whole, const uint32_t* d_nano,
+                                        const uint64_t* d_present, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const char* fn = "pas_tas_snapshot_update_wide_device";
+  int rc = check_update(ctx, gen_from, n_cols, cols, d_whole, d_present, fn);
+  if (rc) return rc;
+  if (n_cols > 0 && ctx->tas.n_nodes > 0 && !d_nano)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  if ((rc = activate(ctx))) return rc;
+  return tas_snapshot_update_wide(ctx, gen_to, n_cols, cols, d_whole, d_nano, d_present,
+                                  pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_snapshot_drop(pas_ctx* ctx) {
+  if (!ctx) return PAS_EINVAL;
+  ctx->tas.valid = false;
+  return PAS_OK;
+}
+
+int pas_tas_snapshot_wide_count(const pas_ctx* ctx, int32_t* n_wide) {
+  if (!ctx || !n_wide) return PAS_EINVAL;
+  if (!ctx->tas.valid) return PAS_ENOSNAP;
+  *n_wide = ctx->tas.n_wide;
+  return PAS_OK;
+}
+
+// The top-k records carry one 64-bit merge key per node: no exact key for a wide column yet.
+static int check_no_wide(pas_ctx* ctx, const char* fn) {
+  if (ctx->tas.n_wide == 0) return PAS_OK;
+  size_t m = 0;
+  while (m < ctx->tas.wide_host.size() && !ctx->tas.wide_host[m]) ++m;
+  return set_error(ctx, PAS_ENOTEXACT, std::string(fn) + ": metric column " + std::to_string(m) +
+                                           " is wide (64-bit top-k merge keys cannot order it)");
+}
+
 int pas_tas_snapshot_info(const pas_ctx* ctx, uint64_t* gen, int32_t* n_nodes,
                           int32_t* n_metrics) {
   if (!ctx) return PAS_EINVAL;
@@ -461,6 +536,13 @@ int pas_tas_snapshot_set_scale(pas_ctx* ctx, uint64_t gen, int32_t n_metrics,
     tab[2 * (size_t)m + 1] = INT64_MAX / mult;
   }
   if (M == 0) return PAS_OK;
+  if (ctx->tas.n_wide > 0)  // a wide column keeps its recorded scale
+    for (int32_t m = 0; m < M; ++m)
+      if (ctx->tas.wide_host[(size_t)m]) {
+        tab[2 * (size_t)m] = ctx->tas.scale_host[2 * (size_t)m];
+        tab[2 * (size_t)m + 1] = ctx->tas.scale_host[2 * (size_t)m + 1];
+      }
+  ctx->tas.scale_host = tab;
   if ((rc = activate(ctx))) return rc;
   hipStream_t s = pick_stream(ctx, hip_stream);
   PAS_HIP(ctx, hipMemcpyAsync(ctx->tas.scale_tab, tab.data(), sizeof(int64_t) * tab.size(),
@@ -1285,6 +1367,7 @@ int pas_tas_topk_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_t n_ru
   if (rc) return rc;
   if (n_pods < 0 || n_rules < 0 || k < 1 || node_base < 0)
     return set_error(ctx, PAS_EINVAL, "pas_tas_topk_device: bad shape");
+  if ((rc = check_no_wide(ctx, "pas_tas_topk_device"))) return rc;
   if ((int64_t)node_base + ctx->tas.n_nodes > INT32_MAX)
     return set_error(ctx, PAS_EINVAL, "pas_tas_topk_device: node ids past int32");
   if (n_pods == 0) return PAS_OK;
@@ -1314,6 +1397,7 @@ int pas_tas_gas_topk_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, in
   if (n_pods < 0 || n_rules < 0 || k < 1 || node_base < 0 || max_containers < 0 ||
       i915_index >= ctx->gas.n_res || i915_index < -1)
     return set_error(ctx, PAS_EINVAL, "pas_tas_gas_topk_device: bad shape");
+  if ((rc = check_no_wide(ctx, "pas_tas_gas_topk_device"))) return rc;
   if ((int64_t)node_base + ctx->tas.n_nodes > INT32_MAX)
     return set_error(ctx, PAS_EINVAL, "pas_tas_gas_topk_device: node ids past int32");
   if (n_pods == 0) return PAS_OK;

@@ -59,6 +59,22 @@ struct TasSnapshot {
   // column m holds value * 10^scale[m]: scale_tab[m] = {10^scale, INT64_MAX / 10^scale}
   // (pas_tas_snapshot_set_scale; milli after every snapshot_set)
   int64_t* scale_tab = nullptr;
+  std::vector<int64_t> scale_host;  // the same table on the host (set_scale keeps wide columns')
+  // Wide columns (pas_tas_snapshot_update_wide): the value of node n is vals[m][n] +
+  // nano[m][n] * 1e-9 (vals holds the floor), sorted[m] / f1k / f32 hold the floors in the
+  // exact pair order and sorted_nano / f1k_nano / f32_nano the nanos at the same positions.
+  // Allocated by the first wide update (all null before); wide_flag [M] on the device and
+  // wide_host mark the wide columns, n_wide counts them.  scale_tab keeps a wide column's
+  // recorded scale (the wide compares do not read it).
+  int32_t n_wide = 0;
+  std::vector<uint8_t> wide_host;
+  uint8_t* wide_flag = nullptr;
+  uint32_t* nano = nullptr;         // [M][N]
+  uint32_t* sorted_nano = nullptr;  // [M][R]
+  uint32_t* f1k_nano = nullptr;     // [M][R / 1024]
+  uint32_t* f32_nano = nullptr;     // [M][R / 32]
+  void* wide_sort_tmp = nullptr;    // temp storage of the wide (128-bit key) sort
+  size_t wide_sort_tmp_bytes = 0;
   // build scratch (kept for column updates): sort keys {value, row} and node ids, two
   // buffers each, [M][R]; per-word popcounts and their scan; the updated rows
   void* keys_a = nullptr;
@@ -250,6 +266,11 @@ int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t n_nodes, int32_t n_me
 // d_vals [n_cols][N] / d_present [n_cols][W64] and rebuild their orders.
 int tas_snapshot_update(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
                         const int64_t* d_vals, const uint64_t* d_present, hipStream_t s);
+// The same with wide columns: d_whole [n_cols][N] (floors), d_nano [n_cols][N] (read clamped
+// below 1e9), d_present [n_cols][W64]; the columns become wide.
+int tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
+                             const int64_t* d_whole, const uint32_t* d_nano,
+                             const uint64_t* d_present, hipStream_t s);
 int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
                     const int32_t* d_rule_off, const pas_rule* d_prio, const uint64_t* d_cand,
                     uint32_t flags, uint64_t* d_pass, int32_t* d_order, int32_t* d_len,

@@ -325,6 +325,33 @@ int pas_quantity_to_scaled(const char* quantity, int32_t places, int64_t* out) {
   return PAS_OK;
 }
 
+int pas_quantity_to_wide(const char* quantity, int64_t* whole, uint32_t* nano) {
+  if (!whole || !nano) return PAS_EINVAL;
+  Parsed q;
+  const int rc = pas::parse_quantity(quantity, &q);
+  if (rc != PAS_OK) return rc;
+  __int128 n;  // the value in units of 1e-9 (both forms keep at most 9 fractional digits)
+  if (q.dec) {
+    n = q.nano;
+  } else {  // value * 10^(scale + 9), scale >= -9
+    n = q.value;
+    for (int32_t e = q.scale + 9; e > 0; --e) {
+      n *= 10;
+      if (n > pas::kMaxNano + 999999999 || n < -pas::kMaxNano - 1000000000) return PAS_ENOTEXACT;
+    }
+  }
+  const __int128 kBillion = 1000000000;
+  __int128 w = n / kBillion, f = n % kBillion;
+  if (f < 0) {  // floor: -0.5 is (-1, 500000000)
+    f += kBillion;
+    w -= 1;
+  }
+  if (w > INT64_MAX || w < INT64_MIN) return PAS_ENOTEXACT;
+  *whole = (int64_t)w;
+  *nano = (uint32_t)f;
+  return PAS_OK;
+}
+
 int pas_quantity_to_milli(const char* quantity, int64_t* milli_out) {
   return pas_quantity_to_scaled(quantity, 3, milli_out);
 }

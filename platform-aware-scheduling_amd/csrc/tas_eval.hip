@@ -107,6 +107,12 @@ struct RangesParams {
   const int64_t* f32;     // [M][R / 32]   sorted[m][32 b]
   int2* ranges;
   const int64_t* scale_tab;  // [M][2] the columns' fixed point (target_scaled)
+  // wide columns (read by the kWide prep only): flags [M], and the nanos at the positions of
+  // sorted / f1k / f32
+  const uint8_t* wide_flag;
+  const uint32_t* sorted_nano;
+  const uint32_t* f1k_nano;
+  const uint32_t* f32_nano;
 };
 
 constexpr int kRuleLanes = 8;  // lanes per rule in the range search
@@ -138,6 +144,69 @@ __device__ __forceinline__ void count_below(const int64_t* __restrict__ al, int3
 // of 8 lanes per rule finds both bounds in three dependent rounds of loads: the 1024-stride
 // fences (f1k), the 32-stride fences of one 1024-block (f32), the 32 values of one
 // 32-block; each round counts the window's entries below the target.
+// count_below for a wide column (value = floor + nano * 1e-9, the rows in exact pair order)
+// against the integer target t:  v < t <=> floor < t;  v <= t <=> floor < t or (floor == t
+// and nano == 0).  Both predicates are monotone along the row.  The lower count reads the
+// floors at al, the upper count the floors at au and the nanos at an.
+template <int kMaxPerLane>
+__device__ __forceinline__ void count_below_wide(const int64_t* __restrict__ al, int32_t nl,
+                                                 const int64_t* __restrict__ au,
+                                                 const uint32_t* __restrict__ an, int32_t nu,
+                                                 int64_t t, int gl, uint64_t gmask, int32_t* cl,
+                                                 int32_t* cu) {
+  int32_t sl = 0, su = 0;
+#pragma unroll
+  for (int q = 0; q < kMaxPerLane; ++q) {
+    const int32_t i = gl + q * kRuleLanes;
+    const int64_t vl = al[min(i, max(nl - 1, 0))];
+    const int64_t vu = au[min(i, max(nu - 1, 0))];
+    const uint32_t fu = an[min(i, max(nu - 1, 0))];
+    sl += __popcll(__ballot(i < nl && vl < t) & gmask);
+    su += __popcll(__ballot(i < nu && (vu < t || (vu == t && fu == 0u))) & gmask);
+  }
+  *cl = sl;
+  *cu = su;
+}
+
+// The three rounds of ranges_group for a wide column m with c present nodes: lb = values
+// below t, ub = values not above t.  No saturation: the target is compared as it is.
+__device__ __forceinline__ void wide_bounds(const RangesParams& R, int32_t m, int32_t c,
+                                            int64_t t, int gl, uint64_t gmask, int32_t* lb,
+                                            int32_t* ub) {
+  const int64_t* sv = R.sorted + (int64_t)m * R.R;
+  const int64_t* f1 = R.f1k + (int64_t)m * (R.R >> 10);
+  const int64_t* f2 = R.f32 + (int64_t)m * (R.R >> 5);
+  const uint32_t* svn = R.sorted_nano + (int64_t)m * R.R;
+  const uint32_t* f1n = R.f1k_nano + (int64_t)m * (R.R >> 10);
+  const uint32_t* f2n = R.f32_nano + (int64_t)m * (R.R >> 5);
+  const int32_t na = (c + 1023) >> 10, nb = (c + 31) >> 5;
+  int32_t n1l = 0, n1u = 0;
+  if (na <= 16 * kRuleLanes) {
+    count_below_wide<16>(f1, na, f1, f1n, na, t, gl, gmask, &n1l, &n1u);
+  } else {
+    for (int32_t i0 = 0; i0 < na; i0 += 4 * kRuleLanes) {
+      int32_t a, b;
+      count_below_wide<4>(f1 + i0, na - i0, f1 + i0, f1n + i0, na - i0, t, gl, gmask, &a, &b);
+      n1l += a;
+      n1u += b;
+    }
+  }
+  const int32_t b1l = max(n1l - 1, 0), b1u = max(n1u - 1, 0);
+  int32_t n2l, n2u;
+  count_below_wide<4>(f2 + b1l * 32, n1l ? min(32, nb - b1l * 32) : 0, f2 + b1u * 32,
+                      f2n + b1u * 32, n1u ? min(32, nb - b1u * 32) : 0, t, gl, gmask, &n2l,
+                      &n2u);
+  const int32_t b2l = b1l * 32 + max(n2l - 1, 0), b2u = b1u * 32 + max(n2u - 1, 0);
+  int32_t n3l, n3u;
+  count_below_wide<4>(sv + b2l * 32, n1l ? min(32, c - b2l * 32) : 0, sv + b2u * 32,
+                      svn + b2u * 32, n1u ? min(32, c - b2u * 32) : 0, t, gl, gmask, &n3l, &n3u);
+  *lb = n1l ? b2l * 32 + n3l : 0;
+  *ub = n1u ? b2u * 32 + n3u : 0;
+}
+
+// kWide: the snapshot holds at least one wide column (the host picks the instantiation; the
+// narrow one is the code every snapshot without wide columns runs).
+template <bool kWide>
 __device__ void ranges_group(const RangesParams& R, int32_t r) {
   const int lane = threadIdx.x & 63, gl = lane & (kRuleLanes - 1);
   const uint64_t gmask = 0xFFull << (lane & ~(kRuleLanes - 1));
@@ -147,9 +216,13 @@ __device__ void ranges_group(const RangesParams& R, int32_t r) {
     const int32_t m = rule.metric;
     const int32_t c = R.cnt[m];
     int64_t t = 0;
-    const int sat = target_scaled(rule.target, R.scale_tab, m, &t);
+    bool wide = false;
+    if constexpr (kWide) wide = R.wide_flag[m] != 0;
+    const int sat = wide ? 0 : target_scaled(rule.target, R.scale_tab, m, &t);
     int32_t lb, ub;
-    if (sat != 0) {
+    if (wide) {
+      wide_bounds(R, m, c, rule.target, gl, gmask, &lb, &ub);
+    } else if (sat != 0) {
       lb = ub = sat > 0 ? c : 0;
     } else {
       const int64_t* sv = R.sorted + (int64_t)m * R.R;
@@ -337,6 +410,7 @@ __device__ void group_body(const GroupParams& g, int32_t* sh) {
 #ifndef PAS_PREP_ABLATE
 #define PAS_PREP_ABLATE 0
 #endif
+template <bool kWide = false>
 __global__ __launch_bounds__(kGroupTpb) void tas_prep_kernel(GroupParams g, RangesParams R) {
   extern __shared__ __attribute__((aligned(16))) int32_t sh[];
 #if PAS_PREP_STAMPS
@@ -351,7 +425,7 @@ __global__ __launch_bounds__(kGroupTpb) void tas_prep_kernel(GroupParams g, Rang
   if (PAS_PREP_ABLATE & 1) return;
   const int32_t r =
       (int32_t)(blockIdx.x - 1) * (kGroupTpb / kRuleLanes) + (int32_t)(threadIdx.x / kRuleLanes);
-  if (r < R.n_rules) ranges_group(R, r);
+  if (r < R.n_rules) ranges_group<kWide>(R, r);
 #if PAS_PREP_STAMPS
   __syncthreads();
   if (threadIdx.x == 0 && (blockIdx.x == 1 || blockIdx.x == gridDim.x - 1))
@@ -691,14 +765,24 @@ struct PlanOut {
   int64_t* part;           // [gridDim.x] violated pairs per block
 };
 
-template <int kRun, bool kPlan = false>
+// kWide (the host picks it only while the snapshot holds a wide column): a rule on a wide
+// column also reads the column's nanos over the run and compares the pair exactly against the
+// integer target:  v < t <=> floor < t;  v == t <=> floor == t and nano == 0;  v > t <=>
+// floor > t or (floor == t and nano != 0).
+struct WideCols {
+  const uint8_t* flag;   // [M]
+  const uint32_t* nano;  // [M][N]
+};
+
+template <int kRun, bool kPlan = false, bool kWide = false>
 __global__ __launch_bounds__(kTpb) void tas_violations_run_kernel(
     int32_t N, int32_t M, int32_t W64, int32_t n_strat, int32_t n_rules,
     const int32_t* __restrict__ rule_off,
     const pas_rule* __restrict__ rules, const int64_t* __restrict__ vals,
     const uint64_t* __restrict__ present, const int64_t* __restrict__ scale_tab,
-    uint64_t* __restrict__ viol_out, PlanOut plan) {
+    uint64_t* __restrict__ viol_out, PlanOut plan, WideCols wc) {
   static_assert(kRun <= 64, "one word per lane");
+  constexpr int kNn = kWide ? kRun : 1;
   __shared__ int64_t red[kPlan ? kWaves : 1];
   __shared__ uint64_t vws[kPlan ? kWaves : 1][kPlan ? 64 : 1][kPlan ? kRun : 1];
   __shared__ uint64_t lws[kPlan ? kWaves : 1][kPlan ? 64 : 1][kPlan ? kRun : 1];
@@ -738,7 +822,8 @@ __global__ __launch_bounds__(kTpb) void tas_violations_run_kernel(
   };
   // rule records arrive two rules ahead (scalar loads), so the column loads of the next rule
   // never wait for its record
-  auto load = [&](const pas_rule& ru, int64_t (&v)[kRun], uint64_t* pr) {
+  auto load = [&](const pas_rule& ru, int64_t (&v)[kRun], uint64_t* pr, uint32_t (&nn)[kNn],
+                  bool* wide) {
     const int32_t m = (ru.metric >= 0 && ru.metric < M) ? ru.metric : 0;
     const int64_t* col = vals + (int64_t)m * N;
 #pragma unroll
@@ -747,14 +832,25 @@ __global__ __launch_bounds__(kTpb) void tas_violations_run_kernel(
       v[k] = PAS_VIOL_NT ? __builtin_nontemporal_load(a) : *a;
     }
     *pr = present[(int64_t)m * W64 + pw_lane];
+    if constexpr (kWide) {
+      *wide = ru.metric >= 0 && ru.metric < M && wc.flag[m] != 0;  // wave-uniform
+      if (*wide) {
+        const uint32_t* ncol = wc.nano + (int64_t)m * N;
+#pragma unroll
+        for (int k = 0; k < kRun; ++k)
+          nn[k] = __builtin_nontemporal_load(ncol + min((gw0 + k) * 64 + lane, N - 1));
+      }
+    }
   };
   pas_rule ru{}, ru1{};
   int64_t v[kRun];
+  uint32_t nn[kNn] = {};
+  bool wide = false;
   uint64_t pr = 0;
   if (r_begin < r_end) {  // (no rule records to read otherwise)
     ru = rules[r_begin];
     ru1 = rules[min(r_begin + 1, r_end - 1)];
-    load(ru, v, &pr);
+    load(ru, v, &pr, nn, &wide);
   }
   for (int32_t r = r_begin; r < r_end; ++r) {
     while (r >= s_end) {  // the list has passed strategy s: its words are complete
@@ -765,8 +861,25 @@ __global__ __launch_bounds__(kTpb) void tas_violations_run_kernel(
     const pas_rule ru2 = rules[min(r + 2, r_end - 1)];
     int64_t nv[kRun];
     uint64_t npr;
-    load(ru1, nv, &npr);  // the next run in flight during this rule's compares
-    if (ru.metric >= 0 && ru.metric < M && ru.op >= 0 && ru.op <= 2) {
+    uint32_t nnn[kNn] = {};
+    bool nwide = false;
+    load(ru1, nv, &npr, nnn, &nwide);  // the next run in flight during this rule's compares
+    if (kWide && wide) {
+      if (ru.op >= 0 && ru.op <= 2) {  // (wide: the metric is in range)
+        const int64_t t = ru.target;
+        const bool lt = ru.op == PAS_OP_LESS_THAN, gt = ru.op == PAS_OP_GREATER_THAN;
+#pragma unroll
+        for (int k = 0; k < kRun; ++k) {
+          const bool valid = (gw0 + k) * 64 + lane < N;
+          const bool frac = nn[kWide ? k : 0] != 0u;
+          const bool hit = lt   ? v[k] < t
+                           : gt ? (v[k] > t) | ((v[k] == t) & frac)
+                                : (v[k] == t) & !frac;
+          const uint64_t mask = __ballot(hit & valid);
+          acc = lane == k ? (acc | (mask & pr)) : acc;
+        }
+      }
+    } else if (ru.metric >= 0 && ru.metric < M && ru.op >= 0 && ru.op <= 2) {
       // the rule as the value range it hits, [lo, hi] (empty: lo > hi), once per rule: the
       // word loop is two compares per word, no branch on the operator
       int64_t tm = 0;
@@ -793,6 +906,11 @@ __global__ __launch_bounds__(kTpb) void tas_violations_run_kernel(
     pr = npr;
 #pragma unroll
     for (int k = 0; k < kRun; ++k) v[k] = nv[k];
+    if constexpr (kWide) {
+      wide = nwide;
+#pragma unroll
+      for (int k = 0; k < kRun; ++k) nn[k] = nnn[k];
+    }
   }
   for (; s < n_strat; ++s) flush();  // the last strategy with rules, then those without
   if constexpr (kPlan) {
@@ -927,18 +1045,21 @@ int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
   // ranges (blocks 1..) beside the grouping (block 0), one launch
   const int32_t range_rules = (flags & PAS_TAS_FILTER) ? n_rules : 0;
   RangesParams rp{range_rules, M, t.row, d_rules, t.cnt, t.sorted, t.f1k, t.f32, d_ranges,
-                  t.scale_tab};
+                  t.scale_tab, t.wide_flag, t.sorted_nano, t.f1k_nano, t.f32_nano};
   GroupParams gp{n_pods, M,      flags,  d_prio,        d_rule_off,
                  t.cnt,  d_keys, d_desc, tune.no_group, std::max(n_rules, 0)};
   const size_t group_lds = sizeof(int32_t) * ((size_t)G + 1 + (size_t)M);  // hist | cnt
+  // the wide-aware ranges only while the snapshot holds a wide column
+  void (*const prep)(GroupParams, RangesParams) =
+      t.n_wide > 0 ? &tas_prep_kernel<true> : &tas_prep_kernel<false>;
   if (group_lds > 64 * 1024)
-    PAS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&tas_prep_kernel),
+    PAS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(prep),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)group_lds));
   constexpr int kRulesPerBlock = kGroupTpb / kRuleLanes;
   const unsigned prep_blocks =
       1u + (unsigned)((range_rules + kRulesPerBlock - 1) / kRulesPerBlock);
   timing_begin(ctx, s, PAS_K_TAS_PREP, &tl);
-  tas_prep_kernel<<<prep_blocks, kGroupTpb, group_lds, s>>>(gp, rp);
+  prep<<<prep_blocks, kGroupTpb, group_lds, s>>>(gp, rp);
   timing_end(ctx, s, &tl);
   PAS_HIP(ctx, hipGetLastError());
 
@@ -993,17 +1114,18 @@ int tas_group_launch(pas_ctx* ctx, int32_t n_pods, const pas_rule* d_prio,
     return set_error(ctx, PAS_ECAPACITY, "more than 4096 metric columns");
   const uint32_t flags = PAS_TAS_FILTER | PAS_TAS_PRIORITIZE;
   const int32_t range_rules = d_ranges ? n_rules : 0;
+  // (the top-k entry points refuse a snapshot with wide columns: narrow ranges only)
   RangesParams rp{range_rules, M, t.row, d_rules, t.cnt, t.sorted, t.f1k, t.f32, d_ranges,
-                  t.scale_tab};
+                  t.scale_tab, nullptr, nullptr, nullptr, nullptr};
   GroupParams gp{n_pods, M, flags, d_prio, d_rule_off, t.cnt, d_keys, d_desc, 0,
                  std::max(n_rules, 0)};
   const size_t group_lds = sizeof(int32_t) * ((size_t)3 * M + 1 + (size_t)M);
   if (group_lds > 64 * 1024)
-    PAS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&tas_prep_kernel),
+    PAS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&tas_prep_kernel<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)group_lds));
   constexpr int kRulesPerBlock = kGroupTpb / kRuleLanes;
   const unsigned blocks = 1u + (unsigned)((range_rules + kRulesPerBlock - 1) / kRulesPerBlock);
-  tas_prep_kernel<<<blocks, kGroupTpb, group_lds, s>>>(gp, rp);
+  tas_prep_kernel<false><<<blocks, kGroupTpb, group_lds, s>>>(gp, rp);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
 }
@@ -1022,11 +1144,16 @@ int tas_violations_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,
              : run == 4  ? &tas_violations_run_kernel<4>
              : run == 16 ? &tas_violations_run_kernel<16>
                          : &tas_violations_run_kernel<8>;
-  const int32_t per = (run == 2 || run == 4 || run == 16) ? run : 8;
+  int32_t per = (run == 2 || run == 4 || run == 16) ? run : 8;
+  if (t.n_wide > 0) {  // the wide-aware sweep (one run length) while a column is wide
+    rfn = &tas_violations_run_kernel<8, false, true>;
+    per = 8;
+  }
   const int32_t rwaves = (W64 + per - 1) / per;
   rfn<<<(rwaves + kWaves - 1) / kWaves, kTpb, 0, s>>>(
       t.n_nodes, t.n_metrics, W64, n_strat, std::max(n_rules, 0), d_rule_off, d_rules, t.vals,
-      t.present, t.scale_tab, d_viol, PlanOut{NamePlan{}, nullptr, nullptr, nullptr, nullptr});
+      t.present, t.scale_tab, d_viol, PlanOut{NamePlan{}, nullptr, nullptr, nullptr, nullptr},
+      WideCols{t.wide_flag, t.nano});
   timing_end(ctx, s, &tl);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
@@ -1058,9 +1185,12 @@ int tas_deschedule_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,
   if (!part) return rc;
   TimedLaunch tl;
   timing_begin(ctx, s, PAS_K_TAS_VIOLATIONS, &tl);
-  tas_violations_run_kernel<kRun, true><<<blocks, kTpb, 0, s>>>(
-      N, t.n_metrics, W64, n_strat, std::max(n_rules, 0), d_rule_off, d_rules, t.vals, t.present,
-      t.scale_tab, d_viol, PlanOut{names, d_labels, d_add, d_rem, part});
+  auto dfn = t.n_wide > 0 ? &tas_violations_run_kernel<kRun, true, true>
+                          : &tas_violations_run_kernel<kRun, true, false>;
+  dfn<<<blocks, kTpb, 0, s>>>(N, t.n_metrics, W64, n_strat, std::max(n_rules, 0), d_rule_off,
+                              d_rules, t.vals, t.present, t.scale_tab, d_viol,
+                              PlanOut{names, d_labels, d_add, d_rem, part},
+                              WideCols{t.wide_flag, t.nano});
   timing_end(ctx, s, &tl);
   PAS_HIP(ctx, hipGetLastError());
   return label_total_launch(ctx, blocks, (int64_t)N * __builtin_popcountll(names.canon), part,

@@ -63,6 +63,24 @@ __device__ __forceinline__ int32_t bound(const int64_t* __restrict__ row, int32_
   return lo;
 }
 
+// The same over a wide column's row (floors in row, nanos in nrow, exact pair order) for the
+// pair (v, f): entries below it, or not above it.
+__device__ __forceinline__ int32_t bound_wide(const int64_t* __restrict__ row,
+                                              const uint32_t* __restrict__ nrow, int32_t cnt,
+                                              int64_t v, uint32_t f, bool upper) {
+  int32_t lo = 0, hi = cnt;
+  while (lo < hi) {
+    const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
+    const int64_t x = row[mid];
+    const uint32_t xf = nrow[mid];
+    if (x < v || (x == v && (xf < f || (upper && xf == f)))) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// kWide: the rule's column is wide (nano [M][N] and sorted_nano [M][R] are the snapshot's).
+template <bool kWide>
 __global__ void request_keys_kernel(int32_t n_req, int32_t N, int32_t R, pas_rule rule,
                                     int pb, uint64_t sentinel, const int32_t* __restrict__ req,
                                     const int32_t* __restrict__ first,
@@ -70,6 +88,8 @@ __global__ void request_keys_kernel(int32_t n_req, int32_t N, int32_t R, pas_rul
                                     const uint64_t* __restrict__ present,
                                     const int32_t* __restrict__ cnt,
                                     const int64_t* __restrict__ sorted,
+                                    const uint32_t* __restrict__ nano,
+                                    const uint32_t* __restrict__ sorted_nano,
                                     uint64_t* __restrict__ keys, int32_t* __restrict__ len) {
   const int32_t j = blockIdx.x * kTpb + threadIdx.x;
   bool keep = false;
@@ -86,8 +106,16 @@ __global__ void request_keys_kernel(int32_t n_req, int32_t N, int32_t R, pas_rul
           const int64_t v = vals[(int64_t)rule.metric * N + n];
           const int32_t c = cnt[rule.metric];
           const int64_t* row = sorted + (int64_t)rule.metric * R;
-          rank = rule.op == PAS_OP_LESS_THAN ? (uint64_t)bound(row, c, v, false)
-                                             : (uint64_t)(c - bound(row, c, v, true));
+          if constexpr (kWide) {
+            const uint32_t f = nano[(int64_t)rule.metric * N + n];
+            const uint32_t* nrow = sorted_nano + (int64_t)rule.metric * R;
+            rank = rule.op == PAS_OP_LESS_THAN
+                       ? (uint64_t)bound_wide(row, nrow, c, v, f, false)
+                       : (uint64_t)(c - bound_wide(row, nrow, c, v, f, true));
+          } else {
+            rank = rule.op == PAS_OP_LESS_THAN ? (uint64_t)bound(row, c, v, false)
+                                               : (uint64_t)(c - bound(row, c, v, true));
+          }
         }
         key = rank << pb | (uint64_t)j;
       }
@@ -163,9 +191,11 @@ int prio_request_launch(pas_ctx* ctx, const pas_rule& rule, int32_t n_req,
   TimedLaunch tl;
   timing_begin(ctx, s, PAS_K_PRIO_REQUEST, &tl);
   first_pos_kernel<<<blocks_for(n_req), kTpb, 0, s>>>(n_req, N, d_req, first);
-  request_keys_kernel<<<blocks_for(n_req), kTpb, 0, s>>>(
-      n_req, N, t.row, rule, b.pb, sentinel, d_req, first, t.vals, t.present, t.cnt, t.sorted,
-      keys_a, d_len);
+  const bool wide = t.n_wide > 0 && t.wide_host[(size_t)rule.metric];
+  auto kfn = wide ? &request_keys_kernel<true> : &request_keys_kernel<false>;
+  kfn<<<blocks_for(n_req), kTpb, 0, s>>>(n_req, N, t.row, rule, b.pb, sentinel, d_req, first,
+                                         t.vals, t.present, t.cnt, t.sorted, t.nano,
+                                         t.sorted_nano, keys_a, d_len);
   PAS_HIP(ctx, rocprim::radix_sort_keys(p, tmp, keys_a, keys_b, (size_t)n_req, 0, b.rb + b.pb,
                                         s));
   request_positions_kernel<<<blocks_for(n_req), kTpb, 0, s>>>(n_req, mask, keys_b, d_len, d_pos);

@@ -52,6 +52,15 @@ struct SortKeyBits {
     return rocprim::tuple<uint32_t&, int64_t&>(k.c, k.v);
   }
 };
+// Wide columns (value = v + pad * 1e-9, v the floor): pad carries the nanos below the floor,
+// so the key order is the exact order of the pairs.  A sort instantiation of its own: the
+// narrow build keeps its 64 + column bits.  Pads carry {INT64_MAX, 0xffffffff}.
+struct WideKeyBits {
+  __host__ __device__ rocprim::tuple<uint32_t&, int64_t&, uint32_t&> operator()(SortKey& k) const {
+    return rocprim::tuple<uint32_t&, int64_t&, uint32_t&>(k.c, k.v, k.pad);
+  }
+};
+constexpr uint32_t kNanoMax = 999999999u;
 
 __device__ __forceinline__ int32_t row_of(const int32_t* rows, int32_t c) {
   return rows ? rows[c] : c;
@@ -71,9 +80,12 @@ __global__ void popc_words(const uint64_t* __restrict__ present, int64_t total_w
   popc[i] = i < total_words ? (uint32_t)__popcll(word_mask(present[i], i % W, N)) : 0u;
 }
 
-// One thread per (column c, order position j < R).
+// One thread per (column c, order position j < R).  kWide: nano [M][N] are the snapshot's
+// rows (already clamped), read at the column's row.
+template <bool kWide>
 __global__ void compact_keys(const uint64_t* __restrict__ present,
-                             const int64_t* __restrict__ vals, const uint32_t* __restrict__ scan,
+                             const int64_t* __restrict__ vals,
+                             const uint32_t* __restrict__ nano, const uint32_t* __restrict__ scan,
                              const int32_t* __restrict__ rows, int32_t C, int32_t N, int32_t R,
                              int64_t W, int32_t MR, SortKey* __restrict__ keys,
                              int32_t* __restrict__ ids, int32_t* __restrict__ perm_index) {
@@ -91,13 +103,14 @@ __global__ void compact_keys(const uint64_t* __restrict__ present,
     if ((bits >> (j & 63)) & 1ull) {
       const int32_t pos = (int32_t)(scan[(int64_t)c * W + w] - base) +
                           __popcll(bits & ((1ull << (j & 63)) - 1ull));
-      keys[out + pos] = SortKey{vals[(int64_t)c * N + j], (uint32_t)c, 0u};
+      keys[out + pos] =
+          SortKey{vals[(int64_t)c * N + j], (uint32_t)c, kWide ? nano[m * N + j] : 0u};
       ids[out + pos] = j;
       perm_index[(int64_t)kOrderIndex * MR + m * R + pos] = j;
     }
   }
   if (j >= cnt) {
-    keys[out + j] = SortKey{INT64_MAX, (uint32_t)c, 0u};
+    keys[out + j] = SortKey{INT64_MAX, (uint32_t)c, kWide ? 0xffffffffu : 0u};
     ids[out + j] = sentinel;
     perm_index[(int64_t)kOrderIndex * MR + m * R + j] = sentinel;
   }
@@ -126,6 +139,53 @@ __global__ void place_asc(const SortKey* __restrict__ skeys, const int32_t* __re
   }
   if (j == 0) cnt_out[m] = cnt;
   if (j < cnt) keys[i].v = ~keys[i].v;  // v1 < v2 <=> ~v1 > ~v2 (no overflow)
+}
+
+// The same for a wide column: floors and nanos of the sorted pairs side by side, fences of
+// both; the descending keys complement both fields.
+__global__ void place_asc_wide(const SortKey* __restrict__ skeys,
+                               const int32_t* __restrict__ sids, SortKey* __restrict__ keys,
+                               const uint32_t* __restrict__ scan,
+                               const int32_t* __restrict__ rows, int32_t C, int32_t R, int64_t W,
+                               int32_t MR, int64_t* __restrict__ sorted,
+                               uint32_t* __restrict__ sorted_nano, int32_t* __restrict__ perm,
+                               int32_t* __restrict__ cnt_out, int64_t* __restrict__ f1k,
+                               int64_t* __restrict__ f32, uint32_t* __restrict__ f1k_nano,
+                               uint32_t* __restrict__ f32_nano) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (i >= (int64_t)C * R) return;
+  const int32_t c = (int32_t)(i / R), j = (int32_t)(i % R);
+  const int64_t m = row_of(rows, c);
+  const int32_t cnt = (int32_t)(scan[(int64_t)(c + 1) * W] - scan[(int64_t)c * W]);
+  const SortKey k = skeys[i];
+  sorted[m * R + j] = k.v;
+  sorted_nano[m * R + j] = k.pad;
+  perm[(int64_t)kOrderAsc * MR + m * R + j] = sids[i];
+  if ((j & 31) == 0) {
+    const int64_t f = j < cnt ? k.v : 0;
+    const uint32_t fn = j < cnt ? k.pad : 0u;
+    f32[m * (R >> 5) + (j >> 5)] = f;
+    f32_nano[m * (R >> 5) + (j >> 5)] = fn;
+    if ((j & 1023) == 0) {
+      f1k[m * (R >> 10) + (j >> 10)] = f;
+      f1k_nano[m * (R >> 10) + (j >> 10)] = fn;
+    }
+  }
+  if (j == 0) cnt_out[m] = cnt;
+  if (j < cnt) {
+    keys[i].v = ~keys[i].v;
+    keys[i].pad = ~keys[i].pad;
+  }
+}
+
+// nano [C][N] of an update into the snapshot's rows, clamped below 1e9 (the device form
+// cannot check it on the host).
+__global__ void clamp_nano(const uint32_t* __restrict__ in, const int32_t* __restrict__ rows,
+                           int32_t C, int32_t N, uint32_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (i >= (int64_t)C * N) return;
+  const int32_t c = (int32_t)(i / N), j = (int32_t)(i % N);
+  out[(int64_t)rows[c] * N + j] = min(in[i], kNanoMax);
 }
 
 __global__ void place_desc(const int32_t* __restrict__ sids, const int32_t* __restrict__ rows,
@@ -161,8 +221,8 @@ int build_columns(pas_ctx* ctx, int32_t C, const int32_t* d_rows, const int64_t*
                                        (size_t)(cw + 1), rocprim::plus<uint32_t>(), s));
   SortKey* ka = static_cast<SortKey*>(t.keys_a);
   SortKey* kb = static_cast<SortKey*>(t.keys_b);
-  compact_keys<<<blocks_for(cr), kTpb, 0, s>>>(present, vals, t.word_scan, d_rows, C, N, R, W, MR,
-                                              ka, t.ids_a, t.perm);
+  compact_keys<false><<<blocks_for(cr), kTpb, 0, s>>>(present, vals, nullptr, t.word_scan, d_rows,
+                                                     C, N, R, W, MR, ka, t.ids_a, t.perm);
   PAS_HIP(ctx, hipGetLastError());
   const unsigned end_bit = 64 + bits_for(C);
   size_t sort_bytes = t.sort_tmp_bytes;
@@ -176,6 +236,83 @@ int build_columns(pas_ctx* ctx, int32_t C, const int32_t* d_rows, const int64_t*
                                          (size_t)cr, SortKeyBits{}, 0u, end_bit, s));
   place_desc<<<blocks_for(cr), kTpb, 0, s>>>(t.ids_b, d_rows, C, R, MR, t.perm);
   PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
+}
+
+// The same for wide columns: vals [C][N] the floors, the nanos already in t.nano's rows.
+int build_columns_wide(pas_ctx* ctx, int32_t C, const int32_t* d_rows, const int64_t* vals,
+                       const uint64_t* present, hipStream_t s) {
+  TasSnapshot& t = ctx->tas;
+  const int32_t N = t.n_nodes, R = t.row;
+  const int64_t W = w64(N);
+  const int32_t MR = t.n_metrics * R;
+  const int64_t cw = (int64_t)C * W;
+  const int64_t cr = (int64_t)C * R;
+  popc_words<<<blocks_for(cw + 1), kTpb, 0, s>>>(present, cw, N, W, t.popc);
+  PAS_HIP(ctx, hipGetLastError());
+  size_t scan_bytes = t.scan_tmp_bytes;
+  PAS_HIP(ctx, rocprim::exclusive_scan(t.scan_tmp, scan_bytes, t.popc, t.word_scan, 0u,
+                                       (size_t)(cw + 1), rocprim::plus<uint32_t>(), s));
+  SortKey* ka = static_cast<SortKey*>(t.keys_a);
+  SortKey* kb = static_cast<SortKey*>(t.keys_b);
+  compact_keys<true><<<blocks_for(cr), kTpb, 0, s>>>(present, vals, t.nano, t.word_scan, d_rows,
+                                                    C, N, R, W, MR, ka, t.ids_a, t.perm);
+  PAS_HIP(ctx, hipGetLastError());
+  const unsigned end_bit = 96 + bits_for(C);
+  size_t sort_bytes = t.wide_sort_tmp_bytes;
+  PAS_HIP(ctx, rocprim::radix_sort_pairs(t.wide_sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
+                                         (size_t)cr, WideKeyBits{}, 0u, end_bit, s));
+  place_asc_wide<<<blocks_for(cr), kTpb, 0, s>>>(kb, t.ids_b, ka, t.word_scan, d_rows, C, R, W,
+                                                MR, t.sorted, t.sorted_nano, t.perm, t.cnt,
+                                                t.f1k, t.f32, t.f1k_nano, t.f32_nano);
+  PAS_HIP(ctx, hipGetLastError());
+  sort_bytes = t.wide_sort_tmp_bytes;
+  PAS_HIP(ctx, rocprim::radix_sort_pairs(t.wide_sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
+                                         (size_t)cr, WideKeyBits{}, 0u, end_bit, s));
+  place_desc<<<blocks_for(cr), kTpb, 0, s>>>(t.ids_b, d_rows, C, R, MR, t.perm);
+  PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
+}
+
+// Storage of the wide parts, on the first wide column of a snapshot shape.
+int ensure_wide(pas_ctx* ctx, hipStream_t s) {
+  TasSnapshot& t = ctx->tas;
+  if (t.wide_flag) return PAS_OK;
+  const size_t mn = (size_t)std::max<int64_t>((int64_t)t.n_metrics * t.n_nodes, 1);
+  const size_t mr = (size_t)std::max<int64_t>((int64_t)t.n_metrics * t.row, 1);
+  const size_t mm = (size_t)std::max(t.n_metrics, 1);
+  PAS_HIP(ctx, hipMalloc(&t.nano, sizeof(uint32_t) * mn));
+  PAS_HIP(ctx, hipMalloc(&t.sorted_nano, sizeof(uint32_t) * mr));
+  PAS_HIP(ctx, hipMalloc(&t.f1k_nano, sizeof(uint32_t) * (mr / 1024 + 1)));
+  PAS_HIP(ctx, hipMalloc(&t.f32_nano, sizeof(uint32_t) * (mr / 32 + 1)));
+  size_t sort_bytes = 0;
+  SortKey* ka = static_cast<SortKey*>(t.keys_a);
+  SortKey* kb = static_cast<SortKey*>(t.keys_b);
+  PAS_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, ka, kb, t.ids_a, t.ids_b,
+                                         (size_t)mr, WideKeyBits{}, 0u,
+                                         96 + bits_for(std::max(t.n_metrics, 1)), s));
+  t.wide_sort_tmp_bytes = std::max<size_t>(sort_bytes, 16);
+  PAS_HIP(ctx, hipMalloc(&t.wide_sort_tmp, t.wide_sort_tmp_bytes));
+  PAS_HIP(ctx, hipMalloc(&t.wide_flag, mm));
+  PAS_HIP(ctx, hipMemsetAsync(t.wide_flag, 0, mm, s));
+  return PAS_OK;
+}
+
+// Columns cols[0 .. n_cols) become wide (1) or narrow (0): host marks, count, device flags.
+// Nothing to do (and nothing touched) while the snapshot has never held a wide column.
+int mark_wide(pas_ctx* ctx, int32_t n_cols, const int32_t* cols, uint8_t wide, hipStream_t s) {
+  TasSnapshot& t = ctx->tas;
+  if (!t.wide_flag) return PAS_OK;
+  bool changed = false;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    uint8_t& f = t.wide_host[(size_t)cols[c]];
+    changed |= f != wide;
+    t.n_wide += (int32_t)wide - (int32_t)f;
+    f = wide;
+  }
+  if (changed)  // wide_host lives as long as the snapshot; callers synchronize s after this
+    PAS_HIP(ctx, hipMemcpyAsync(t.wide_flag, t.wide_host.data(), (size_t)t.n_metrics,
+                                hipMemcpyHostToDevice, s));
   return PAS_OK;
 }
 
@@ -239,6 +376,15 @@ int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t N, int32_t M,
     t.n_metrics = M;
     t.row = R;
   }
+  t.scale_host.assign(2 * (size_t)M, 0);
+  for (int32_t m = 0; m < M; ++m) {
+    t.scale_host[2 * (size_t)m] = 1000;
+    t.scale_host[2 * (size_t)m + 1] = INT64_MAX / 1000;
+  }
+  // every column narrow again
+  t.wide_host.assign((size_t)M, 0);
+  t.n_wide = 0;
+  if (t.wide_flag) PAS_HIP(ctx, hipMemsetAsync(t.wide_flag, 0, (size_t)std::max(M, 1), s));
   if (M > 0) {
     // every column milli until pas_tas_snapshot_set_scale says otherwise
     scale_fill_kernel<<<(M + 255) / 256, 256, 0, s>>>(t.scale_tab, M);
@@ -274,9 +420,48 @@ int tas_snapshot_update(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_
     // cols is a caller-owned host array: wait for its copy before returning
     PAS_HIP(ctx, hipMemcpyAsync(t.rows, cols, sizeof(int32_t) * n_cols, hipMemcpyHostToDevice,
                                 s));
+    // a wide column refreshed here is narrow again, at its recorded scale
+    if (int rc = mark_wide(ctx, n_cols, cols, 0, s)) return rc;
     PAS_HIP(ctx, hipStreamSynchronize(s));
     t.valid = false;
     if (int rc = build_columns(ctx, n_cols, t.rows, d_vals, d_present, s)) return rc;
+  }
+  t.gen = gen;
+  t.valid = true;
+  ++t.epoch;
+  return PAS_OK;
+}
+
+int tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
+                             const int64_t* d_whole, const uint32_t* d_nano,
+                             const uint64_t* d_present, hipStream_t s) {
+  TasSnapshot& t = ctx->tas;
+  const int32_t N = t.n_nodes;
+  const int64_t W = w64(N);
+  if (n_cols > 0) {
+    if (int rc = ensure_wide(ctx, s)) {
+      t.valid = false;
+      return rc;
+    }
+    for (int32_t c = 0; c < n_cols && N > 0; ++c) {
+      const int64_t m = cols[c];
+      PAS_HIP(ctx, hipMemcpyAsync(t.vals + m * N, d_whole + (int64_t)c * N, sizeof(int64_t) * N,
+                                  hipMemcpyDeviceToDevice, s));
+      PAS_HIP(ctx, hipMemcpyAsync(t.present + m * W, d_present + (int64_t)c * W,
+                                  sizeof(uint64_t) * W, hipMemcpyDeviceToDevice, s));
+    }
+    PAS_HIP(ctx, hipMemcpyAsync(t.rows, cols, sizeof(int32_t) * n_cols, hipMemcpyHostToDevice,
+                                s));
+    if (int rc = mark_wide(ctx, n_cols, cols, 1, s)) return rc;
+    // cols is a caller-owned host array: wait for its copy before returning
+    PAS_HIP(ctx, hipStreamSynchronize(s));
+    t.valid = false;
+    if (N > 0) {
+      clamp_nano<<<blocks_for((int64_t)n_cols * N), kTpb, 0, s>>>(d_nano, t.rows, n_cols, N,
+                                                                 t.nano);
+      PAS_HIP(ctx, hipGetLastError());
+    }
+    if (int rc = build_columns_wide(ctx, n_cols, t.rows, d_whole, d_present, s)) return rc;
   }
   t.gen = gen;
   t.valid = true;

@@ -126,6 +126,12 @@ SIGNATURES = {
     "pas_tas_snapshot_update": (c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P]),
     "pas_tas_snapshot_update_device": (
         c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P]),
+    "pas_quantity_to_wide": (c_int, [c_char_p, POINTER(c_int64), POINTER(c_uint32)]),
+    "pas_tas_snapshot_update_wide": (c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P]),
+    "pas_tas_snapshot_update_wide_device": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P]),
+    "pas_tas_snapshot_wide_count": (c_int, [_P, POINTER(c_int32)]),
+    "pas_tas_snapshot_drop": (c_int, [_P]),
     "pas_tas_snapshot_info":(c_int, [_P, POINTER(c_uint64), POINTER(c_int32), POINTER(c_int32)]),
     "pas_tas_snapshot_set_scale": (c_int, [_P, c_uint64, c_int32, _P, _P]),
     "pas_tas_eval": (c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, c_uint32, _P, _P, _P]),

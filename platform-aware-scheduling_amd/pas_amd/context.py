@@ -82,6 +82,18 @@ def quantity_to_scaled(q: str, places: int) -> int:
     return out.value
 
 
+def quantity_to_wide(q: str) -> Tuple[int, int]:
+    """(whole, nano) of a resource.Quantity string: value = whole + nano * 1e-9 exactly, whole
+    the floor, 0 <= nano < 10^9; PasError(PAS_ENOTEXACT) only when the integer part is outside
+    int64."""
+    whole = c_int64()
+    nano = ctypes.c_uint32()
+    rc = _lib.load().pas_quantity_to_wide(q.encode(), byref(whole), byref(nano))
+    if rc != _lib.PAS_OK:
+        raise PasError(rc, f"quantity {q!r}")
+    return whole.value, nano.value
+
+
 def quantity_decimals(q: str) -> int:
     """The fewest decimal places (0..9) that hold the parsed quantity exactly."""
     out = ctypes.c_int32()
@@ -225,6 +237,55 @@ class Context:
         self._check(self._l.pas_tas_snapshot_update_device(
             self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None, _dptr(v_t),
             _dptr(p_t), _stream(stream)), "pas_tas_snapshot_update_device")
+
+    def tas_snapshot_update_wide(self, gen_from: int, gen_to: int, cols, whole: np.ndarray,
+                                 nano: np.ndarray, present: np.ndarray):
+        """Replace metric columns `cols` with wide columns: value = whole + nano * 1e-9
+        (pas_tas_snapshot_update_wide; whole int64, nano uint32 < 10^9, [len(cols)][N])."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        w = np.ascontiguousarray(whole, dtype=np.int64).reshape(len(cols), self.n_nodes)
+        f = np.ascontiguousarray(nano, dtype=np.uint32).reshape(len(cols), self.n_nodes)
+        p = np.ascontiguousarray(present, dtype=np.uint64).reshape(len(cols), w64(self.n_nodes))
+        self._check(self._l.pas_tas_snapshot_update_wide(
+            self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None,
+            _ptr(w) if w.size else None, _ptr(f) if f.size else None,
+            _ptr(p) if p.size else None), "pas_tas_snapshot_update_wide")
+
+    def tas_snapshot_update_wide_device(self, gen_from: int, gen_to: int, cols, whole_t, nano_t,
+                                        p_t, stream=None):
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        self._check(self._l.pas_tas_snapshot_update_wide_device(
+            self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None,
+            _dptr(whole_t), _dptr(nano_t), _dptr(p_t), _stream(stream)),
+            "pas_tas_snapshot_update_wide_device")
+
+    def tas_snapshot_wide_count(self) -> int:
+        """Number of wide columns of the resident snapshot."""
+        n = c_int32()
+        self._check(self._l.pas_tas_snapshot_wide_count(self._h, byref(n)),
+                    "pas_tas_snapshot_wide_count")
+        return n.value
+
+    def tas_snapshot_set_wide(self, gen: int, v: np.ndarray, present: np.ndarray, scale, wide):
+        """Install what snapshot.tas_snapshot_from_metrics_wide returns: the narrow columns at
+        their scales, then the wide columns {m: (whole [N], nano [N])}, ending at generation
+        gen.  The set itself carries an intermediate generation (gen with the top bit flipped)
+        that no caller evaluates against; if the wide update fails the context is left without
+        a TAS snapshot."""
+        if not wide:
+            self.tas_snapshot_set(gen, v, present, scale)
+            return
+        mid = gen ^ (1 << 63)
+        cols = sorted(wide)
+        whole = np.stack([np.asarray(wide[m][0], dtype=np.int64) for m in cols])
+        nano = np.stack([np.asarray(wide[m][1], dtype=np.uint32) for m in cols])
+        p = np.ascontiguousarray(present, dtype=np.uint64)
+        self.tas_snapshot_set(mid, v, p, scale)
+        try:
+            self.tas_snapshot_update_wide(mid, gen, cols, whole, nano, p[cols])
+        except Exception:
+            self._l.pas_tas_snapshot_drop(self._h)
+            raise
 
     def tas_snapshot_info(self):
         g = c_uint64()

@@ -27,7 +27,8 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .context import quantity_as_int64, quantity_decimals, quantity_to_scaled, w64
+from .context import (quantity_as_int64, quantity_decimals, quantity_to_scaled,
+                      quantity_to_wide, w64)
 
 GPU_LIST_LABEL = "gpu.intel.com/cards"
 RESOURCE_PREFIX = "gpu.intel.com/"
@@ -62,6 +63,48 @@ def tas_snapshot_from_metrics(metrics: Mapping[str, Mapping[str, str]],
                                             "outside int64") from None
             present[j, i >> 6] |= np.uint64(1 << (i & 63))
     return v, present, scale
+
+
+def tas_snapshot_from_metrics_wide(metrics: Mapping[str, Mapping[str, str]],
+                                   node_names: Sequence[str],
+                                   metric_names: Optional[Sequence[str]] = None):
+    """(v, present, scale, wide) for Context.tas_snapshot_set_wide: every column on which
+    tas_snapshot_from_metrics succeeds is exactly that function's column; any other column
+    (its values do not all fit int64 at one decimal scale) is zero in v, keeps its presence
+    bits, and has an entry wide[m] = (whole [N] int64, nano [N] uint32), value = whole +
+    nano * 1e-9 with whole the floor (pas_quantity_to_wide).  PasError(PAS_ENOTEXACT), naming
+    the metric, only for a value whose integer part is outside int64."""
+    metric_names = list(metrics) if metric_names is None else list(metric_names)
+    index = {n: i for i, n in enumerate(node_names)}
+    n, m = len(node_names), len(metric_names)
+    v = np.zeros((m, n), np.int64)
+    present = np.zeros((m, w64(n)), np.uint64)
+    scale = np.full(m, 3, np.int32)
+    wide = {}
+    for j, name in enumerate(metric_names):
+        try:
+            cv, cp, cs = tas_snapshot_from_metrics(metrics, node_names, [name])
+            v[j], present[j], scale[j] = cv[0], cp[0], cs[0]
+            continue
+        except _lib.PasError as e:
+            if e.code != _lib.PAS_ENOTEXACT:
+                raise
+        whole = np.zeros(n, np.int64)
+        nano = np.zeros(n, np.uint32)
+        for node, q in metrics.get(name, {}).items():
+            if node not in index:
+                continue
+            i = index[node]
+            try:
+                whole[i], nano[i] = quantity_to_wide(q)
+            except _lib.PasError as e:
+                if e.code != _lib.PAS_ENOTEXACT:
+                    raise
+                raise _lib.PasError(e.code, f"metric {name!r}: the integer part of {q!r} is "
+                                            "outside int64") from None
+            present[j, i >> 6] |= np.uint64(1 << (i & 63))
+        wide[j] = (whole, nano)
+    return v, present, scale, wide
 
 
 def go_sort_strings(names):
