@@ -396,26 +396,40 @@ static int check_update(pas_ctx* ctx, uint64_t gen_from, int32_t n_cols, const i
   return PAS_OK;
 }
 
+// The host forms' staging: the columns (nano with the wide form only) into the context's
+// scratch, the update on the context's stream, and its end awaited.
+static int stage_update(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols, const int32_t* cols,
+                        const int64_t* vals, const uint32_t* nano, const uint64_t* present,
+                        bool wide) {
+  int rc = activate(ctx);
+  if (rc) return rc;
+  const int32_t N = ctx->tas.n_nodes;
+  const size_t vb = sizeof(int64_t) * (size_t)n_cols * N;
+  const size_t nb = wide ? sizeof(uint32_t) * (size_t)n_cols * N : 0;
+  const size_t pb = sizeof(uint64_t) * (size_t)n_cols * w64(N);
+  if ((rc = ensure_scratch(ctx, carve_size({vb, nb, pb})))) return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int64_t* d_v = cv.take<int64_t>(vb / sizeof(int64_t));
+  uint32_t* d_n = cv.take<uint32_t>(nb / sizeof(uint32_t));
+  uint64_t* d_p = cv.take<uint64_t>(pb / sizeof(uint64_t));
+  hipStream_t s = ctx->stream;
+  if (vb) PAS_HIP(ctx, hipMemcpyAsync(d_v, vals, vb, hipMemcpyHostToDevice, s));
+  if (nb) PAS_HIP(ctx, hipMemcpyAsync(d_n, nano, nb, hipMemcpyHostToDevice, s));
+  if (pb) PAS_HIP(ctx, hipMemcpyAsync(d_p, present, pb, hipMemcpyHostToDevice, s));
+  rc = wide ? tas_snapshot_update_wide(ctx, gen_to, n_cols, cols, d_v, d_n, d_p, s)
+            : tas_snapshot_update(ctx, gen_to, n_cols, cols, d_v, d_p, s);
+  if (rc) return rc;
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  return PAS_OK;
+}
+
 int pas_tas_snapshot_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_cols,
                             const int32_t* cols, const int64_t* v_milli,
                             const uint64_t* present) {
   if (!ctx) return PAS_EINVAL;
   int rc = check_update(ctx, gen_from, n_cols, cols, v_milli, present, "pas_tas_snapshot_update");
   if (rc) return rc;
-  if ((rc = activate(ctx))) return rc;
-  const int32_t N = ctx->tas.n_nodes;
-  const size_t vb = sizeof(int64_t) * (size_t)n_cols * N;
-  const size_t pb = sizeof(uint64_t) * (size_t)n_cols * w64(N);
-  if ((rc = ensure_scratch(ctx, carve_size({vb, pb})))) return rc;
-  Carve cv{static_cast<char*>(ctx->scratch)};
-  int64_t* d_v = cv.take<int64_t>((size_t)n_cols * N);
-  uint64_t* d_p = cv.take<uint64_t>((size_t)n_cols * w64(N));
-  hipStream_t s = ctx->stream;
-  if (vb) PAS_HIP(ctx, hipMemcpyAsync(d_v, v_milli, vb, hipMemcpyHostToDevice, s));
-  if (pb) PAS_HIP(ctx, hipMemcpyAsync(d_p, present, pb, hipMemcpyHostToDevice, s));
-  if ((rc = tas_snapshot_update(ctx, gen_to, n_cols, cols, d_v, d_p, s))) return rc;
-  PAS_HIP(ctx, hipStreamSynchronize(s));
-  return PAS_OK;
+  return stage_update(ctx, gen_to, n_cols, cols, v_milli, nullptr, present, false);
 }
 
 int pas_tas_snapshot_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
@@ -444,22 +458,7 @@ int pas_tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_t
       return set_error(ctx, PAS_EINVAL, std::string(fn) + ": nano of column " +
                                             std::to_string(cols[i / N]) + ", node " +
                                             std::to_string(i % N) + " is not below 10^9");
-  if ((rc = activate(ctx))) return rc;
-  const size_t vb = sizeof(int64_t) * (size_t)n_cols * N;
-  const size_t nb = sizeof(uint32_t) * (size_t)n_cols * N;
-  const size_t pb = sizeof(uint64_t) * (size_t)n_cols * w64(N);
-  if ((rc = ensure_scratch(ctx, carve_size({vb, nb, pb})))) return rc;
-  Carve cv{static_cast<char*>(ctx->scratch)};
-  int64_t* d_v = cv.take<int64_t>((size_t)n_cols * N);
-  uint32_t* d_n = cv.take<uint32_t>((size_t)n_cols * N);
-  uint64_t* d_p = cv.take<uint64_t>((size_t)n_cols * w64(N));
-  hipStream_t s = ctx->stream;
-  if (vb) PAS_HIP(ctx, hipMemcpyAsync(d_v, whole, vb, hipMemcpyHostToDevice, s));
-  if (nb) PAS_HIP(ctx, hipMemcpyAsync(d_n, nano, nb, hipMemcpyHostToDevice, s));
-  if (pb) PAS_HIP(ctx, hipMemcpyAsync(d_p, present, pb, hipMemcpyHostToDevice, s));
-  if ((rc = tas_snapshot_update_wide(ctx, gen_to, n_cols, cols, d_v, d_n, d_p, s))) return rc;
-  PAS_HIP(ctx, hipStreamSynchronize(s));
-  return PAS_OK;
+  return stage_update(ctx, gen_to, n_cols, cols, whole, nano, present, true);
 }
 
 int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,

@@ -114,6 +114,32 @@ __device__ __forceinline__ int target_scaled(int64_t t, const int64_t* __restric
   return 0;
 }
 
+// The same compares for a wide column's pair (value = whole + nano * 1e-9, whole the floor,
+// nano < 1e9) against the integer target t, exact in 64-bit arithmetic.  "Above" is
+// ceil(value) > t without forming ceil = whole + (nano != 0), which a pair (2^63 - 1,
+// nano != 0) would overflow; the target is compared as it is (no scale, no saturation), so
+// whole = -2^63 is ordinary too.
+__device__ __forceinline__ bool wide_below(int64_t whole, uint32_t, int64_t t) {
+  return whole < t;
+}
+__device__ __forceinline__ bool wide_equal(int64_t whole, uint32_t nano, int64_t t) {
+  return whole == t && nano == 0u;
+}
+__device__ __forceinline__ bool wide_not_above(int64_t whole, uint32_t nano, int64_t t) {
+  return whole < t || wide_equal(whole, nano, t);
+}
+__device__ __forceinline__ bool wide_above(int64_t whole, uint32_t nano, int64_t t) {
+  return whole > t || (whole == t && nano != 0u);
+}
+// A pair against the pair (v, f), in the columns' order: whole signed, then nano unsigned.
+__device__ __forceinline__ bool pair_below(int64_t whole, uint32_t nano, int64_t v, uint32_t f) {
+  return whole < v || (whole == v && nano < f);
+}
+__device__ __forceinline__ bool pair_not_above(int64_t whole, uint32_t nano, int64_t v,
+                                               uint32_t f) {
+  return whole < v || (whole == v && nano <= f);
+}
+
 struct GasSnapshot {
   bool valid = false;
   uint64_t gen = 0;

@@ -117,93 +117,90 @@ struct RangesParams {
 
 constexpr int kRuleLanes = 8;  // lanes per rule in the range search
 
-// Numbers of entries of a[0..n) below t (cl: v < t) and not above t (cu: v <= t), for an
-// ascending a, counted by the rule's lane group (gl = lane within the group, gmask = the
-// group's lanes) with every load of the window in flight at once.
-template <int kMaxPerLane>
-__device__ __forceinline__ void count_below(const int64_t* __restrict__ al, int32_t nl,
-                                            const int64_t* __restrict__ au, int32_t nu,
-                                            int64_t t, int gl, uint64_t gmask, int32_t* cl,
-                                            int32_t* cu) {
+// An ascending row of a column as the range search reads it: entry i, and whether an entry
+// is below the target t (v < t) or not above it (v <= t).  Narrow: one int64 row.
+struct NarrowRow {
+  const int64_t* v;
+  __device__ __forceinline__ NarrowRow at(int32_t i) const { return {v + i}; }
+  __device__ __forceinline__ int64_t load(int32_t i) const { return v[i]; }
+  static __device__ __forceinline__ bool below(int64_t x, int64_t t) { return x < t; }
+  static __device__ __forceinline__ bool not_above(int64_t x, int64_t t) { return x <= t; }
+};
+// Wide (value = floor + nano * 1e-9, the rows in exact pair order): floors and nanos side by
+// side.  Both predicates are monotone along the row; "below" needs the floor alone, so a
+// lower count loads no nano.
+struct WideRow {
+  struct Pair {
+    int64_t whole;
+    uint32_t nano;
+  };
+  const int64_t* v;
+  const uint32_t* n;
+  __device__ __forceinline__ WideRow at(int32_t i) const { return {v + i, n + i}; }
+  __device__ __forceinline__ Pair load(int32_t i) const { return {v[i], n[i]}; }
+  static __device__ __forceinline__ bool below(Pair x, int64_t t) {
+    return wide_below(x.whole, x.nano, t);
+  }
+  static __device__ __forceinline__ bool not_above(Pair x, int64_t t) {
+    return wide_not_above(x.whole, x.nano, t);
+  }
+};
+
+// Numbers of entries of a[0..n) below t (cl) and not above t (cu), for an ascending a,
+// counted by the rule's lane group (gl = lane within the group, gmask = the group's lanes)
+// with every load of the window in flight at once.
+template <int kMaxPerLane, class Row>
+__device__ __forceinline__ void count_below(Row al, int32_t nl, Row au, int32_t nu, int64_t t,
+                                            int gl, uint64_t gmask, int32_t* cl, int32_t* cu) {
   int32_t sl = 0, su = 0;
 #pragma unroll
   for (int q = 0; q < kMaxPerLane; ++q) {
     const int32_t i = gl + q * kRuleLanes;
-    const int64_t vl = al[min(i, max(nl - 1, 0))];
-    const int64_t vu = au[min(i, max(nu - 1, 0))];
-    sl += __popcll(__ballot(i < nl && vl < t) & gmask);
-    su += __popcll(__ballot(i < nu && vu <= t) & gmask);
+    const auto vl = al.load(min(i, max(nl - 1, 0)));
+    const auto vu = au.load(min(i, max(nu - 1, 0)));
+    sl += __popcll(__ballot(i < nl && Row::below(vl, t)) & gmask);
+    su += __popcll(__ballot(i < nu && Row::not_above(vu, t)) & gmask);
   }
   *cl = sl;
   *cu = su;
 }
 
-// EvaluateRule (operator.go:13-26) over the ascending column: the nodes a rule selects form
-// one range, [lower_bound, upper_bound) of t*1000 for Equals, the prefix below it for
-// LessThan, the suffix above it for GreaterThan (t*1000 saturates).  A group
-// of 8 lanes per rule finds both bounds in three dependent rounds of loads: the 1024-stride
-// fences (f1k), the 32-stride fences of one 1024-block (f32), the 32 values of one
-// 32-block; each round counts the window's entries below the target.
-// count_below for a wide column (value = floor + nano * 1e-9, the rows in exact pair order)
-// against the integer target t:  v < t <=> floor < t;  v <= t <=> floor < t or (floor == t
-// and nano == 0).  Both predicates are monotone along the row.  The lower count reads the
-// floors at al, the upper count the floors at au and the nanos at an.
-template <int kMaxPerLane>
-__device__ __forceinline__ void count_below_wide(const int64_t* __restrict__ al, int32_t nl,
-                                                 const int64_t* __restrict__ au,
-                                                 const uint32_t* __restrict__ an, int32_t nu,
-                                                 int64_t t, int gl, uint64_t gmask, int32_t* cl,
-                                                 int32_t* cu) {
-  int32_t sl = 0, su = 0;
-#pragma unroll
-  for (int q = 0; q < kMaxPerLane; ++q) {
-    const int32_t i = gl + q * kRuleLanes;
-    const int64_t vl = al[min(i, max(nl - 1, 0))];
-    const int64_t vu = au[min(i, max(nu - 1, 0))];
-    const uint32_t fu = an[min(i, max(nu - 1, 0))];
-    sl += __popcll(__ballot(i < nl && vl < t) & gmask);
-    su += __popcll(__ballot(i < nu && (vu < t || (vu == t && fu == 0u))) & gmask);
-  }
-  *cl = sl;
-  *cu = su;
-}
-
-// The three rounds of ranges_group for a wide column m with c present nodes: lb = values
-// below t, ub = values not above t.  No saturation: the target is compared as it is.
-__device__ __forceinline__ void wide_bounds(const RangesParams& R, int32_t m, int32_t c,
-                                            int64_t t, int gl, uint64_t gmask, int32_t* lb,
-                                            int32_t* ub) {
-  const int64_t* sv = R.sorted + (int64_t)m * R.R;
-  const int64_t* f1 = R.f1k + (int64_t)m * (R.R >> 10);
-  const int64_t* f2 = R.f32 + (int64_t)m * (R.R >> 5);
-  const uint32_t* svn = R.sorted_nano + (int64_t)m * R.R;
-  const uint32_t* f1n = R.f1k_nano + (int64_t)m * (R.R >> 10);
-  const uint32_t* f2n = R.f32_nano + (int64_t)m * (R.R >> 5);
+// lb = entries below t, ub = entries not above t of a column with c present nodes (sv its
+// ascending row), in three dependent rounds of loads: the 1024-stride fences (f1), the
+// 32-stride fences of one 1024-block (f2), the 32 values of one 32-block; each round counts
+// the window's entries below the target.
+template <class Row>
+__device__ __forceinline__ void fence_bounds(Row sv, Row f1, Row f2, int32_t c, int64_t t,
+                                             int gl, uint64_t gmask, int32_t* lb, int32_t* ub) {
   const int32_t na = (c + 1023) >> 10, nb = (c + 31) >> 5;
-  int32_t n1l = 0, n1u = 0;
-  if (na <= 16 * kRuleLanes) {
-    count_below_wide<16>(f1, na, f1, f1n, na, t, gl, gmask, &n1l, &n1u);
+  int32_t n1l = 0, n1u = 0;  // fences (1024 apart) below the target
+  if (na <= 16 * kRuleLanes) {  // up to 131 072 nodes: every fence load in flight at once
+    count_below<16>(f1, na, f1, na, t, gl, gmask, &n1l, &n1u);
   } else {
     for (int32_t i0 = 0; i0 < na; i0 += 4 * kRuleLanes) {
       int32_t a, b;
-      count_below_wide<4>(f1 + i0, na - i0, f1 + i0, f1n + i0, na - i0, t, gl, gmask, &a, &b);
+      count_below<4>(f1.at(i0), na - i0, f1.at(i0), na - i0, t, gl, gmask, &a, &b);
       n1l += a;
       n1u += b;
     }
   }
+  // 1024-blocks holding each bound (sorted[1024 b1] is below; block 0 if none is)
   const int32_t b1l = max(n1l - 1, 0), b1u = max(n1u - 1, 0);
   int32_t n2l, n2u;
-  count_below_wide<4>(f2 + b1l * 32, n1l ? min(32, nb - b1l * 32) : 0, f2 + b1u * 32,
-                      f2n + b1u * 32, n1u ? min(32, nb - b1u * 32) : 0, t, gl, gmask, &n2l,
-                      &n2u);
+  count_below<4>(f2.at(b1l * 32), n1l ? min(32, nb - b1l * 32) : 0, f2.at(b1u * 32),
+                 n1u ? min(32, nb - b1u * 32) : 0, t, gl, gmask, &n2l, &n2u);
   const int32_t b2l = b1l * 32 + max(n2l - 1, 0), b2u = b1u * 32 + max(n2u - 1, 0);
   int32_t n3l, n3u;
-  count_below_wide<4>(sv + b2l * 32, n1l ? min(32, c - b2l * 32) : 0, sv + b2u * 32,
-                      svn + b2u * 32, n1u ? min(32, c - b2u * 32) : 0, t, gl, gmask, &n3l, &n3u);
+  count_below<4>(sv.at(b2l * 32), n1l ? min(32, c - b2l * 32) : 0, sv.at(b2u * 32),
+                 n1u ? min(32, c - b2u * 32) : 0, t, gl, gmask, &n3l, &n3u);
   *lb = n1l ? b2l * 32 + n3l : 0;
   *ub = n1u ? b2u * 32 + n3u : 0;
 }
 
+// EvaluateRule (operator.go:13-26) over the ascending column: the nodes a rule selects form
+// one range, [lower_bound, upper_bound) of t*1000 for Equals, the prefix below it for
+// LessThan, the suffix above it for GreaterThan (t*1000 saturates), found by a
+// group of 8 lanes per rule (fence_bounds).  A wide column compares the target as it is.
 // kWide: the snapshot holds at least one wide column (the host picks the instantiation; the
 // narrow one is the code every snapshot without wide columns runs).
 template <bool kWide>
@@ -221,36 +218,18 @@ __device__ void ranges_group(const RangesParams& R, int32_t r) {
     const int sat = wide ? 0 : target_scaled(rule.target, R.scale_tab, m, &t);
     int32_t lb, ub;
     if (wide) {
-      wide_bounds(R, m, c, rule.target, gl, gmask, &lb, &ub);
+      const int64_t o0 = (int64_t)m * R.R, o1 = (int64_t)m * (R.R >> 10),
+                    o2 = (int64_t)m * (R.R >> 5);
+      fence_bounds(WideRow{R.sorted + o0, R.sorted_nano + o0},
+                   WideRow{R.f1k + o1, R.f1k_nano + o1}, WideRow{R.f32 + o2, R.f32_nano + o2},
+                   c, rule.target, gl, gmask, &lb, &ub);
     } else if (sat != 0) {
       lb = ub = sat > 0 ? c : 0;
     } else {
-      const int64_t* sv = R.sorted + (int64_t)m * R.R;
-      const int64_t* f1 = R.f1k + (int64_t)m * (R.R >> 10);
-      const int64_t* f2 = R.f32 + (int64_t)m * (R.R >> 5);
-      const int32_t na = (c + 1023) >> 10, nb = (c + 31) >> 5;
-      int32_t n1l = 0, n1u = 0;  // fences (1024 apart) below the target
-      if (na <= 16 * kRuleLanes) {  // up to 131 072 nodes: every fence load in flight at once
-        count_below<16>(f1, na, f1, na, t, gl, gmask, &n1l, &n1u);
-      } else {
-        for (int32_t i0 = 0; i0 < na; i0 += 4 * kRuleLanes) {
-          int32_t a, b;
-          count_below<4>(f1 + i0, na - i0, f1 + i0, na - i0, t, gl, gmask, &a, &b);
-          n1l += a;
-          n1u += b;
-        }
-      }
-      // 1024-blocks holding each bound (sorted[1024 b1] is below; block 0 if none is)
-      const int32_t b1l = max(n1l - 1, 0), b1u = max(n1u - 1, 0);
-      int32_t n2l, n2u;
-      count_below<4>(f2 + b1l * 32, n1l ? min(32, nb - b1l * 32) : 0, f2 + b1u * 32,
-                     n1u ? min(32, nb - b1u * 32) : 0, t, gl, gmask, &n2l, &n2u);
-      const int32_t b2l = b1l * 32 + max(n2l - 1, 0), b2u = b1u * 32 + max(n2u - 1, 0);
-      int32_t n3l, n3u;
-      count_below<4>(sv + b2l * 32, n1l ? min(32, c - b2l * 32) : 0, sv + b2u * 32,
-                     n1u ? min(32, c - b2u * 32) : 0, t, gl, gmask, &n3l, &n3u);
-      lb = n1l ? b2l * 32 + n3l : 0;
-      ub = n1u ? b2u * 32 + n3u : 0;
+      const int64_t o0 = (int64_t)m * R.R, o1 = (int64_t)m * (R.R >> 10),
+                    o2 = (int64_t)m * (R.R >> 5);
+      fence_bounds(NarrowRow{R.sorted + o0}, NarrowRow{R.f1k + o1}, NarrowRow{R.f32 + o2}, c, t,
+                   gl, gmask, &lb, &ub);
     }
     if (rule.op == PAS_OP_LESS_THAN) out = make_int2(0, lb);
     else if (rule.op == PAS_OP_GREATER_THAN) out = make_int2(ub, c);
@@ -767,8 +746,7 @@ struct PlanOut {
 
 // kWide (the host picks it only while the snapshot holds a wide column): a rule on a wide
 // column also reads the column's nanos over the run and compares the pair exactly against the
-// integer target:  v < t <=> floor < t;  v == t <=> floor == t and nano == 0;  v > t <=>
-// floor > t or (floor == t and nano != 0).
+// integer target (wide_below / wide_equal / wide_above).
 struct WideCols {
   const uint8_t* flag;   // [M]
   const uint32_t* nano;  // [M][N]
@@ -871,10 +849,10 @@ __global__ __launch_bounds__(kTpb) void tas_violations_run_kernel(
 #pragma unroll
         for (int k = 0; k < kRun; ++k) {
           const bool valid = (gw0 + k) * 64 + lane < N;
-          const bool frac = nn[kWide ? k : 0] != 0u;
-          const bool hit = lt   ? v[k] < t
-                           : gt ? (v[k] > t) | ((v[k] == t) & frac)
-                                : (v[k] == t) & !frac;
+          const uint32_t f = nn[kWide ? k : 0];
+          const bool hit = lt   ? wide_below(v[k], f, t)
+                           : gt ? wide_above(v[k], f, t)
+                                : wide_equal(v[k], f, t);
           const uint64_t mask = __ballot(hit & valid);
           acc = lane == k ? (acc | (mask & pr)) : acc;
         }
@@ -982,6 +960,34 @@ const TasTuning& tas_tuning() {
   return t;
 }
 
+// The prep launch: the pods' grouping (block 0) beside the ranges of the first range_rules
+// rules (blocks 1..).  wide: the wide-aware ranges, for a snapshot that holds a wide column.
+int prep_launch(pas_ctx* ctx, uint32_t flags, int32_t n_pods, const pas_rule* d_prio,
+                const int32_t* d_rule_off, int32_t n_rules, int32_t range_rules,
+                const pas_rule* d_rules, int2* d_ranges, int4* d_desc, int2* d_keys,
+                int32_t no_group, bool wide, bool timed, hipStream_t s) {
+  const TasSnapshot& t = ctx->tas;
+  const int32_t M = t.n_metrics;
+  RangesParams rp{range_rules, M, t.row, d_rules, t.cnt, t.sorted, t.f1k, t.f32, d_ranges,
+                  t.scale_tab, t.wide_flag, t.sorted_nano, t.f1k_nano, t.f32_nano};
+  GroupParams gp{n_pods, M,      flags,  d_prio,   d_rule_off,
+                 t.cnt,  d_keys, d_desc, no_group, std::max(n_rules, 0)};
+  const size_t group_lds = sizeof(int32_t) * ((size_t)3 * M + 1 + (size_t)M);  // hist | cnt
+  void (*const prep)(GroupParams, RangesParams) =
+      wide ? &tas_prep_kernel<true> : &tas_prep_kernel<false>;
+  if (group_lds > 64 * 1024)
+    PAS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(prep),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)group_lds));
+  constexpr int kRulesPerBlock = kGroupTpb / kRuleLanes;
+  const unsigned blocks = 1u + (unsigned)((range_rules + kRulesPerBlock - 1) / kRulesPerBlock);
+  TimedLaunch tl;
+  if (timed) timing_begin(ctx, s, PAS_K_TAS_PREP, &tl);
+  prep<<<blocks, kGroupTpb, group_lds, s>>>(gp, rp);
+  if (timed) timing_end(ctx, s, &tl);
+  PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
+}
+
 }  // namespace
 
 int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
@@ -991,7 +997,6 @@ int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
   const TasSnapshot& t = ctx->tas;
   const int32_t N = t.n_nodes, M = t.n_metrics;
   const int32_t W64 = (int32_t)w64(N);
-  const int32_t G = 3 * M;
   const TasTuning& tune = tas_tuning();
   if (M > kMaxGroupMetrics)
     return set_error(ctx, PAS_ECAPACITY, "pas_tas_eval: more than 4096 metric columns");
@@ -1042,26 +1047,11 @@ int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
 
   TimedLaunch span, tl;
   timing_begin(ctx, s, PAS_K_TAS_SPAN, &span);
-  // ranges (blocks 1..) beside the grouping (block 0), one launch
-  const int32_t range_rules = (flags & PAS_TAS_FILTER) ? n_rules : 0;
-  RangesParams rp{range_rules, M, t.row, d_rules, t.cnt, t.sorted, t.f1k, t.f32, d_ranges,
-                  t.scale_tab, t.wide_flag, t.sorted_nano, t.f1k_nano, t.f32_nano};
-  GroupParams gp{n_pods, M,      flags,  d_prio,        d_rule_off,
-                 t.cnt,  d_keys, d_desc, tune.no_group, std::max(n_rules, 0)};
-  const size_t group_lds = sizeof(int32_t) * ((size_t)G + 1 + (size_t)M);  // hist | cnt
   // the wide-aware ranges only while the snapshot holds a wide column
-  void (*const prep)(GroupParams, RangesParams) =
-      t.n_wide > 0 ? &tas_prep_kernel<true> : &tas_prep_kernel<false>;
-  if (group_lds > 64 * 1024)
-    PAS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(prep),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)group_lds));
-  constexpr int kRulesPerBlock = kGroupTpb / kRuleLanes;
-  const unsigned prep_blocks =
-      1u + (unsigned)((range_rules + kRulesPerBlock - 1) / kRulesPerBlock);
-  timing_begin(ctx, s, PAS_K_TAS_PREP, &tl);
-  prep<<<prep_blocks, kGroupTpb, group_lds, s>>>(gp, rp);
-  timing_end(ctx, s, &tl);
-  PAS_HIP(ctx, hipGetLastError());
+  if ((rc = prep_launch(ctx, flags, n_pods, d_prio, d_rule_off, n_rules,
+                        (flags & PAS_TAS_FILTER) ? n_rules : 0, d_rules, d_ranges, d_desc,
+                        d_keys, tune.no_group, t.n_wide > 0, true, s)))
+    return rc;
 
   ep.flags = flags;
   ep.ranges = d_ranges;
@@ -1112,22 +1102,10 @@ int tas_group_launch(pas_ctx* ctx, int32_t n_pods, const pas_rule* d_prio,
   const int32_t M = t.n_metrics;
   if (M > kMaxGroupMetrics)
     return set_error(ctx, PAS_ECAPACITY, "more than 4096 metric columns");
-  const uint32_t flags = PAS_TAS_FILTER | PAS_TAS_PRIORITIZE;
-  const int32_t range_rules = d_ranges ? n_rules : 0;
   // (the top-k entry points refuse a snapshot with wide columns: narrow ranges only)
-  RangesParams rp{range_rules, M, t.row, d_rules, t.cnt, t.sorted, t.f1k, t.f32, d_ranges,
-                  t.scale_tab, nullptr, nullptr, nullptr, nullptr};
-  GroupParams gp{n_pods, M, flags, d_prio, d_rule_off, t.cnt, d_keys, d_desc, 0,
-                 std::max(n_rules, 0)};
-  const size_t group_lds = sizeof(int32_t) * ((size_t)3 * M + 1 + (size_t)M);
-  if (group_lds > 64 * 1024)
-    PAS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&tas_prep_kernel<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)group_lds));
-  constexpr int kRulesPerBlock = kGroupTpb / kRuleLanes;
-  const unsigned blocks = 1u + (unsigned)((range_rules + kRulesPerBlock - 1) / kRulesPerBlock);
-  tas_prep_kernel<false><<<blocks, kGroupTpb, group_lds, s>>>(gp, rp);
-  PAS_HIP(ctx, hipGetLastError());
-  return PAS_OK;
+  return prep_launch(ctx, PAS_TAS_FILTER | PAS_TAS_PRIORITIZE, n_pods, d_prio, d_rule_off,
+                     n_rules, d_ranges ? n_rules : 0, d_rules, d_ranges, d_desc, d_keys, 0, false,
+                     false, s);
 }
 
 int tas_violations_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,

@@ -51,29 +51,24 @@ __global__ void first_pos_kernel(int32_t n_req, int32_t N, const int32_t* __rest
 }
 
 // Number of entries of the ascending row[0, cnt) that are < v (lower) or <= v (upper).
-__device__ __forceinline__ int32_t bound(const int64_t* __restrict__ row, int32_t cnt, int64_t v,
-                                         bool upper) {
+// kWide: the same over a wide column's row (floors in row, nanos in nrow, exact pair order)
+// for the pair (v, f); the narrow form reads neither nrow nor f.
+template <bool kWide>
+__device__ __forceinline__ int32_t bound(const int64_t* __restrict__ row,
+                                         const uint32_t* __restrict__ nrow, int32_t cnt,
+                                         int64_t v, uint32_t f, bool upper) {
   int32_t lo = 0, hi = cnt;
   while (lo < hi) {
     const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
     const int64_t x = row[mid];
-    if (x < v || (upper && x == v)) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// The same over a wide column's row (floors in row, nanos in nrow, exact pair order) for the
-// pair (v, f): entries below it, or not above it.
-__device__ __forceinline__ int32_t bound_wide(const int64_t* __restrict__ row,
-                                              const uint32_t* __restrict__ nrow, int32_t cnt,
-                                              int64_t v, uint32_t f, bool upper) {
-  int32_t lo = 0, hi = cnt;
-  while (lo < hi) {
-    const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
-    const int64_t x = row[mid];
-    const uint32_t xf = nrow[mid];
-    if (x < v || (x == v && (xf < f || (upper && xf == f)))) lo = mid + 1;
+    bool before;
+    if constexpr (kWide) {
+      const uint32_t xf = nrow[mid];
+      before = upper ? pair_not_above(x, xf, v, f) : pair_below(x, xf, v, f);
+    } else {
+      before = x < v || (upper && x == v);
+    }
+    if (before) lo = mid + 1;
     else hi = mid;
   }
   return lo;
@@ -106,16 +101,12 @@ __global__ void request_keys_kernel(int32_t n_req, int32_t N, int32_t R, pas_rul
           const int64_t v = vals[(int64_t)rule.metric * N + n];
           const int32_t c = cnt[rule.metric];
           const int64_t* row = sorted + (int64_t)rule.metric * R;
-          if constexpr (kWide) {
-            const uint32_t f = nano[(int64_t)rule.metric * N + n];
-            const uint32_t* nrow = sorted_nano + (int64_t)rule.metric * R;
-            rank = rule.op == PAS_OP_LESS_THAN
-                       ? (uint64_t)bound_wide(row, nrow, c, v, f, false)
-                       : (uint64_t)(c - bound_wide(row, nrow, c, v, f, true));
-          } else {
-            rank = rule.op == PAS_OP_LESS_THAN ? (uint64_t)bound(row, c, v, false)
-                                               : (uint64_t)(c - bound(row, c, v, true));
-          }
+          uint32_t f = 0;
+          if constexpr (kWide) f = nano[(int64_t)rule.metric * N + n];
+          const uint32_t* nrow = sorted_nano + (int64_t)rule.metric * R;
+          rank = rule.op == PAS_OP_LESS_THAN
+                     ? (uint64_t)bound<kWide>(row, nrow, c, v, f, false)
+                     : (uint64_t)(c - bound<kWide>(row, nrow, c, v, f, true));
         }
         key = rank << pb | (uint64_t)j;
       }

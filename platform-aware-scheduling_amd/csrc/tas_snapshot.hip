@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <type_traits>
 
 #include "pas_internal.h"
 
@@ -53,13 +54,17 @@ struct SortKeyBits {
   }
 };
 // Wide columns (value = v + pad * 1e-9, v the floor): pad carries the nanos below the floor,
-// so the key order is the exact order of the pairs.  A sort instantiation of its own: the
-// narrow build keeps its 64 + column bits.  Pads carry {INT64_MAX, 0xffffffff}.
+// so the key order is the exact order of the pairs.  The second instantiation of the same
+// sort: the narrow build keeps its 64 + column bits.  Pads carry {INT64_MAX, 0xffffffff}.
 struct WideKeyBits {
   __host__ __device__ rocprim::tuple<uint32_t&, int64_t&, uint32_t&> operator()(SortKey& k) const {
     return rocprim::tuple<uint32_t&, int64_t&, uint32_t&>(k.c, k.v, k.pad);
   }
 };
+template <bool kWide>
+using KeyBits = std::conditional_t<kWide, WideKeyBits, SortKeyBits>;
+template <bool kWide>
+constexpr unsigned kValueBits = kWide ? 96 : 64;  // key bits below the column index
 constexpr uint32_t kNanoMax = 999999999u;
 
 __device__ __forceinline__ int32_t row_of(const int32_t* rows, int32_t c) {
@@ -117,41 +122,17 @@ __global__ void compact_keys(const uint64_t* __restrict__ present,
 }
 
 // Ascending result -> sorted / perm_asc rows and the fences (f32[m][b] = sorted[32 b],
-// f1k[m][a] = sorted[1024 a], 0 past cnt); the input keys become the descending keys.
+// f1k[m][a] = sorted[1024 a], 0 past cnt); the input keys become the descending keys
+// (v1 < v2 <=> ~v1 > ~v2, no overflow).  kWide: floors and nanos of the sorted pairs side by
+// side, fences of both; the descending keys complement both fields.
+template <bool kWide>
 __global__ void place_asc(const SortKey* __restrict__ skeys, const int32_t* __restrict__ sids,
                           SortKey* __restrict__ keys, const uint32_t* __restrict__ scan,
                           const int32_t* __restrict__ rows, int32_t C, int32_t R, int64_t W,
                           int32_t MR, int64_t* __restrict__ sorted, int32_t* __restrict__ perm,
                           int32_t* __restrict__ cnt_out, int64_t* __restrict__ f1k,
-                          int64_t* __restrict__ f32) {
-  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
-  if (i >= (int64_t)C * R) return;
-  const int32_t c = (int32_t)(i / R), j = (int32_t)(i % R);
-  const int64_t m = row_of(rows, c);
-  const int32_t cnt = (int32_t)(scan[(int64_t)(c + 1) * W] - scan[(int64_t)c * W]);
-  const int64_t v = skeys[i].v;
-  sorted[m * R + j] = v;
-  perm[(int64_t)kOrderAsc * MR + m * R + j] = sids[i];
-  if ((j & 31) == 0) {
-    const int64_t f = j < cnt ? v : 0;
-    f32[m * (R >> 5) + (j >> 5)] = f;
-    if ((j & 1023) == 0) f1k[m * (R >> 10) + (j >> 10)] = f;
-  }
-  if (j == 0) cnt_out[m] = cnt;
-  if (j < cnt) keys[i].v = ~keys[i].v;  // v1 < v2 <=> ~v1 > ~v2 (no overflow)
-}
-
-// The same for a wide column: floors and nanos of the sorted pairs side by side, fences of
-// both; the descending keys complement both fields.
-__global__ void place_asc_wide(const SortKey* __restrict__ skeys,
-                               const int32_t* __restrict__ sids, SortKey* __restrict__ keys,
-                               const uint32_t* __restrict__ scan,
-                               const int32_t* __restrict__ rows, int32_t C, int32_t R, int64_t W,
-                               int32_t MR, int64_t* __restrict__ sorted,
-                               uint32_t* __restrict__ sorted_nano, int32_t* __restrict__ perm,
-                               int32_t* __restrict__ cnt_out, int64_t* __restrict__ f1k,
-                               int64_t* __restrict__ f32, uint32_t* __restrict__ f1k_nano,
-                               uint32_t* __restrict__ f32_nano) {
+                          int64_t* __restrict__ f32, uint32_t* __restrict__ sorted_nano,
+                          uint32_t* __restrict__ f1k_nano, uint32_t* __restrict__ f32_nano) {
   const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
   if (i >= (int64_t)C * R) return;
   const int32_t c = (int32_t)(i / R), j = (int32_t)(i % R);
@@ -159,22 +140,22 @@ __global__ void place_asc_wide(const SortKey* __restrict__ skeys,
   const int32_t cnt = (int32_t)(scan[(int64_t)(c + 1) * W] - scan[(int64_t)c * W]);
   const SortKey k = skeys[i];
   sorted[m * R + j] = k.v;
-  sorted_nano[m * R + j] = k.pad;
+  if constexpr (kWide) sorted_nano[m * R + j] = k.pad;
   perm[(int64_t)kOrderAsc * MR + m * R + j] = sids[i];
   if ((j & 31) == 0) {
     const int64_t f = j < cnt ? k.v : 0;
     const uint32_t fn = j < cnt ? k.pad : 0u;
     f32[m * (R >> 5) + (j >> 5)] = f;
-    f32_nano[m * (R >> 5) + (j >> 5)] = fn;
+    if constexpr (kWide) f32_nano[m * (R >> 5) + (j >> 5)] = fn;
     if ((j & 1023) == 0) {
       f1k[m * (R >> 10) + (j >> 10)] = f;
-      f1k_nano[m * (R >> 10) + (j >> 10)] = fn;
+      if constexpr (kWide) f1k_nano[m * (R >> 10) + (j >> 10)] = fn;
     }
   }
   if (j == 0) cnt_out[m] = cnt;
   if (j < cnt) {
     keys[i].v = ~keys[i].v;
-    keys[i].pad = ~keys[i].pad;
+    if constexpr (kWide) keys[i].pad = ~keys[i].pad;
   }
 }
 
@@ -204,8 +185,26 @@ inline unsigned bits_for(int32_t c) {  // bits of the column index in the sort k
   return b;
 }
 
+// Temp storage of the largest (whole-snapshot, M columns of row R) sort of either key width.
+template <bool kWide>
+int alloc_sort_tmp(pas_ctx* ctx, size_t mr, int32_t M, hipStream_t s) {
+  TasSnapshot& t = ctx->tas;
+  size_t sort_bytes = 0;
+  SortKey* ka = static_cast<SortKey*>(t.keys_a);
+  SortKey* kb = static_cast<SortKey*>(t.keys_b);
+  PAS_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, ka, kb, t.ids_a, t.ids_b, mr,
+                                         KeyBits<kWide>{}, 0u,
+                                         kValueBits<kWide> + bits_for(std::max(M, 1)), s));
+  size_t& bytes = kWide ? t.wide_sort_tmp_bytes : t.sort_tmp_bytes;
+  bytes = std::max<size_t>(sort_bytes, 16);
+  PAS_HIP(ctx, hipMalloc(kWide ? &t.wide_sort_tmp : &t.sort_tmp, bytes));
+  return PAS_OK;
+}
+
 // Orders of C columns whose values / presence sit at vals [C][N] / present [C][W]
-// (rows: snapshot row of each column, nullptr = identity).
+// (rows: snapshot row of each column, nullptr = identity).  kWide: vals are the floors, the
+// nanos are already in t.nano's rows.
+template <bool kWide>
 int build_columns(pas_ctx* ctx, int32_t C, const int32_t* d_rows, const int64_t* vals,
                   const uint64_t* present, hipStream_t s) {
   TasSnapshot& t = ctx->tas;
@@ -221,54 +220,22 @@ int build_columns(pas_ctx* ctx, int32_t C, const int32_t* d_rows, const int64_t*
                                        (size_t)(cw + 1), rocprim::plus<uint32_t>(), s));
   SortKey* ka = static_cast<SortKey*>(t.keys_a);
   SortKey* kb = static_cast<SortKey*>(t.keys_b);
-  compact_keys<false><<<blocks_for(cr), kTpb, 0, s>>>(present, vals, nullptr, t.word_scan, d_rows,
+  compact_keys<kWide><<<blocks_for(cr), kTpb, 0, s>>>(present, vals, t.nano, t.word_scan, d_rows,
                                                      C, N, R, W, MR, ka, t.ids_a, t.perm);
   PAS_HIP(ctx, hipGetLastError());
-  const unsigned end_bit = 64 + bits_for(C);
-  size_t sort_bytes = t.sort_tmp_bytes;
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(t.sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
-                                         (size_t)cr, SortKeyBits{}, 0u, end_bit, s));
-  place_asc<<<blocks_for(cr), kTpb, 0, s>>>(kb, t.ids_b, ka, t.word_scan, d_rows, C, R, W, MR,
-                                           t.sorted, t.perm, t.cnt, t.f1k, t.f32);
+  const unsigned end_bit = kValueBits<kWide> + bits_for(C);
+  void* const sort_tmp = kWide ? t.wide_sort_tmp : t.sort_tmp;
+  const size_t sort_tmp_bytes = kWide ? t.wide_sort_tmp_bytes : t.sort_tmp_bytes;
+  size_t sort_bytes = sort_tmp_bytes;
+  PAS_HIP(ctx, rocprim::radix_sort_pairs(sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
+                                         (size_t)cr, KeyBits<kWide>{}, 0u, end_bit, s));
+  place_asc<kWide><<<blocks_for(cr), kTpb, 0, s>>>(kb, t.ids_b, ka, t.word_scan, d_rows, C, R, W,
+                                                  MR, t.sorted, t.perm, t.cnt, t.f1k, t.f32,
+                                                  t.sorted_nano, t.f1k_nano, t.f32_nano);
   PAS_HIP(ctx, hipGetLastError());
-  sort_bytes = t.sort_tmp_bytes;
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(t.sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
-                                         (size_t)cr, SortKeyBits{}, 0u, end_bit, s));
-  place_desc<<<blocks_for(cr), kTpb, 0, s>>>(t.ids_b, d_rows, C, R, MR, t.perm);
-  PAS_HIP(ctx, hipGetLastError());
-  return PAS_OK;
-}
-
-// The same for wide columns: vals [C][N] the floors, the nanos already in t.nano's rows.
-int build_columns_wide(pas_ctx* ctx, int32_t C, const int32_t* d_rows, const int64_t* vals,
-                       const uint64_t* present, hipStream_t s) {
-  TasSnapshot& t = ctx->tas;
-  const int32_t N = t.n_nodes, R = t.row;
-  const int64_t W = w64(N);
-  const int32_t MR = t.n_metrics * R;
-  const int64_t cw = (int64_t)C * W;
-  const int64_t cr = (int64_t)C * R;
-  popc_words<<<blocks_for(cw + 1), kTpb, 0, s>>>(present, cw, N, W, t.popc);
-  PAS_HIP(ctx, hipGetLastError());
-  size_t scan_bytes = t.scan_tmp_bytes;
-  PAS_HIP(ctx, rocprim::exclusive_scan(t.scan_tmp, scan_bytes, t.popc, t.word_scan, 0u,
-                                       (size_t)(cw + 1), rocprim::plus<uint32_t>(), s));
-  SortKey* ka = static_cast<SortKey*>(t.keys_a);
-  SortKey* kb = static_cast<SortKey*>(t.keys_b);
-  compact_keys<true><<<blocks_for(cr), kTpb, 0, s>>>(present, vals, t.nano, t.word_scan, d_rows,
-                                                    C, N, R, W, MR, ka, t.ids_a, t.perm);
-  PAS_HIP(ctx, hipGetLastError());
-  const unsigned end_bit = 96 + bits_for(C);
-  size_t sort_bytes = t.wide_sort_tmp_bytes;
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(t.wide_sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
-                                         (size_t)cr, WideKeyBits{}, 0u, end_bit, s));
-  place_asc_wide<<<blocks_for(cr), kTpb, 0, s>>>(kb, t.ids_b, ka, t.word_scan, d_rows, C, R, W,
-                                                MR, t.sorted, t.sorted_nano, t.perm, t.cnt,
-                                                t.f1k, t.f32, t.f1k_nano, t.f32_nano);
-  PAS_HIP(ctx, hipGetLastError());
-  sort_bytes = t.wide_sort_tmp_bytes;
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(t.wide_sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
-                                         (size_t)cr, WideKeyBits{}, 0u, end_bit, s));
+  sort_bytes = sort_tmp_bytes;
+  PAS_HIP(ctx, rocprim::radix_sort_pairs(sort_tmp, sort_bytes, ka, kb, t.ids_a, t.ids_b,
+                                         (size_t)cr, KeyBits<kWide>{}, 0u, end_bit, s));
   place_desc<<<blocks_for(cr), kTpb, 0, s>>>(t.ids_b, d_rows, C, R, MR, t.perm);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
@@ -285,14 +252,7 @@ int ensure_wide(pas_ctx* ctx, hipStream_t s) {
   PAS_HIP(ctx, hipMalloc(&t.sorted_nano, sizeof(uint32_t) * mr));
   PAS_HIP(ctx, hipMalloc(&t.f1k_nano, sizeof(uint32_t) * (mr / 1024 + 1)));
   PAS_HIP(ctx, hipMalloc(&t.f32_nano, sizeof(uint32_t) * (mr / 32 + 1)));
-  size_t sort_bytes = 0;
-  SortKey* ka = static_cast<SortKey*>(t.keys_a);
-  SortKey* kb = static_cast<SortKey*>(t.keys_b);
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, ka, kb, t.ids_a, t.ids_b,
-                                         (size_t)mr, WideKeyBits{}, 0u,
-                                         96 + bits_for(std::max(t.n_metrics, 1)), s));
-  t.wide_sort_tmp_bytes = std::max<size_t>(sort_bytes, 16);
-  PAS_HIP(ctx, hipMalloc(&t.wide_sort_tmp, t.wide_sort_tmp_bytes));
+  if (int rc = alloc_sort_tmp<true>(ctx, mr, t.n_metrics, s)) return rc;
   PAS_HIP(ctx, hipMalloc(&t.wide_flag, mm));
   PAS_HIP(ctx, hipMemsetAsync(t.wide_flag, 0, mm, s));
   return PAS_OK;
@@ -313,6 +273,52 @@ int mark_wide(pas_ctx* ctx, int32_t n_cols, const int32_t* cols, uint8_t wide, h
   if (changed)  // wide_host lives as long as the snapshot; callers synchronize s after this
     PAS_HIP(ctx, hipMemcpyAsync(t.wide_flag, t.wide_host.data(), (size_t)t.n_metrics,
                                 hipMemcpyHostToDevice, s));
+  return PAS_OK;
+}
+
+// The columns cols[0 .. n_cols) replaced by d_vals / d_present (kWide: floors d_vals, nanos
+// d_nano; the columns become wide, else narrow) and their orders rebuilt.
+template <bool kWide>
+int update_columns(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
+                   const int64_t* d_vals, const uint32_t* d_nano, const uint64_t* d_present,
+                   hipStream_t s) {
+  TasSnapshot& t = ctx->tas;
+  const int32_t N = t.n_nodes;
+  const int64_t W = w64(N);
+  if (n_cols > 0) {
+    if constexpr (kWide) {
+      if (int rc = ensure_wide(ctx, s)) {
+        t.valid = false;
+        return rc;
+      }
+    }
+    // the new columns into their snapshot rows, then their orders
+    for (int32_t c = 0; c < n_cols && N > 0; ++c) {
+      const int64_t m = cols[c];
+      PAS_HIP(ctx, hipMemcpyAsync(t.vals + m * N, d_vals + (int64_t)c * N, sizeof(int64_t) * N,
+                                  hipMemcpyDeviceToDevice, s));
+      PAS_HIP(ctx, hipMemcpyAsync(t.present + m * W, d_present + (int64_t)c * W,
+                                  sizeof(uint64_t) * W, hipMemcpyDeviceToDevice, s));
+    }
+    PAS_HIP(ctx, hipMemcpyAsync(t.rows, cols, sizeof(int32_t) * n_cols, hipMemcpyHostToDevice,
+                                s));
+    // (a wide column refreshed by a narrow update is narrow again, at its recorded scale)
+    if (int rc = mark_wide(ctx, n_cols, cols, kWide ? 1 : 0, s)) return rc;
+    // cols is a caller-owned host array: wait for its copy before returning
+    PAS_HIP(ctx, hipStreamSynchronize(s));
+    t.valid = false;
+    if constexpr (kWide) {
+      if (N > 0) {
+        clamp_nano<<<blocks_for((int64_t)n_cols * N), kTpb, 0, s>>>(d_nano, t.rows, n_cols, N,
+                                                                   t.nano);
+        PAS_HIP(ctx, hipGetLastError());
+      }
+    }
+    if (int rc = build_columns<kWide>(ctx, n_cols, t.rows, d_vals, d_present, s)) return rc;
+  }
+  t.gen = gen;
+  t.valid = true;
+  ++t.epoch;
   return PAS_OK;
 }
 
@@ -360,17 +366,11 @@ int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t N, int32_t M,
     PAS_HIP(ctx, hipMalloc(&t.rows, sizeof(int32_t) * mm));
     PAS_HIP(ctx, hipMalloc(&t.scale_tab, sizeof(int64_t) * 2 * mm));
     // temp storage for the largest (whole-snapshot) sort and scan
-    size_t sort_bytes = 0, scan_bytes = 0;
-    SortKey* ka = static_cast<SortKey*>(t.keys_a);
-    SortKey* kb = static_cast<SortKey*>(t.keys_b);
-    PAS_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, ka, kb, t.ids_a, t.ids_b,
-                                           (size_t)mr, SortKeyBits{}, 0u,
-                                           64 + bits_for(std::max(M, 1)), s));
+    if (int rc = alloc_sort_tmp<false>(ctx, mr, M, s)) return rc;
+    size_t scan_bytes = 0;
     PAS_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, t.popc, t.word_scan, 0u,
                                          (size_t)(mw + 1), rocprim::plus<uint32_t>(), s));
-    t.sort_tmp_bytes = std::max<size_t>(sort_bytes, 16);
     t.scan_tmp_bytes = std::max<size_t>(scan_bytes, 16);
-    PAS_HIP(ctx, hipMalloc(&t.sort_tmp, t.sort_tmp_bytes));
     PAS_HIP(ctx, hipMalloc(&t.scan_tmp, t.scan_tmp_bytes));
     t.n_nodes = N;
     t.n_metrics = M;
@@ -395,7 +395,7 @@ int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t N, int32_t M,
     if (MN > 0 && d_present != t.present)
       PAS_HIP(ctx, hipMemcpyAsync(t.present, d_present, sizeof(uint64_t) * M * W,
                                   hipMemcpyDeviceToDevice, s));
-    if (int rc = build_columns(ctx, M, nullptr, t.vals, t.present, s)) return rc;
+    if (int rc = build_columns<false>(ctx, M, nullptr, t.vals, t.present, s)) return rc;
   }
   t.gen = gen;
   t.valid = true;
@@ -405,68 +405,13 @@ int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t N, int32_t M,
 
 int tas_snapshot_update(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
                         const int64_t* d_vals, const uint64_t* d_present, hipStream_t s) {
-  TasSnapshot& t = ctx->tas;
-  const int32_t N = t.n_nodes;
-  const int64_t W = w64(N);
-  if (n_cols > 0) {
-    // the new columns into their snapshot rows, then their orders
-    for (int32_t c = 0; c < n_cols && N > 0; ++c) {
-      const int64_t m = cols[c];
-      PAS_HIP(ctx, hipMemcpyAsync(t.vals + m * N, d_vals + (int64_t)c * N, sizeof(int64_t) * N,
-                                  hipMemcpyDeviceToDevice, s));
-      PAS_HIP(ctx, hipMemcpyAsync(t.present + m * W, d_present + (int64_t)c * W,
-                                  sizeof(uint64_t) * W, hipMemcpyDeviceToDevice, s));
-    }
-    // cols is a caller-owned host array: wait for its copy before returning
-    PAS_HIP(ctx, hipMemcpyAsync(t.rows, cols, sizeof(int32_t) * n_cols, hipMemcpyHostToDevice,
-                                s));
-    // a wide column refreshed here is narrow again, at its recorded scale
-    if (int rc = mark_wide(ctx, n_cols, cols, 0, s)) return rc;
-    PAS_HIP(ctx, hipStreamSynchronize(s));
-    t.valid = false;
-    if (int rc = build_columns(ctx, n_cols, t.rows, d_vals, d_present, s)) return rc;
-  }
-  t.gen = gen;
-  t.valid = true;
-  ++t.epoch;
-  return PAS_OK;
+  return update_columns<false>(ctx, gen, n_cols, cols, d_vals, nullptr, d_present, s);
 }
 
 int tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
                              const int64_t* d_whole, const uint32_t* d_nano,
                              const uint64_t* d_present, hipStream_t s) {
-  TasSnapshot& t = ctx->tas;
-  const int32_t N = t.n_nodes;
-  const int64_t W = w64(N);
-  if (n_cols > 0) {
-    if (int rc = ensure_wide(ctx, s)) {
-      t.valid = false;
-      return rc;
-    }
-    for (int32_t c = 0; c < n_cols && N > 0; ++c) {
-      const int64_t m = cols[c];
-      PAS_HIP(ctx, hipMemcpyAsync(t.vals + m * N, d_whole + (int64_t)c * N, sizeof(int64_t) * N,
-                                  hipMemcpyDeviceToDevice, s));
-      PAS_HIP(ctx, hipMemcpyAsync(t.present + m * W, d_present + (int64_t)c * W,
-                                  sizeof(uint64_t) * W, hipMemcpyDeviceToDevice, s));
-    }
-    PAS_HIP(ctx, hipMemcpyAsync(t.rows, cols, sizeof(int32_t) * n_cols, hipMemcpyHostToDevice,
-                                s));
-    if (int rc = mark_wide(ctx, n_cols, cols, 1, s)) return rc;
-    // cols is a caller-owned host array: wait for its copy before returning
-    PAS_HIP(ctx, hipStreamSynchronize(s));
-    t.valid = false;
-    if (N > 0) {
-      clamp_nano<<<blocks_for((int64_t)n_cols * N), kTpb, 0, s>>>(d_nano, t.rows, n_cols, N,
-                                                                 t.nano);
-      PAS_HIP(ctx, hipGetLastError());
-    }
-    if (int rc = build_columns_wide(ctx, n_cols, t.rows, d_whole, d_present, s)) return rc;
-  }
-  t.gen = gen;
-  t.valid = true;
-  ++t.epoch;
-  return PAS_OK;
+  return update_columns<true>(ctx, gen, n_cols, cols, d_whole, d_nano, d_present, s);
 }
 
 }  // namespace pas

@@ -509,6 +509,38 @@ def test_long_row_chunked_fences(ctx, oracle):
 
 
 @pytest.mark.gpu
+def test_bounds_in_different_fence_blocks(ctx, oracle):
+    """2100 present nodes (two 1024-blocks, a last 32-block of 20) whose sorted row holds a run
+    of equal pairs over position 1024: the 1024-fence equals the target, so the lower and the
+    upper bound of a rule on it are searched in different blocks of both fence levels."""
+    rng = np.random.default_rng(0x1024)
+    N = 2100
+    i = np.arange(N)
+    whole = np.where(i < 1000, i - 3000, np.where(i <= 1100, 7, 8 + (i - 1101) // 2))
+    nano = np.where(i < 1000, 5, np.where(i <= 1100, 0, (i - 1101) % 2 * 500_000_000))
+    order = rng.permutation(N)  # node order is not value order
+    whole, nano = whole[order].astype(np.int64), nano[order].astype(np.uint32)
+    pres = pack_bits(np.ones((1, N), bool))
+    u, s = wide_oracle_values(whole, nano)
+    ctx.tas_snapshot_set(9545, np.zeros((1, N), np.int64), pres)
+    ctx.tas_snapshot_update_wide(9545, 9546, [0], whole[None], nano[None], pres)
+    last = int(whole.max())
+    targets = [7, 6, 8, -2001, -2000, last, last + 1, -3001]
+    rules = np.array([(0, op, t) for t in targets for op in range(3)], RULE_DTYPE)
+    off = np.arange(len(rules) + 1, dtype=np.int32)  # one rule per pod
+    prio = np.array([(0, p % 3, 0) for p in range(len(rules))], RULE_DTYPE)
+    gp, go, gl = ctx.tas_eval(9546, rules, off, prio)
+    wp, wo, wlens = oracle.tas_eval(u[None], pres, rules, off, prio, v_scale=s[None])
+    np.testing.assert_array_equal(gp, wp)
+    np.testing.assert_array_equal(gl, wlens)
+    for p in range(len(rules)):
+        np.testing.assert_array_equal(go[p, :gl[p]], wo[p, :wlens[p]], err_msg=f"pod {p}")
+    # by hand for target 7: 1000 nodes below it, 999 above it, the run of 101 equal to it
+    failed = [N - sum(int(w).bit_count() for w in gp[p]) for p in range(3)]
+    assert failed == [1000, 999, 101]
+
+
+@pytest.mark.gpu
 def test_transitions_and_errors(ctx, oracle):
     import torch
     rng = np.random.default_rng(0x7A)
