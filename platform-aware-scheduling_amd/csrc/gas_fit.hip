@@ -38,6 +38,21 @@
 // kind) or list 0, and the fit kernels instantiate one body per list.  The last kind a
 // selection requests stays compared, so cards a node does not have (free -1) still fail.  In
 // the C3 mix the i915 kind (1 per selection against >= 30 free) goes.
+//
+// Filing rule (gas_prep_kernel).  A pod's selections are its containers' in order, numI915
+// for each container that requests a kind; S = their count.  free, and so gmin, is -1 for a
+// real card whose cap[q] <= 0 or used[k][q] < 0.
+//   S <= 1, the single lists [Q + 1]: list 1 + q for the lowest kind q that the selection
+//     requests together with another kind and whose per-GPU need is <= gmin[q]; else list 0
+//     (S = 0: list 0).
+//   S >= 2, the multi lists [Q + 1][kClasses]: list 1 + q for the lowest kind q that some
+//     selection requests, that no selection requests alone, and whose total take over the
+//     pod's selections (a negative need counts 0) is <= gmin[q]; else list 0.  Class: S = 2;
+//     S = 3; S = 4 in closed form (lists 1 .. Q only); else S >= 4 in order (list 0's S = 4
+//     pods included; S > 8 is listed there too and evaluated by the generic kernel).
+// With one kind nothing can be skipped: only list 0 is used.  The 64-bit in-order path
+// (multi_list / multi_state) serves exactly the in-order class of the lists without a skipped
+// kind; every other multi-selection list runs on group ranks.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -73,9 +88,6 @@ constexpr int kSingleTpb = PAS_GAS_SINGLE_TPB;
 // 1: the fault-injection build (lib/libpas_fault.so): PAS_GAS_FORCE_TIMEOUT=n makes the next
 // n fits' side-stream waits give up at once, to test that the call then fails loudly
 #define PAS_GAS_FAULT_INJECTION 0
-#endif
-#ifndef PAS_GAS_SEQ_FIRST
-#define PAS_GAS_SEQ_FIRST 0  // 1: the sequential kernel before the closed-form one (diagnostic)
 #endif
 #ifndef PAS_GAS_BLOCKS_SINGLE
 #define PAS_GAS_BLOCKS_SINGLE 8192  // target blocks of a fit grid: (node block, pod chunk) pairs
@@ -689,17 +701,10 @@ __device__ __forceinline__ void put_result(ResSoff res, uint64_t* __restrict__ f
 struct BlockTile {
   int32_t node_block, chunk, chunks;
 };
-#ifndef PAS_GAS_POD_MAJOR
-#define PAS_GAS_POD_MAJOR 0  // 1: a chunk's node blocks consecutive on an XCD (diagnostic)
-#endif
 __device__ __forceinline__ BlockTile block_tile(int32_t chunks) {
   const int32_t nb = gridDim.x, b = blockIdx.x;
   const int32_t xcd = b & 7, per = nb >> 3, rem = nb & 7;
   const int32_t pos = xcd * per + min(xcd, rem) + (b >> 3);
-  if (PAS_GAS_POD_MAJOR) {
-    const int32_t node_blocks = nb / chunks;
-    return BlockTile{pos % node_blocks, pos / node_blocks, chunks};
-  }
   return BlockTile{pos / chunks, pos % chunks, chunks};
 }
 
@@ -710,6 +715,15 @@ __device__ __forceinline__ void list_share(const int32_t* count, const BlockTile
   const int32_t per = (cnt + bt.chunks - 1) / bt.chunks;
   *b = min(cnt, bt.chunk * per);
   *e = min(cnt, *b + per);
+}
+
+// A wave publishes what its lanes just wrote to its LDS slice (a staged batch, sorted rows):
+// after this every lane of the wave reads the other lanes' writes.  No block barrier: the
+// slices are per wave, so a wave waiting for its copy does not hold up the others.
+__device__ __forceinline__ void wave_publish() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
 }
 
 constexpr int kPodBatch = 64;  // one-selection pod records staged in LDS per round and wave
@@ -804,23 +818,8 @@ __device__ __forceinline__ uint32_t fit_mask(const int64_t (&need)[C],
                                              const int64_t (&fr)[kMaxCards][C], uint64_t live) {
   uint32_t bm = 0u;
   if constexpr (C == 1) {
-#ifdef PAS_C1_PERCARD
-#pragma unroll
-    for (int k = kMaxCards - 1; k >= 0; --k) {
-      uint32_t r;
-      uint64_t m0, co;
-      asm("v_cmp_le_i64_e64 %1, %3, %4\n\t"
-          "s_and_b64 %1, %1, %5\n\t"
-          "v_addc_co_u32_e64 %0, %2, %6, %6, %1"
-          : "=&v"(r), "=&s"(m0), "=&s"(co)
-          : "v"(need[0]), "v"(fr[k][0]), "s"(live), "v"(bm)
-          : "scc");
-      bm = r;
-    }
-#else
     bm = push4_c1(bm, need[0], fr[7][0], fr[6][0], fr[5][0], fr[4][0], live);
     bm = push4_c1(bm, need[0], fr[3][0], fr[2][0], fr[1][0], fr[0][0], live);
-#endif
   } else if constexpr (C == 2) {
     bm = push4_c2(bm, need[0], need[1], fr[7][0], fr[7][1], fr[6][0], fr[6][1], fr[5][0],
                   fr[5][1], fr[4][0], fr[4][1]);
@@ -840,23 +839,6 @@ __device__ __forceinline__ uint32_t fit_mask(const int64_t (&need)[C],
 
 constexpr int kMB = 2;  // multi-selection pods staged in LDS per round and wave (LDS: 4 workgroups per CU)
 constexpr int kRowChunks = kPacked * (int)sizeof(GasSel) / 16;  // 16-B chunks per row
-template <int Q, int SKIP>
-__device__ __forceinline__ uint32_t th_mask(const int64_t (&free)[kMaxCards][Q], const int64_t* th,
-                                            uint64_t live) {
-  constexpr int kSkip = Q == 1 ? -1 : SKIP;  // a selection's only kind is never skipped
-  constexpr int kC = Q - (kSkip >= 0 ? 1 : 0);
-  int64_t need[kC];
-  int64_t fr[kMaxCards][kC];
-#pragma unroll
-  for (int q = 0, j = 0; q < Q; ++q)
-    if (q != kSkip) need[j++] = th[q];
-#pragma unroll
-  for (int k = 0; k < kMaxCards; ++k)
-#pragma unroll
-    for (int q = 0, j = 0; q < Q; ++q)
-      if (q != kSkip) fr[k][j++] = free[k][q];
-  return fit_mask<kC>(need, fr, live);
-}
 
 // v_ffbl_b32: the lowest set bit of a lane mask, 0xFFFFFFFF for none, in one instruction (the
 // C form adds a compare and a select for the zero case)
@@ -1156,9 +1138,7 @@ __device__ __forceinline__ void load_sorted(const int64_t* __restrict__ srt, int
 #pragma unroll
     for (int j = 0; j < C; ++j) lds[j * kRankItems + e] = x[it][j];
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+  wave_publish();
 }
 
 // Four upper-bound levels at once: pos[k] = 2 pos[k] + (x[k] <= f[k]).  The compares go first
@@ -1284,11 +1264,12 @@ __device__ __forceinline__ void fill_tab_t(const int64_t* __restrict__ free_t, i
   fill_tab<Q, SKIP, kC>(free, tab, lane);
 }
 
-// A pod with 4 to 8 selections: the selections in order on a working copy of the free values
-// (registers, loaded from the card-major copy per pod: the rare list without a skipped kind
-// keeps no second copy live), each a fit mask on the copy; the chosen card's copy drops by
-// the take, updated under the lanes that chose it (one branch per card some lane chose).
-template <int Q, int SKIP>
+// A pod with 4 to 8 selections of a list without a skipped kind (list 0, and every list when
+// there is one kind): the selections in order on a working copy of the free values (registers,
+// loaded from the card-major copy per pod: this rare path keeps no second copy live), each a
+// 64-bit fit mask over all Q kinds on the copy; the chosen card's copy drops by the take,
+// updated under the lanes that chose it (one branch per card some lane chose).
+template <int Q>
 __device__ __forceinline__ uint32_t multi_state(const int64_t* __restrict__ free_t, int32_t n,
                                                 bool valid, int32_t N, const GasSel* rec,
                                                 int32_t S, uint64_t live, uint32_t node_ok) {
@@ -1305,7 +1286,7 @@ __device__ __forceinline__ uint32_t multi_state(const int64_t* __restrict__ free
       cmp[q] = ct.x;
       neg[q] = ct.y;
     }
-    const uint32_t c = lowest(th_mask<Q, SKIP>(w, cmp, live));
+    const uint32_t c = lowest(fit_mask<Q>(cmp, w, live));
     fits = fits && c < 8u;
     if (!__ballot(fits)) break;
 #pragma unroll
@@ -1318,37 +1299,26 @@ __device__ __forceinline__ uint32_t multi_state(const int64_t* __restrict__ free
   return fits ? (node_ok | ((uint32_t)S << 24) | word) : 0u;
 }
 
-// A pod with several selections, in order: selection t takes the first card (lexicographic)
-// whose current free covers its need (getCardsForContainerGPURequest, scheduler.go:200-257;
-// addRM after each take).  A card no earlier selection of the pod took from still has its
-// snapshot free, so the candidates are the fit mask of the need on the snapshot (free only
-// falls: a card outside the mask cannot pass); among them a card an earlier selection s took
-// from passes only if its current free cur[s] covers the need.  So
+// A pod with 4 to 8 selections of a list with a skipped kind, in order: selection t takes the
+// first card (lexicographic) whose current free covers its need
+// (getCardsForContainerGPURequest, scheduler.go:200-257; addRM after each take).  A card no
+// earlier selection of the pod took from still has its snapshot free, so the candidates are
+// the fit mask of the need on the snapshot (free only falls: a card outside the mask cannot
+// pass); among them a card an earlier selection s took from passes only if its current free
+// cur[s] covers the need.  So
 //   c_t = lowest(mask(need_t) without {c_s : s < t, need_t > cur[s]})
 // and the take lowers cur of every s with c_s = c_t (a card first taken reads its snapshot
 // free from the lane's LDS copy).  Registers only, unrolled over t; a selection whose need
 // equals the previous one's reuses its mask (the selections of one container are identical).
-
-// kRanked: the fit masks from the group ranks (rk: selection t's ranks per compared kind,
-// replicated; fa / fb the node's card ranks) instead of 64-bit compares; card k is then bit
-// 4k + 3 of a mask (rmask), else bit k.
-template <int Q, int SKIP, int kC, bool kRanked = false>
-__device__ __forceinline__ uint32_t multi_seq(const int64_t (*free)[Q],  // [kMaxCards][Q]; unused ranked
-                                              const GasSel* rec, int32_t S, uint64_t live,
-                                              uint32_t node_ok, const FreeTab<kC>& tab,
-                                              int lane, uint32_t same_row,
-                                              const uint32_t* rk = nullptr,
-                                              const uint32_t* fa = nullptr,
-                                              const uint32_t* fb = nullptr) {
+// The fit masks come from the group ranks (rk: selection t's ranks per compared kind,
+// replicated; fa / fb the node's card ranks), so card k is bit 4k + 3 of a mask (rmask); only
+// the current-free checks of cards already taken from are 64-bit compares.
+template <int Q, int SKIP, int kC>
+__device__ __forceinline__ uint32_t multi_seq(const GasSel* rec, int32_t S, uint32_t node_ok,
+                                              const FreeTab<kC>& tab, int lane, uint32_t same_row,
+                                              const GasRSeq& rk, const uint32_t (&fa)[kC],
+                                              const uint32_t (&fb)[kC]) {
   typedef int64_t v2i64 __attribute__((ext_vector_type(2)));
-  int64_t fr[kMaxCards][kC];
-  if constexpr (!kRanked) {
-#pragma unroll
-    for (int k = 0; k < kMaxCards; ++k)
-#pragma unroll
-      for (int q = 0, j = 0; q < Q; ++q)
-        if (q != SKIP) fr[k][j++] = free[k][q];
-  }
   int64_t cur[kPacked][kC];
   uint32_t cb[kPacked];  // the card of each earlier selection's entry, one-hot
   uint32_t word = 0u, m = 0u, bad_prev = 0u;
@@ -1366,20 +1336,7 @@ __device__ __forceinline__ uint32_t multi_seq(const int64_t (*free)[Q],  // [kMa
       }
     // same_row: nibble t all ones = selection t's record equals selection t - 1's
     const bool same = t > 0 && ((same_row >> (4 * t)) & 0xFu) == 0xFu;
-    if (!same) {
-      if constexpr (kRanked) {
-        uint32_t ga[kC], gfa[kC], gfb[kC];
-#pragma unroll
-        for (int j = 0; j < kC; ++j) {
-          ga[j] = rk[t * PAS_GAS_MAX_RES + j];
-          gfa[j] = fa[j];
-          gfb[j] = fb[j];
-        }
-        m = rmask<kC>(gfa, gfb, ga);
-      } else {
-        m = fit_mask<kC>(need, fr, live);
-      }
-    }
+    if (!same) m = rmask<kC>(fa, fb, rk.rep[t]);
     uint32_t bad = 0u;
     if (same) {
       // the need of step t - 1: the entries before t - 1 are unchanged since then (a take
@@ -1401,15 +1358,8 @@ __device__ __forceinline__ uint32_t multi_seq(const int64_t (*free)[Q],  // [kMa
     bad_prev = bad;
     // the chosen card, and its bit in the mask layout (a failed lane's later choices are
     // garbage: its word is 0 whatever they are)
-    uint32_t c, bc;
-    if constexpr (kRanked) {
-      const uint32_t pb = lowbit(m & ~bad);
-      c = pb >> 2;
-      bc = 1u << (pb & 31u);
-    } else {
-      c = lowest(m & ~bad);
-      bc = 1u << c;  // c = 8 (no card): bit 8, outside every 8-card mask
-    }
+    const uint32_t pb = lowbit(m & ~bad);
+    const uint32_t c = pb >> 2, bc = 1u << (pb & 31u);
     fit_m &= __ballot(c < 8u);  // (a lane mask in SGPRs: one compare per step)
     if (!fit_m) break;
     int64_t g[kC];
@@ -1438,28 +1388,21 @@ __device__ __forceinline__ uint32_t multi_seq(const int64_t (*free)[Q],  // [kMa
   return ((fit_m >> lane) & 1u) ? (node_ok | ((uint32_t)S << 24) | word) : 0u;
 }
 
-// Pods of 4 to 8 selections (list `list`, kind SKIP = list - 1 dropped).  Each wave stages
-// the rows of kMB pods in its own LDS slice (one contiguous copy: rows sit in list order) and
-// reads them back with broadcast LDS reads (values in VGPRs).  No block barrier: a wave
-// waiting for its copy does not hold up the other waves of the block.
-template <int Q, int SKIP, bool kBits, class RO>
+// Pods of 4 to 8 selections of a list without a skipped kind, each evaluated on 64-bit values
+// (multi_state).  Each wave stages the rows of kMB pods in its own LDS slice (one contiguous
+// copy: rows sit in list order) and reads them back with broadcast LDS reads (values in
+// VGPRs).
+template <int Q, bool kBits, class RO>
 __device__ __forceinline__ void multi_list(const int64_t* __restrict__ free_t, GasSel* stage,
-                                           int64_t* tab_base, uint32_t node_ok,
-                                           int32_t N, int32_t n, bool valid,
+                                           uint32_t node_ok, int32_t N, int32_t n, bool valid,
                                            const int32_t* __restrict__ list,
                                            const GasSel* __restrict__ sels,
                                            const int32_t* __restrict__ count, const BlockTile& bt,
-                                           RO res,
-                                           uint64_t* __restrict__ fit) {
+                                           RO res, uint64_t* __restrict__ fit) {
   const int32_t lane = threadIdx.x & 63;
   const uint64_t live = __ballot(valid && node_ok != 0u);
   int32_t i0, i1;
   list_share(count, bt, &i0, &i1);
-  // lists with a skipped kind read chosen cards back from the lane's LDS copy (kC = Q - 1)
-  constexpr bool kGather = Q > 1 && SKIP >= 0;
-  constexpr int kC = Q > 1 ? Q - 1 : 1;
-  const FreeTab<kC> tab{tab_base};
-  if (kGather && i0 < i1) fill_tab_t<Q, SKIP, kC>(free_t, n, valid, N, tab, lane);
   // a batch's rows are loaded one batch ahead: every load of the next batch is in flight
   // while this batch's pods are evaluated (rows past the batch: zeros, not read)
   constexpr int kIters = kMB * kRowChunks / 64;
@@ -1481,19 +1424,7 @@ __device__ __forceinline__ void multi_list(const int64_t* __restrict__ free_t, G
     __builtin_amdgcn_wave_barrier();  // the previous batch's stage reads are done
 #pragma unroll
     for (int it = 0; it < kIters; ++it) reinterpret_cast<int4*>(stage)[lane + it * 64] = v[it];
-    // for the sequential class: which selections repeat the previous one, for the whole batch
-    // in one ballot (lane l holds 16-B piece l % 4 of selection (l % 32) / 4 of row l / 32)
-    static_assert(kIters == 1 && kMB * kRowChunks == 64 && sizeof(GasSel) == 64, "pieces");
-    uint64_t same_m;
-    {
-      const int4 u = v[0];
-      const int ux = __shfl_up(u.x, 4, 64), uy = __shfl_up(u.y, 4, 64);
-      const int uz = __shfl_up(u.z, 4, 64), uw = __shfl_up(u.w, 4, 64);
-      same_m = __ballot((lane & 31) >= 4 && u.x == ux && u.y == uy && u.z == uz && u.w == uw);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+    wave_publish();
     // the batch's pod words straight from the staging register (lane j: pod j's word)
     const int32_t wcur = wd;
     load_batch(b0 + kMB);
@@ -1504,25 +1435,15 @@ __device__ __forceinline__ void multi_list(const int64_t* __restrict__ free_t, G
       const GasSel* rec = stage + j * kPacked;
       if (!kBits && S > kPacked) continue;  // the generic kernel's row (it runs beside this one)
       uint32_t out = 0u;
-      if (!(pw & kBadPod)) {
-        if (S <= kPacked) {  // 4..8 in order (more: the generic kernel's, 0 here)
-          if constexpr (kGather) {
-            int64_t free[kMaxCards][Q];
-            load_free_t<Q>(n, valid, N, free_t, free);
-            out = multi_seq<Q, SKIP, kC>(free, rec, S, live, node_ok, tab, lane,
-                                         (uint32_t)(same_m >> (32 * j)));
-          } else {
-            out = multi_state<Q, SKIP>(free_t, n, valid, N, rec, S, live, node_ok);
-          }
-        }
-      }
+      if (!(pw & kBadPod) && S <= kPacked)  // more: the generic kernel's (bitmaps: 0 here)
+        out = multi_state<Q>(free_t, n, valid, N, rec, S, live, node_ok);
       put_result<kBits>(res, fit, pod, N, n, valid, out);
     }
   }
 }
 
 // Pods of 4 to 8 selections of a list with a skipped kind, with fit masks from group ranks
-// (multi_seq<..., true>): the list is cut into groups of 15 pods (8 rows each), a chunk takes
+// (multi_seq): the list is cut into groups of 15 pods (8 rows each), a chunk takes
 // whole groups; per group the node's cards are ranked once, then batches of kMB pods (their
 // 64-bit rows for the current-free checks and their rank rows) are staged as in multi_list.
 // LDS: the FreeTab copy, then the sorted rows of the ranking, overlaid by the batch stage.
@@ -1564,15 +1485,15 @@ __device__ __forceinline__ void rseq_list(const int64_t* __restrict__ free_t, ch
       __builtin_amdgcn_wave_barrier();  // the previous batch's (or the ranking's) reads are done
       reinterpret_cast<int4*>(stage)[lane] = v;
       if (lane < kMB * kRWords) reinterpret_cast<int4*>(rstage)[lane] = rv;
-      uint64_t same_m;  // selections repeating the previous one (as multi_list)
+      // which selections repeat the previous one, for the whole batch in one ballot (lane l
+      // holds 16-B piece l % 4 of selection (l % 32) / 4 of row l / 32)
+      uint64_t same_m;
       {
         const int ux = __shfl_up(v.x, 4, 64), uy = __shfl_up(v.y, 4, 64);
         const int uz = __shfl_up(v.z, 4, 64), uw = __shfl_up(v.w, 4, 64);
         same_m = __ballot((lane & 31) >= 4 && v.x == ux && v.y == uy && v.z == uz && v.w == uw);
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+      wave_publish();
       const GasSel* st = lane_ptr(stage);  // (lane_ptr: record reads at immediate offsets)
       const GasRSeq* rst = lane_ptr(rstage);
       for (int32_t j = 0; j < nb; ++j) {
@@ -1582,9 +1503,8 @@ __device__ __forceinline__ void rseq_list(const int64_t* __restrict__ free_t, ch
         if (!kBits && S > kPacked) continue;  // the generic kernel's row (it runs beside this one)
         uint32_t out = 0u;
         if (!(pw & kBadPod) && S <= kPacked)  // more: the generic kernel's (bitmaps: 0 here)
-          out = multi_seq<Q, SKIP, kC, true>(nullptr, st + j * kPacked, S, 0, node_ok, tab, lane,
-                                             (uint32_t)(same_m >> (32 * j)),
-                                             &rst[j].rep[0][0], fa, fb);
+          out = multi_seq<Q, SKIP, kC>(st + j * kPacked, S, node_ok, tab, lane,
+                                       (uint32_t)(same_m >> (32 * j)), rst[j], fa, fb);
         put_result<kBits>(res, fit, pod, N, n, valid, out);
       }
     }
@@ -1725,9 +1645,7 @@ __device__ __forceinline__ void rfour_list(const int64_t* __restrict__ free_t, c
       for (int it = 0; it < kIters; ++it)
         if (lane + 64 * it < kFourMB * kPieces) reinterpret_cast<int4*>(stage)[lane + 64 * it] = v[it];
       if (lane < kFourMB * kRPieces) reinterpret_cast<int4*>(rstage)[lane] = rv;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+      wave_publish();
       const FourStage* st = lane_ptr(stage);  // (lane_ptr: record reads at immediate offsets)
       const GasRFour* rst = lane_ptr(rstage);
 #pragma unroll
@@ -1765,8 +1683,10 @@ __device__ __forceinline__ void four_lists(const int64_t* __restrict__ free_t, c
                                 item0 + (int64_t)cnt * 4, counts, bt, res, fit);
 }
 
-// The lists of pods with 4 to 8 selections (class 2 of each kind-skip list): ranked where a
-// kind is skipped (rseq_list), else on 64-bit values (multi_list).  item0: the first sorted
+// The lists of pods with 4 to 8 selections (class kClsSeq of each kind-skip list).  List 0
+// skips no kind, and with one kind (Q == 1) no list does (a selection's only kind is never
+// skipped): those go through multi_list, in order on 64-bit values.  Lists 1 .. Q of Q > 1
+// kinds skip kind l - 1 and go through rseq_list, on group ranks.  item0: the first sorted
 // row of list 1's groups (after the two- and three-selection lists' rows).
 template <int Q, bool kBits, int l = 0, class RO>
 __device__ __forceinline__ void seq_lists(const int64_t* __restrict__ free_t, char* wlds,
@@ -1777,13 +1697,12 @@ __device__ __forceinline__ void seq_lists(const int64_t* __restrict__ free_t, ch
                                           const int64_t* __restrict__ srt, int64_t item0,
                                           const int32_t* __restrict__ counts, const BlockTile& bt,
                                           RO res, uint64_t* __restrict__ fit) {
-  constexpr int L = l * kClasses + 2;
+  constexpr int L = l * kClasses + kClsSeq;
   int32_t cnt = 0;
   if constexpr (l == 0 || Q == 1) {
-    GasSel* stage = reinterpret_cast<GasSel*>(wlds);
-    int64_t* tab = reinterpret_cast<int64_t*>(stage + kPacked * kMB);
-    multi_list<Q, l - 1, kBits>(free_t, stage, tab, node_ok, N, n, valid, multi + (int64_t)L * P,
-                                sels + (int64_t)L * P * kPacked, counts + L, bt, res, fit);
+    multi_list<Q, kBits>(free_t, reinterpret_cast<GasSel*>(wlds), node_ok, N, n, valid,
+                         multi + (int64_t)L * P, sels + (int64_t)L * P * kPacked, counts + L, bt,
+                         res, fit);
   } else {
     cnt = __builtin_amdgcn_readfirstlane(counts[L]);
     rseq_list<Q, l - 1, kBits>(free_t, wlds, node_ok, N, n, valid, multi + (int64_t)L * P,
@@ -1858,9 +1777,7 @@ __device__ __forceinline__ void rsingle_list(const int64_t* __restrict__ free_t,
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int it = 0; it < kIters; ++it) reinterpret_cast<int4*>(stage)[lane + it * 64] = v[it];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+    wave_publish();
     // pods in pairs: both records read (broadcast LDS reads) before the first one's tests;
     // eight pods per iteration, so the records' LDS offsets are constants off one address
     for (int32_t j0 = 0; j0 < nb; j0 += 8) {
@@ -1941,7 +1858,7 @@ __device__ __forceinline__ void rfit_single_body(
 // kSoff: word results through put_result(ResSoff) (a batch of < 2^31 result bytes)
 template <int Q, bool kBits, bool kSoff>
 __global__ __launch_bounds__(kSingleTpb) void gas_rfit_single_kernel(
-    int32_t N, int32_t K, int32_t P, const int32_t* __restrict__ n_cards,
+    int32_t N, int32_t P, const int32_t* __restrict__ n_cards,
     const int64_t* __restrict__ free_t, const GasRSingle* __restrict__ rs, const int64_t* __restrict__ srt,
     const int32_t* __restrict__ counts, int32_t chunks, ResOut res,
     uint64_t* __restrict__ fit) {
@@ -1979,7 +1896,7 @@ __device__ __forceinline__ bool rpoint(uint32_t x, uint32_t gp) {
 template <int C, int S>
 __device__ __forceinline__ uint32_t rclosed(const uint32_t (&fa)[C], const uint32_t (&fb)[C],
                                            const GasRMulti& r, uint32_t w, const uint32_t* tab,
-                                           int lane, uint32_t node_ok) {
+                                           int lane) {
   uint32_t g0[C], g1[C];
 #pragma unroll
   for (int j = 0; j < C; ++j) {
@@ -2014,7 +1931,6 @@ __device__ __forceinline__ uint32_t rclosed(const uint32_t (&fa)[C], const uint3
   // base = pass | S: a complete word xors to a negative value (kept by the min), a negative
   // word to a positive one (0).  A node without cards (every free -1) has empty masks, so
   // node_ok is not needed here; bitmap results take it at the caller.
-  (void)node_ok;
   return (uint32_t)min(word ^ (int32_t)(0x80000000u | ((uint32_t)S << 24)), 0);
 }
 
@@ -2058,9 +1974,7 @@ __device__ __forceinline__ void rmulti_list(const int64_t* __restrict__ free_t, 
       const int32_t wd = lane < nb ? rw[b0 + lane] : 0;
       __builtin_amdgcn_wave_barrier();
       reinterpret_cast<int4*>(stage)[lane] = v;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+      wave_publish();
       // four pods per iteration: their records' LDS offsets are constants off one address
       for (int32_t j0 = 0; j0 < nb; j0 += 4) {
         const GasRMulti* st = lane_ptr(stage) + j0;
@@ -2068,7 +1982,7 @@ __device__ __forceinline__ void rmulti_list(const int64_t* __restrict__ free_t, 
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const uint32_t w = (uint32_t)__builtin_amdgcn_readlane(wd, j0 + u);
-            uint32_t out = rclosed<C, S>(fa, fb, st[u], w, tab, lane, node_ok);
+            uint32_t out = rclosed<C, S>(fa, fb, st[u], w, tab, lane);
             if constexpr (kBits) out = out ? node_ok : 0u;
             put_result<kBits>(res, fit, w & 0xFFFFFF, N, n, valid, out);
           }
@@ -2080,7 +1994,7 @@ __device__ __forceinline__ void rmulti_list(const int64_t* __restrict__ free_t, 
           const uint32_t w = (uint32_t)__builtin_amdgcn_readlane(wd, j0 + u);
           const int64_t pod = w & 0xFFFFFF;
           // (a bad pod's row 0 ranks 0x80: its word comes out 0)
-          uint32_t out = rclosed<C, S>(fa, fb, st[u], w, tab, lane, node_ok);
+          uint32_t out = rclosed<C, S>(fa, fb, st[u], w, tab, lane);
           if constexpr (kBits) out = out ? node_ok : 0u;
           put_result<kBits>(res, fit, pod, N, n, valid, out);
         }
@@ -2126,9 +2040,13 @@ struct MultiLds {
   static constexpr size_t kRows = sizeof(int64_t) * Q * kRankItems;
   static constexpr size_t kRowsOrStage =
       kRows > sizeof(GasRMulti) * kRankMB ? kRows : sizeof(GasRMulti) * kRankMB;
-  static constexpr size_t kRanked = kRowsOrStage + sizeof(uint32_t) * kMaxCards * 64;
-  // the sequential kernel: the FreeTab copy, then the sorted rows overlaid by a batch stage
-  // (sequential pods or closed-form four-selection pods)
+  static constexpr size_t kClosed = kRowsOrStage + sizeof(uint32_t) * kMaxCards * 64;
+  // the sequential kernel, lists with a skipped kind: the FreeTab copy (kC compared kinds),
+  // then the sorted rows overlaid by a batch stage (sequential pods or closed-form
+  // four-selection pods).  The lists without one (multi_list) only stage a batch of kMB pods'
+  // rows, at the slice's start: no table, no sorted rows.  The size is the former's for every
+  // Q (Q = 1 has no such list and leaves most of it unused): LDS per block decides how the
+  // three fit kernels share the CUs
   static constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
   static constexpr size_t kSeqOver =
       cmax(sizeof(int64_t) * kC * kRankItems,
@@ -2158,10 +2076,14 @@ __device__ __forceinline__ void rfit_closed_body(
 }
 
 // Waves per SIMD the closed-form kernel is compiled for.  Its LDS (the sorted rows overlaid
-// by the pod stage, MultiLds) allows 8 below four kinds.  With all three fit kernels side by
-// side, same box, C3 ms: 5 waves (96 VGPRs, 16 B of scratch per lane, the rows and the stage
-// apart) 0.710-0.723 -> 6 waves 0.684-0.692 -> overlay 0.660-0.668 -> 7 waves (72 VGPRs,
-// 112 B) 0.648-0.649; 8 waves (64 VGPRs, 144 B) 0.669-0.672; 4 waves 0.743-0.748.
+// by the pod stage, MultiLds) allows 8 below four kinds.  As measured in round 4, with that
+// round's toolchain and kernel, all three fit kernels side by side, same box, C3 ms: 5 waves
+// (96 VGPRs, 16 B of scratch per lane, the rows and the stage apart) 0.710-0.723 -> 6 waves
+// 0.684-0.692 -> overlay 0.660-0.668 -> 7 waves (72 VGPRs, 112 B) 0.648-0.649; 8 waves (64
+// VGPRs, 144 B) 0.669-0.672; 4 waves 0.743-0.748.  Today's toolchain compiles the kernel to
+// 56-66 VGPRs without scratch (56-58 / 58 / 60-61 / 66 for 1 / 2 / 3 / 4 kinds; DESIGN.md,
+// "GAS fit"), so the attribute no longer caps its registers (round 5 re-checked 6 against 7
+// waves: no change, DESIGN_LOG.md).
 #ifndef PAS_GAS_CLOSED_WAVES
 #define PAS_GAS_CLOSED_WAVES 7
 #endif
@@ -2169,11 +2091,11 @@ template <int Q>
 constexpr int closed_waves() { return Q < 4 ? PAS_GAS_CLOSED_WAVES : 5; }
 template <int Q, bool kBits, bool kSoff>
 __global__ __launch_bounds__(kClosedTpb) __attribute__((amdgpu_waves_per_eu(closed_waves<Q>()))) void gas_rfit_closed_kernel(
-    int32_t N, int32_t K, int32_t P, const int32_t* __restrict__ n_cards,
+    int32_t N, int32_t P, const int32_t* __restrict__ n_cards,
     const int64_t* __restrict__ free_t, const GasRMulti* __restrict__ rm,
     const int32_t* __restrict__ rw, const int64_t* __restrict__ srt,
     const int32_t* __restrict__ counts, int32_t chunks, ResOut res, uint64_t* __restrict__ fit) {
-  __shared__ int4 smem[kClosedTpb / 64][MultiLds<Q>::kRanked / 16];
+  __shared__ int4 smem[kClosedTpb / 64][MultiLds<Q>::kClosed / 16];
   if (fit_aborted(res.abort, res.epoch)) return;
   const int32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (kSoff)
@@ -2217,7 +2139,7 @@ __device__ __forceinline__ void rfit_seq_body(
 
 template <int Q, bool kBits, bool kSoff>
 __global__ __launch_bounds__(kSeqTpb) void gas_rfit_seq_kernel(
-    int32_t N, int32_t K, int32_t P, const int32_t* __restrict__ n_cards,
+    int32_t N, int32_t P, const int32_t* __restrict__ n_cards,
     const int64_t* __restrict__ free_t, const GasRSeq* __restrict__ rq,
     const GasRFour* __restrict__ rf, const int64_t* __restrict__ srt,
     const int32_t* __restrict__ multi, const GasSel* __restrict__ sels,
@@ -2489,29 +2411,28 @@ int gas_fit_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t
   // the fit kernels' 32-bit byte offsets into the card-major free table (free_at)
   if ((int64_t)N * PAS_GAS_MAX_RES * 8 > INT32_MAX)
     return set_error(ctx, PAS_ECAPACITY, "pas_gas_fit: more than 2^26 nodes");
-  // scratch: single-selection records [Q+1][P] | multi-selection pod words [Q+1][3][P] |
-  // their selection rows [Q+1][3][P][8] | the generic path's pods [P] and per-pod selection
-  // counts [P] | list counts [Q+1] + [(Q+1)3] and the generic pod count (zeroed together).  The flipped
-  // kind minima and the generic path's nodes depend on the snapshot alone: they sit in
-  // g.derived and are recomputed only after the snapshot changed.
+  // scratch, one carve of the call's slot (NL = Q + 1 lists, kClasses classes, P pods):
+  // single-selection records [NL][P] | multi-selection pod words [NL][kClasses][P] | their
+  // selection rows [NL][kClasses][P][8] | the generic path's pods [P] | per-pod selection
+  // counts [P] | the ranked paths' pod records: one selection [NL][P], two / three [NL][2][P]
+  // and their words | the sorted rows of the one-selection (<= P items) and multi-selection
+  // (<= 8 P items) groups | the ranked sequential [NL][P] and four-selection [NL][P] records.
+  // The list counts and the generic pod count are the slot's (gas_counts).  The flipped kind
+  // minima and the generic path's nodes depend on the snapshot alone: they sit in g.derived
+  // and are recomputed only after the snapshot changed.
   const int32_t NL = Q + 1;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t b_single = al(sizeof(GasSingle) * (size_t)NL * n_pods);
-  const size_t b_multi = al(sizeof(int32_t) * (size_t)NL * kClasses * n_pods);
-  const size_t b_sels = al(sizeof(GasSel) * kPacked * (size_t)NL * kClasses * n_pods);
-  const size_t b_pods = al(sizeof(int32_t) * (size_t)n_pods);
-  // ranked paths: pod records and sorted rows (items: <= P one-selection, <= 7P closed-form)
-  const size_t b_rs = al(sizeof(GasRSingle) * (size_t)NL * n_pods);
-  const size_t b_rm = al(sizeof(GasRMulti) * (size_t)NL * 2 * n_pods);
-  const size_t b_rw = al(sizeof(int32_t) * (size_t)NL * 2 * n_pods);
-  const size_t b_srs = al(sizeof(int64_t) * PAS_GAS_MAX_RES * (size_t)n_pods);
-  const size_t b_srm = al(sizeof(int64_t) * PAS_GAS_MAX_RES * kPacked * (size_t)n_pods);
-  const size_t b_rq = al(sizeof(GasRSeq) * (size_t)NL * n_pods);
-  const size_t b_rf = al(sizeof(GasRFour) * (size_t)NL * n_pods);
+  // element counts; the sizes and the takes below list the sub-buffers in the same order
+  const size_t P = (size_t)n_pods, lists = (size_t)NL * P;
+  const size_t n_multi = lists * kClasses, n_sels = n_multi * kPacked, n_rm = lists * 2;
+  const size_t n_srs = PAS_GAS_MAX_RES * P, n_srm = n_srs * kPacked;
   const bool empty = N == 0 || n_pods == 0;
-  const size_t need = empty ? 0
-                            : b_single + b_multi + b_sels + 2 * b_pods + b_rs + b_rm + b_rw +
-                                  b_srs + b_srm + b_rq + b_rf;
+  const size_t need =
+      empty ? 0
+            : carve_size({sizeof(GasSingle) * lists, sizeof(int32_t) * n_multi,
+                          sizeof(GasSel) * n_sels, sizeof(int32_t) * P, sizeof(int32_t) * P,
+                          sizeof(GasRSingle) * lists, sizeof(GasRMulti) * n_rm,
+                          sizeof(int32_t) * n_rm, sizeof(int64_t) * n_srs, sizeof(int64_t) * n_srm,
+                          sizeof(GasRSeq) * lists, sizeof(GasRFour) * lists});
   // the stream's scratch slot (ordered after its previous user on another stream)
   int rc = PAS_OK;
   AuxSlot* slot = aux_acquire(ctx, s, need, &rc);
@@ -2541,31 +2462,19 @@ int gas_fit_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t
     if (d_side_count) PAS_HIP(ctx, hipMemsetAsync(d_side_count, 0, sizeof(int64_t), s));
     return PAS_OK;
   }
-  char* base = static_cast<char*>(slot->p);
-  GasSingle* single = reinterpret_cast<GasSingle*>(base);
-  base += b_single;
-  int32_t* multi = reinterpret_cast<int32_t*>(base);
-  base += b_multi;
-  GasSel* sels = reinterpret_cast<GasSel*>(base);
-  base += b_sels;
-  int32_t* big_pods = reinterpret_cast<int32_t*>(base);
-  base += b_pods;
-  int32_t* pod_steps = reinterpret_cast<int32_t*>(base);
-  base += b_pods;
-  GasRSingle* rsingle = reinterpret_cast<GasRSingle*>(base);
-  base += b_rs;
-  GasRMulti* rmulti = reinterpret_cast<GasRMulti*>(base);
-  base += b_rm;
-  int32_t* rword = reinterpret_cast<int32_t*>(base);
-  base += b_rw;
-  int64_t* srt_s = reinterpret_cast<int64_t*>(base);
-  base += b_srs;
-  int64_t* srt_m = reinterpret_cast<int64_t*>(base);
-  base += b_srm;
-  GasRSeq* rseq = reinterpret_cast<GasRSeq*>(base);
-  base += b_rq;
-  GasRFour* rfour = reinterpret_cast<GasRFour*>(base);
-  base += b_rf;
+  Carve cv{static_cast<char*>(slot->p)};
+  GasSingle* single = cv.take<GasSingle>(lists);
+  int32_t* multi = cv.take<int32_t>(n_multi);
+  GasSel* sels = cv.take<GasSel>(n_sels);
+  int32_t* big_pods = cv.take<int32_t>(P);
+  int32_t* pod_steps = cv.take<int32_t>(P);
+  GasRSingle* rsingle = cv.take<GasRSingle>(lists);
+  GasRMulti* rmulti = cv.take<GasRMulti>(n_rm);
+  int32_t* rword = cv.take<int32_t>(n_rm);
+  int64_t* srt_s = cv.take<int64_t>(n_srs);
+  int64_t* srt_m = cv.take<int64_t>(n_srm);
+  GasRSeq* rseq = cv.take<GasRSeq>(lists);
+  GasRFour* rfour = cv.take<GasRFour>(lists);
   // this fit's list counts (zeroed by the previous fit's prep kernel, or at allocation) and
   // the other set, which this fit's prep kernel zeroes for the next one
   int32_t* counts = slot->gas_counts + kCounts * slot->gas_counts_set;
@@ -2667,33 +2576,11 @@ int gas_fit_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t
   const bool bits = d_fit != nullptr;
   // the wide shapes: the lists' lengths are on the device, so the grid is fixed and threads
   // past the work return at once
-  GenericArgs ga;
-  ga.N = N;
-  ga.K = K;
-  ga.Q = Q;
-  ga.C = max_containers;
-  ga.i915 = i915_index;
-  ga.n_cards = g.n_cards;
-  ga.cap = g.cap;
-  ga.used = g.used;
-  ga.req = d_req;
-  ga.mask = d_req_mask;
-  ga.ncont = d_n_containers;
-  ga.big_pods = big_pods;
-  ga.n_big_pods = n_big_pods;
-  ga.big_nodes = big_nodes;
-  ga.n_big_nodes = n_big_nodes;
-  ga.pod_steps = pod_steps;
-  ga.n_pods = n_pods;
-  ga.res = d_res;
-  ga.ld = ld_res;
-  ga.fit = d_fit;
-  ga.side = d_side;
-  ga.side_cap = d_side ? side_cap : 0;
-  ga.side_count = reinterpret_cast<unsigned long long*>(d_side_count);
-  ga.limit_count = reinterpret_cast<unsigned long long*>(slot->gas_limit);
-  ga.abort = abort_flag;
-  ga.epoch = epoch;
+  const GenericArgs ga{N, K, Q, max_containers, i915_index, g.n_cards, g.cap, g.used, d_req,
+                       d_req_mask, d_n_containers, big_pods, n_big_pods, big_nodes, n_big_nodes,
+                       pod_steps, n_pods, d_res, ld_res, d_fit, d_side, d_side ? side_cap : 0,
+                       reinterpret_cast<unsigned long long*>(d_side_count),
+                       reinterpret_cast<unsigned long long*>(slot->gas_limit), abort_flag, epoch};
   const ResOut ro{d_res, ld_res, abort_flag, epoch};
   auto generic = [&](hipStream_t st) {
     constexpr int kGenericBlocks = 512;
@@ -2747,23 +2634,17 @@ int gas_fit_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t
   // into the fast kernels' words, so it runs after the join
   // word results of < 2^31 bytes: row offsets as the stores' 32-bit scalar offsets (ResSoff)
   const bool soff = !bits && (int64_t)n_pods * ld_res * 4 < ((int64_t)1 << 31);
+  const int64_t* free_t = static_cast<const int64_t*>(g.free_t);
   switch (Q * 4 + (bits ? 1 : 0) * 2 + (soff ? 1 : 0)) {
 #define PAS_GAS_CASE(QQ, B, SO)                                                                \
   case QQ * 4 + B * 2 + SO:                                                                    \
-    if (PAS_GAS_SEQ_FIRST)                                                                     \
-      gas_rfit_seq_kernel<QQ, B, SO><<<nb_q * ch_q, kSeqTpb, 0, qs>>>(                         \
-          N, K, n_pods, g.n_cards, static_cast<int64_t*>(g.free_t), rseq, rfour, srt_m, multi, \
-          sels, counts + NL, ch_q, ro, d_fit);                                                  \
     gas_rfit_closed_kernel<QQ, B, SO><<<nb_c * ch_c, kClosedTpb, 0, s>>>(                      \
-        N, K, n_pods, g.n_cards, static_cast<int64_t*>(g.free_t), rmulti, rword, srt_m,         \
-        counts + NL, ch_c, ro, d_fit);                                                          \
-    if (!PAS_GAS_SEQ_FIRST)                                                                    \
-      gas_rfit_seq_kernel<QQ, B, SO><<<nb_q * ch_q, kSeqTpb, 0, qs>>>(                         \
-          N, K, n_pods, g.n_cards, static_cast<int64_t*>(g.free_t), rseq, rfour, srt_m, multi, \
-          sels, counts + NL, ch_q, ro, d_fit);                                                  \
+        N, n_pods, g.n_cards, free_t, rmulti, rword, srt_m, counts + NL, ch_c, ro, d_fit);      \
+    gas_rfit_seq_kernel<QQ, B, SO><<<nb_q * ch_q, kSeqTpb, 0, qs>>>(                           \
+        N, n_pods, g.n_cards, free_t, rseq, rfour, srt_m, multi, sels, counts + NL, ch_q, ro,   \
+        d_fit);                                                                                 \
     gas_rfit_single_kernel<QQ, B, SO><<<nb_s * ch_s, kSingleTpb, 0, ss>>>(                     \
-        N, K, n_pods, g.n_cards, static_cast<int64_t*>(g.free_t), rsingle, srt_s, counts,       \
-        ch_s, ro, d_fit);                                                                       \
+        N, n_pods, g.n_cards, free_t, rsingle, srt_s, counts, ch_s, ro, d_fit);                 \
     break;
     PAS_GAS_CASE(1, 0, 0) PAS_GAS_CASE(2, 0, 0) PAS_GAS_CASE(3, 0, 0) PAS_GAS_CASE(4, 0, 0)
     PAS_GAS_CASE(1, 0, 1) PAS_GAS_CASE(2, 0, 1) PAS_GAS_CASE(3, 0, 1) PAS_GAS_CASE(4, 0, 1)

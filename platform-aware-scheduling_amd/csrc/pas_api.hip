@@ -224,23 +224,6 @@ void free_gas(pas_ctx* ctx) {
   g.derived_sync.ev = ev;
 }
 
-struct Carve {
-  char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(base + off);
-    off += (count * sizeof(T) + 255) & ~size_t(255);
-    return p;
-  }
-};
-
-static size_t carve_size(std::initializer_list<size_t> sizes) {
-  size_t s = 0;
-  for (size_t b : sizes) s += (b + 255) & ~size_t(255);
-  return s;
-}
-
 }  // namespace pas
 
 using namespace pas;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -201,6 +202,24 @@ struct AuxSlot {
   size_t buf_bytes[kSlotBufs] = {};
 };
 constexpr int kAuxSlots = 4;
+
+// Sub-buffers of one scratch allocation, each rounded up to 256 bytes: carve_size() of the
+// sub-buffers' byte sizes is what take() of their element counts, in the same order, uses.
+struct Carve {
+  char* base;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* p = reinterpret_cast<T*>(base + off);
+    off += (count * sizeof(T) + 255) & ~size_t(255);
+    return p;
+  }
+};
+inline size_t carve_size(std::initializer_list<size_t> sizes) {
+  size_t s = 0;
+  for (size_t b : sizes) s += (b + 255) & ~size_t(255);
+  return s;
+}
 
 struct TimedLaunch {
   hipEvent_t start;

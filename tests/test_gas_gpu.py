@@ -337,3 +337,152 @@ def test_fits_alternating_streams(oracle):
             np.testing.assert_array_equal(res.cpu().numpy().view(np.uint32), want[i])
     finally:
         c.close()
+
+
+# ---- every list and class of the fit kernels, by construction (test_every_list_and_class)
+ELC_N, ELC_K, ELC_C = 130, 9, 4  # two full waves and a 2-lane tail; one node has 9 cards
+
+
+def elc_pods(q, rng):
+    """Pods by chosen selection count S (i915 is kind 0; a container of ni selections asks ni of
+    it and ni x its per-GPU need of every other kind, 1..10): 3 of S = 0, 130 of S = 1 (a rank
+    group of 127 and 3, a partial batch of 64, a partial run of 8), 43 of S = 2 (groups of 42),
+    19 of S = 3 (groups of 18), 33 of S = 4 (groups of 31 in the closed-form class), 17 over
+    S = 5..8 (groups of 15; 18 with the next), one of S = 9 (the generic kernel's), all asking
+    every kind: a list's last group is then short and its last batch partial.  Then two each
+    of S = 1..5 that ask i915 alone (nothing to skip: list 0 in every snapshot), and one bad
+    pod of S = 2: a negative need, or with one kind, where a selecting pod has none, the
+    unknown-kind flag."""
+    full = (1 << q) - 1
+    shapes = ([0] * 3 + [1] * 130 + [2] * 43 + [3] * 19 + [4] * 33 + [5 + i % 4 for i in range(17)]
+              + [9])
+    alone = len(shapes)  # from here: i915 alone
+    shapes += [1, 1, 2, 2, 3, 3, 4, 4, 5, 5]
+    p = len(shapes) + 1
+    req = np.zeros((p, ELC_C, q), np.int64)
+    mask = np.zeros((p, ELC_C), np.uint32)
+    ncont = np.zeros(p, np.int32)
+    for pi, s in enumerate(shapes):
+        if s == 0:  # no container / a container without kinds / one that selects no card
+            ncont[pi] = min(pi, 1)
+            mask[pi, 0] = full if pi == 2 else 0
+            req[pi, 0, 1:] = 5
+            continue
+        splits = [(s,)] + [(1, s - 1), (s - 1, 1)] * (s > 1) + [(2, s - 2)] * (s > 3)
+        splits += [(1,) * s] * (2 < s <= ELC_C)
+        split = splits[pi % len(splits)]
+        ncont[pi] = len(split)
+        for ci, ni in enumerate(split):
+            req[pi, ci, 0] = ni
+            req[pi, ci, 1:] = rng.integers(1, 11, size=q - 1) * ni
+            mask[pi, ci] = 1 if pi >= alone else full
+    ncont[-1] = 2
+    req[-1, :2, 0] = 1
+    req[-1, :2, 1:] = 3
+    mask[-1, :2] = full
+    if q > 1:
+        req[-1, 1, q - 1] = -3
+    else:
+        mask[-1, 1] |= pas_amd._lib.PAS_REQ_UNKNOWN_KIND
+    return req, mask, ncont
+
+
+def elc_snapshot(q, rng, roomy):
+    """n_cards from -1, 0, 1..8 and one node of 9.  roomy = None, the tight snapshot: a real
+    card with negative used in every kind, so every kind minimum is -1.  roomy = j: every real
+    card keeps >= 100 of kind j free (a pod's total take is <= 90) and a full card (free 0, every
+    need is >= 1) makes the other kinds tight, so exactly kind j is skippable."""
+    n_cards = rng.integers(-1, 9, size=ELC_N).astype(np.int32)
+    n_cards[0], n_cards[77] = 3, 9
+    cap = np.full((ELC_N, q), 40, np.int64)
+    cap[:, 0] = 4
+    used = rng.integers(0, 41, size=(ELC_N, ELC_K, q)).astype(np.int64)
+    used[:, :, 0] = rng.integers(0, 5, size=(ELC_N, ELC_K))
+    if roomy is None:
+        used[0, 0, :] = -1
+    else:
+        used[0, 0, :] = cap[0]
+        cap[:, roomy] = 1000
+        used[:, :, roomy] = rng.integers(0, 901, size=(ELC_N, ELC_K))
+    return n_cards, cap, used
+
+
+def elc_filing(n_cards, cap, used, req, mask, ncont):
+    """Per pod (single?, list, class) by the filing rule of csrc/gas_fit.hip's header comment
+    (i915 = kind 0), restated here; classes: 2, 3, 4 (closed form) or "seq"."""
+    _, k, q = used.shape
+    real = np.arange(k)[None, :] < np.minimum(n_cards, k)[:, None]
+    free = np.where((cap[:, None, :] > 0) & (used >= 0), cap[:, None, :] - used, -1)
+    gmin = [int(free[:, :, j][real].min()) for j in range(q)]
+    filed = []
+    for p in range(len(ncont)):
+        sels = []  # per selection: (requested kinds, per-GPU need per kind)
+        for c in range(ncont[p]):
+            m = int(mask[p, c]) & ((1 << q) - 1)
+            ni = int(req[p, c, 0]) if m & 1 and req[p, c, 0] > 0 else 0
+            if m == 0 or ni == 0:
+                continue
+            need = [int(v) if ni == 1 else int(abs(v) // ni * np.sign(v)) for v in req[p, c]]
+            sels += [(m, need)] * ni
+        lst = 0
+        if len(sels) == 1:
+            m, need = sels[0]
+            ok = [j for j in range(q) if m >> j & 1 and m != 1 << j and need[j] <= gmin[j]]
+            lst = 1 + ok[0] if ok else 0
+        elif len(sels) > 1:
+            for j in reversed(range(q)):
+                asking = [s for s in sels if s[0] >> j & 1]
+                if (asking and all(m != 1 << j for m, _ in asking)
+                        and sum(max(need[j], 0) for _, need in asking) <= gmin[j]):
+                    lst = 1 + j
+        s = len(sels)
+        filed.append((s <= 1, lst, None if s <= 1 else s if s < 4 or (s == 4 and lst) else "seq"))
+    return gmin, filed
+
+
+@pytest.mark.parametrize("q", [1, 2, 3, 4])
+def test_every_list_and_class(ctx, oracle, q):
+    """Every single list 0..q and every multi (list, class) pair of the fit kernels that can be
+    non-empty, reached by construction: a tight snapshot files every pod under list 0 (the
+    64-bit in-order path for S >= 4), and for each kind j a roomy snapshot in which exactly
+    kind j is skippable files the pods that request it under list 1 + j.  The filing is
+    asserted on the CPU first; then words and node bitmaps against the oracle."""
+    import torch
+    rng = np.random.default_rng(8100 + q)
+    req, mask, ncont = elc_pods(q, rng)
+    snaps = [elc_snapshot(q, rng, roomy) for roomy in [None] + list(range(q))]
+    singles, multis = {}, {}
+    for si, snap in enumerate(snaps):
+        gmin, filed = elc_filing(*snap, req, mask, ncont)
+        if si == 0:  # tight: list 0 alone
+            assert gmin == [-1] * q and {lst for _, lst, _ in filed} == {0}
+        elif q > 1:  # roomy: kind si - 1 alone is skippable
+            assert gmin[si - 1] >= 100 and all(g == 0 for j, g in enumerate(gmin) if j != si - 1)
+            assert {lst for _, lst, _ in filed} == {0, si}
+        for one, lst, cls in filed:
+            if one:
+                singles[lst] = singles.get(lst, 0) + 1
+            else:
+                multis[lst, cls] = multis.get((lst, cls), 0) + 1
+    lists = range(q + 1) if q > 1 else [0]  # one kind: a selection's only kind is never skipped
+    assert sorted(singles) == list(lists) and min(singles.values()) >= 2
+    want_multi = {(li, c) for li in lists for c in (2, 3, "seq")} | {(li, 4) for li in lists if li}
+    assert set(multis) == want_multi and min(multis.values()) >= 2
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    p = len(ncont)
+    d_req, d_mask, d_nc = dev(req), dev(mask.view(np.int32)), dev(ncont)
+    for snap in snaps:
+        want = oracle.gas_fit(*snap, req, mask, ncont, 0)
+        _gen[0] += 1
+        ctx.gas_snapshot_set(_gen[0], *snap)
+        res = torch.zeros((p, ELC_N), dtype=torch.int32, device="cuda")
+        bm = torch.zeros((p, (ELC_N + 63) // 64), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        ctx.gas_fit_device(_gen[0], p, ELC_C, 0, d_req, d_mask, d_nc, res)
+        ctx.gas_fit_bitmap_device(_gen[0], p, ELC_C, 0, d_req, d_mask, d_nc, bm)
+        ctx.synchronize()
+        got = res.cpu().numpy().view(np.uint32)
+        np.testing.assert_array_equal(got, want)
+        bits = wl.unpack_bits(bm.cpu().numpy().view(np.uint64), ELC_N)
+        np.testing.assert_array_equal(bits, (want >> 31).astype(bool))
+        np.testing.assert_array_equal(bits, (got >> 31).astype(bool))
