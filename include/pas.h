@@ -193,8 +193,10 @@ int pas_tas_snapshot_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen
  * and every rule compare against an integer target is exact:  v < t <=> whole < t,
  * v == t <=> whole == t and nano == 0,  v > t <=> whole > t or (whole == t and nano != 0).
  * Filter, prioritize, the deschedule sweep (both forms) and the request prioritize evaluate
- * wide columns; the top-k entry points (pas_tas_topk_device, pas_tas_gas_topk_device) return
- * PAS_ENOTEXACT while the resident snapshot holds a wide column (their merge keys are 64-bit).
+ * wide columns; so do the top-k entry points with wide merge records
+ * (pas_tas_topk_wide_device, pas_tas_gas_topk_wide_device and their merges).  The 64-bit
+ * record forms (pas_tas_topk_device, pas_tas_gas_topk_device) return PAS_ENOTEXACT while the
+ * resident snapshot holds a wide column: use the wide entry points there.
  * The contract is pas_tas_snapshot_update[_device]'s: gen_from is checked (PAS_ESTALE), the
  * generation moves to gen_to in the same call, only these columns' orders are rebuilt; the
  * _device form is asynchronous on hip_stream except for the copy of cols.  The host form
@@ -606,6 +608,66 @@ int pas_tas_gas_topk_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, in
 int pas_topk_merge_device(pas_ctx* ctx, int32_t n_pods, int32_t k, int32_t n_shards,
                           const int64_t* d_keys, const int32_t* d_nodes, int32_t* d_out_node,
                           int32_t* d_out_len, void* hip_stream);
+
+/* Wide merge records: the same node-sharded top-k, exact on snapshots that hold wide columns
+ * (pas_tas_snapshot_update_wide) and across shards that hold one metric in different forms.
+ * A wide record is (key int64, sub uint32, node int32) in three arrays:
+ *   top_key [n_pods][k], top_sub [n_pods][k], top_node [n_pods][k], top_len [n_pods]
+ * Every record is in one canonical unit, whatever form the shard holds the prioritize column
+ * in.  The value of node n on metric m as the pair (W, F), value = W + F * 10^-9:
+ *   wide column    W = whole[m][n], F = nano[m][n]
+ *   narrow column  with multiplier 10^s (pas_tas_snapshot_set_scale, s = 0..9; milli: s = 3)
+ *                  and v the stored integer: W = floor(v / 10^s) toward -infinity,
+ *                  F = (v - W * 10^s) * 10^(9-s), so 0 <= F < 10^9 (-1500 at scale 3 is
+ *                  (-2, 500000000)); exact in 64-bit arithmetic
+ * Keys:
+ *   LessThan        key = W,  sub = F
+ *   GreaterThan     key = ~W, sub = ~F (32-bit complement)
+ *   other operator  key = 0,  sub = 0
+ *   past top_len    key = INT64_MAX, sub = UINT32_MAX, node = INT32_MAX
+ * Ascending (key signed, sub unsigned, node) is the HostPriorityList order: the pair order is
+ * the exact value order and ~ reverses both fields without overflow.  Because the unit is
+ * canonical, shards may hold the same metric narrow at different scales or wide and the
+ * merge is still exact (the 64-bit records of pas_tas_topk_device promise that only for one
+ * narrow scale on every shard).  The wide entry points work on any snapshot, one without a
+ * wide column included; ranks of one merge group must all use the same record form. */
+
+/* pas_tas_topk_device with wide records: the same lists (top_node, top_len), keyed in the
+ * canonical unit; d_top_sub [n_pods][k].  Never PAS_ENOTEXACT for a wide column. */
+int pas_tas_topk_wide_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_t n_rules,
+                             const pas_rule* d_rules, const int32_t* d_rule_off,
+                             const pas_rule* d_prio, const uint64_t* d_cand, int32_t k,
+                             int32_t node_base, int64_t* d_top_key, uint32_t* d_top_sub,
+                             int32_t* d_top_node, int32_t* d_top_len, void* hip_stream);
+
+/* pas_tas_gas_topk_device with wide records: dontschedule rules on wide columns are compared
+ * exactly (the target as it is against the pair), evaluated along each pod's order as there.
+ * Equal to pas_gas_fit_bitmap_device followed by pas_tas_topk_wide_device. */
+int pas_tas_gas_topk_wide_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                 int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+                                 const int32_t* d_rule_off, const pas_rule* d_prio,
+                                 const uint64_t* d_cand, int32_t max_containers,
+                                 int32_t i915_index, const int64_t* d_req,
+                                 const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                 int32_t k, int32_t node_base, int64_t* d_top_key,
+                                 uint32_t* d_top_sub, int32_t* d_top_node, int32_t* d_top_len,
+                                 void* hip_stream);
+
+/* pas_topk_merge_device over wide records: keys / subs / nodes [n_shards][n_pods][k], the k
+ * smallest (key, sub, node) records' nodes in order.  PAS_ECAPACITY when n_shards * k > 4096
+ * (16 bytes of LDS per record). */
+int pas_topk_merge_wide_device(pas_ctx* ctx, int32_t n_pods, int32_t k, int32_t n_shards,
+                               const int64_t* d_keys, const uint32_t* d_subs,
+                               const int32_t* d_nodes, int32_t* d_out_node, int32_t* d_out_len,
+                               void* hip_stream);
+
+/* pas_list_merge_device over wide records (pas_tas_topk_wide_device with k = width): keys /
+ * subs / nodes [n_shards][n_pods][width], merged by ascending (key, sub, node); the output
+ * is node ids only, as there. */
+int pas_list_merge_wide_device(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
+                               const int64_t* d_keys, const uint32_t* d_subs,
+                               const int32_t* d_nodes, int32_t* d_out_node, int64_t out_ld,
+                               int32_t* d_out_len, void* hip_stream);
 
 /* ------------------------------------------------------------------------- */
 /* Wire encoders, host only                                */

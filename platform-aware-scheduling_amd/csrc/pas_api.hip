@@ -1339,27 +1339,81 @@ int pas_tas_deschedule_device(pas_ctx* ctx, uint64_t gen, int32_t n_strategies,
 
 // --------------------------------------------------------------------------- node shards
 
+// (d_top_sub: the wide entry points' third record array; fn names the entry point)
+static int tas_topk_api(pas_ctx* ctx, const char* fn, bool wide, uint64_t gen, int32_t n_pods,
+                        int32_t n_rules, const pas_rule* d_rules, const int32_t* d_rule_off,
+                        const pas_rule* d_prio, const uint64_t* d_cand, int32_t k,
+                        int32_t node_base, int64_t* d_top_key, uint32_t* d_top_sub,
+                        int32_t* d_top_node, int32_t* d_top_len, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  if (n_pods < 0 || n_rules < 0 || k < 1 || node_base < 0)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  if (!wide && (rc = check_no_wide(ctx, fn))) return rc;
+  if ((int64_t)node_base + ctx->tas.n_nodes > INT32_MAX)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": node ids past int32");
+  if (n_pods == 0) return PAS_OK;
+  if (!d_rule_off || !d_prio || (n_rules > 0 && !d_rules) || !d_top_key || !d_top_node ||
+      !d_top_len || (wide && !d_top_sub))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
+  if ((rc = activate(ctx))) return rc;
+  return tas_topk_launch(ctx, n_pods, n_rules, d_rules, d_rule_off, d_prio, d_cand, k,
+                         node_base, d_top_key, wide ? d_top_sub : nullptr, d_top_node,
+                         d_top_len, pick_stream(ctx, hip_stream));
+}
+
 int pas_tas_topk_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_t n_rules,
                         const pas_rule* d_rules, const int32_t* d_rule_off,
                         const pas_rule* d_prio, const uint64_t* d_cand, int32_t k,
                         int32_t node_base, int64_t* d_top_key, int32_t* d_top_node,
                         int32_t* d_top_len, void* hip_stream) {
+  return tas_topk_api(ctx, "pas_tas_topk_device", false, gen, n_pods, n_rules, d_rules,
+                      d_rule_off, d_prio, d_cand, k, node_base, d_top_key, nullptr, d_top_node,
+                      d_top_len, hip_stream);
+}
+
+int pas_tas_topk_wide_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_t n_rules,
+                             const pas_rule* d_rules, const int32_t* d_rule_off,
+                             const pas_rule* d_prio, const uint64_t* d_cand, int32_t k,
+                             int32_t node_base, int64_t* d_top_key, uint32_t* d_top_sub,
+                             int32_t* d_top_node, int32_t* d_top_len, void* hip_stream) {
+  return tas_topk_api(ctx, "pas_tas_topk_wide_device", true, gen, n_pods, n_rules, d_rules,
+                      d_rule_off, d_prio, d_cand, k, node_base, d_top_key, d_top_sub,
+                      d_top_node, d_top_len, hip_stream);
+}
+
+static int tas_gas_topk_api(pas_ctx* ctx, const char* fn, bool wide, uint64_t tas_gen,
+                            uint64_t gas_gen, int32_t n_pods, int32_t n_rules,
+                            const pas_rule* d_rules, const int32_t* d_rule_off,
+                            const pas_rule* d_prio, const uint64_t* d_cand,
+                            int32_t max_containers, int32_t i915_index, const int64_t* d_req,
+                            const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                            int32_t k, int32_t node_base, int64_t* d_top_key,
+                            uint32_t* d_top_sub, int32_t* d_top_node, int32_t* d_top_len,
+                            void* hip_stream) {
   if (!ctx) return PAS_EINVAL;
-  int rc = check_tas_gen(ctx, gen);
+  int rc = check_tas_gen(ctx, tas_gen);
   if (rc) return rc;
-  if (n_pods < 0 || n_rules < 0 || k < 1 || node_base < 0)
-    return set_error(ctx, PAS_EINVAL, "pas_tas_topk_device: bad shape");
-  if ((rc = check_no_wide(ctx, "pas_tas_topk_device"))) return rc;
+  if ((rc = check_gas_gen(ctx, gas_gen))) return rc;
+  if (ctx->gas.n_nodes != ctx->tas.n_nodes)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": TAS and GAS snapshots differ in node count");
+  if (n_pods < 0 || n_rules < 0 || k < 1 || node_base < 0 || max_containers < 0 ||
+      i915_index >= ctx->gas.n_res || i915_index < -1)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  if (!wide && (rc = check_no_wide(ctx, fn))) return rc;
   if ((int64_t)node_base + ctx->tas.n_nodes > INT32_MAX)
-    return set_error(ctx, PAS_EINVAL, "pas_tas_topk_device: node ids past int32");
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": node ids past int32");
   if (n_pods == 0) return PAS_OK;
   if (!d_rule_off || !d_prio || (n_rules > 0 && !d_rules) || !d_top_key || !d_top_node ||
-      !d_top_len)
-    return set_error(ctx, PAS_EINVAL, "pas_tas_topk_device: null argument");
+      !d_top_len || !d_n_containers || (max_containers > 0 && (!d_req || !d_req_mask)) ||
+      (wide && !d_top_sub))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
   if ((rc = activate(ctx))) return rc;
-  return tas_topk_launch(ctx, n_pods, n_rules, d_rules, d_rule_off, d_prio, d_cand, k,
-                         node_base, d_top_key, d_top_node, d_top_len,
-                         pick_stream(ctx, hip_stream));
+  return tas_gas_topk_launch(ctx, n_pods, n_rules, d_rules, d_rule_off, d_prio, d_cand,
+                             max_containers, i915_index, d_req, d_req_mask, d_n_containers, k,
+                             node_base, d_top_key, wide ? d_top_sub : nullptr, d_top_node,
+                             d_top_len, pick_stream(ctx, hip_stream));
 }
 
 int pas_tas_gas_topk_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, int32_t n_pods,
@@ -1369,58 +1423,88 @@ int pas_tas_gas_topk_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, in
                             const uint32_t* d_req_mask, const int32_t* d_n_containers,
                             int32_t k, int32_t node_base, int64_t* d_top_key,
                             int32_t* d_top_node, int32_t* d_top_len, void* hip_stream) {
+  return tas_gas_topk_api(ctx, "pas_tas_gas_topk_device", false, tas_gen, gas_gen, n_pods,
+                          n_rules, d_rules, d_rule_off, d_prio, d_cand, max_containers,
+                          i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
+                          d_top_key, nullptr, d_top_node, d_top_len, hip_stream);
+}
+
+int pas_tas_gas_topk_wide_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                 int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+                                 const int32_t* d_rule_off, const pas_rule* d_prio,
+                                 const uint64_t* d_cand, int32_t max_containers,
+                                 int32_t i915_index, const int64_t* d_req,
+                                 const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                 int32_t k, int32_t node_base, int64_t* d_top_key,
+                                 uint32_t* d_top_sub, int32_t* d_top_node, int32_t* d_top_len,
+                                 void* hip_stream) {
+  return tas_gas_topk_api(ctx, "pas_tas_gas_topk_wide_device", true, tas_gen, gas_gen, n_pods,
+                          n_rules, d_rules, d_rule_off, d_prio, d_cand, max_containers,
+                          i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
+                          d_top_key, d_top_sub, d_top_node, d_top_len, hip_stream);
+}
+
+static int topk_merge_api(pas_ctx* ctx, const char* fn, bool wide, int32_t n_pods, int32_t k,
+                          int32_t n_shards, const int64_t* d_keys, const uint32_t* d_subs,
+                          const int32_t* d_nodes, int32_t* d_out_node, int32_t* d_out_len,
+                          void* hip_stream) {
   if (!ctx) return PAS_EINVAL;
-  int rc = check_tas_gen(ctx, tas_gen);
-  if (rc) return rc;
-  if ((rc = check_gas_gen(ctx, gas_gen))) return rc;
-  if (ctx->gas.n_nodes != ctx->tas.n_nodes)
-    return set_error(ctx, PAS_EINVAL, "pas_tas_gas_topk_device: TAS and GAS snapshots differ "
-                                      "in node count");
-  if (n_pods < 0 || n_rules < 0 || k < 1 || node_base < 0 || max_containers < 0 ||
-      i915_index >= ctx->gas.n_res || i915_index < -1)
-    return set_error(ctx, PAS_EINVAL, "pas_tas_gas_topk_device: bad shape");
-  if ((rc = check_no_wide(ctx, "pas_tas_gas_topk_device"))) return rc;
-  if ((int64_t)node_base + ctx->tas.n_nodes > INT32_MAX)
-    return set_error(ctx, PAS_EINVAL, "pas_tas_gas_topk_device: node ids past int32");
+  if (n_pods < 0 || k < 1 || n_shards < 1) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
   if (n_pods == 0) return PAS_OK;
-  if (!d_rule_off || !d_prio || (n_rules > 0 && !d_rules) || !d_top_key || !d_top_node ||
-      !d_top_len || !d_n_containers || (max_containers > 0 && (!d_req || !d_req_mask)))
-    return set_error(ctx, PAS_EINVAL, "pas_tas_gas_topk_device: null argument");
-  if ((rc = activate(ctx))) return rc;
-  return tas_gas_topk_launch(ctx, n_pods, n_rules, d_rules, d_rule_off, d_prio, d_cand, max_containers,
-                             i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
-                             d_top_key, d_top_node, d_top_len, pick_stream(ctx, hip_stream));
+  if (!d_keys || !d_nodes || !d_out_node || !d_out_len || (wide && !d_subs))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
+  int rc = activate(ctx);
+  if (rc) return rc;
+  return topk_merge_launch(ctx, n_pods, k, n_shards, d_keys, wide ? d_subs : nullptr, d_nodes,
+                           d_out_node, d_out_len, pick_stream(ctx, hip_stream));
 }
 
 int pas_topk_merge_device(pas_ctx* ctx, int32_t n_pods, int32_t k, int32_t n_shards,
                           const int64_t* d_keys, const int32_t* d_nodes, int32_t* d_out_node,
                           int32_t* d_out_len, void* hip_stream) {
+  return topk_merge_api(ctx, "pas_topk_merge_device", false, n_pods, k, n_shards, d_keys,
+                        nullptr, d_nodes, d_out_node, d_out_len, hip_stream);
+}
+
+int pas_topk_merge_wide_device(pas_ctx* ctx, int32_t n_pods, int32_t k, int32_t n_shards,
+                               const int64_t* d_keys, const uint32_t* d_subs,
+                               const int32_t* d_nodes, int32_t* d_out_node, int32_t* d_out_len,
+                               void* hip_stream) {
+  return topk_merge_api(ctx, "pas_topk_merge_wide_device", true, n_pods, k, n_shards, d_keys,
+                        d_subs, d_nodes, d_out_node, d_out_len, hip_stream);
+}
+
+static int list_merge_api(pas_ctx* ctx, const char* fn, bool wide, int32_t n_pods,
+                          int32_t n_shards, int32_t width, const int64_t* d_keys,
+                          const uint32_t* d_subs, const int32_t* d_nodes, int32_t* d_out_node,
+                          int64_t out_ld, int32_t* d_out_len, void* hip_stream) {
   if (!ctx) return PAS_EINVAL;
-  if (n_pods < 0 || k < 1 || n_shards < 1)
-    return set_error(ctx, PAS_EINVAL, "pas_topk_merge_device: bad shape");
+  if (n_pods < 0 || n_shards < 1 || n_shards > 4096 || width < 1 ||
+      out_ld < (int64_t)n_shards * width || (int64_t)n_shards * width > INT32_MAX)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
   if (n_pods == 0) return PAS_OK;
-  if (!d_keys || !d_nodes || !d_out_node || !d_out_len)
-    return set_error(ctx, PAS_EINVAL, "pas_topk_merge_device: null argument");
+  if (!d_keys || !d_nodes || !d_out_node || !d_out_len || (wide && !d_subs))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
   int rc = activate(ctx);
   if (rc) return rc;
-  return topk_merge_launch(ctx, n_pods, k, n_shards, d_keys, d_nodes, d_out_node, d_out_len,
+  return list_merge_launch(ctx, n_pods, n_shards, width, d_keys, wide ? d_subs : nullptr,
+                           d_nodes, d_out_node, out_ld, d_out_len,
                            pick_stream(ctx, hip_stream));
 }
 
 int pas_list_merge_device(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
                           const int64_t* d_keys, const int32_t* d_nodes, int32_t* d_out_node,
                           int64_t out_ld, int32_t* d_out_len, void* hip_stream) {
-  if (!ctx) return PAS_EINVAL;
-  if (n_pods < 0 || n_shards < 1 || n_shards > 4096 || width < 1 ||
-      out_ld < (int64_t)n_shards * width || (int64_t)n_shards * width > INT32_MAX)
-    return set_error(ctx, PAS_EINVAL, "pas_list_merge_device: bad shape");
-  if (n_pods == 0) return PAS_OK;
-  if (!d_keys || !d_nodes || !d_out_node || !d_out_len)
-    return set_error(ctx, PAS_EINVAL, "pas_list_merge_device: null argument");
-  int rc = activate(ctx);
-  if (rc) return rc;
-  return list_merge_launch(ctx, n_pods, n_shards, width, d_keys, d_nodes, d_out_node, out_ld,
-                           d_out_len, pick_stream(ctx, hip_stream));
+  return list_merge_api(ctx, "pas_list_merge_device", false, n_pods, n_shards, width, d_keys,
+                        nullptr, d_nodes, d_out_node, out_ld, d_out_len, hip_stream);
+}
+
+int pas_list_merge_wide_device(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
+                               const int64_t* d_keys, const uint32_t* d_subs,
+                               const int32_t* d_nodes, int32_t* d_out_node, int64_t out_ld,
+                               int32_t* d_out_len, void* hip_stream) {
+  return list_merge_api(ctx, "pas_list_merge_wide_device", true, n_pods, n_shards, width,
+                        d_keys, d_subs, d_nodes, d_out_node, out_ld, d_out_len, hip_stream);
 }
 
 // --------------------------------------------------------------------------- timing

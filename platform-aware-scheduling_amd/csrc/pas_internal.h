@@ -141,6 +141,28 @@ __device__ __forceinline__ bool pair_not_above(int64_t whole, uint32_t nano, int
   return whole < v || (whole == v && nano <= f);
 }
 
+// The canonical pair (W, F) of a narrow column's value v held at multiplier mult = 10^s,
+// s = 0..9 (scale_tab[2m]): v * 10^-s = W + F * 1e-9 with W the floor (toward -inf) and
+// 0 <= F < 1e9, the unit of the wide merge records (pas.h).  Exact: the remainder is below
+// 10^9 and 10^(9-s) scales it below 10^9.
+__host__ __device__ __forceinline__ void canonical_pair(int64_t v, int64_t mult, int64_t* W,
+                                                        uint32_t* F) {
+  int64_t q = v / mult, r = v - q * mult;
+  if (r < 0) {
+    q -= 1;
+    r += mult;
+  }
+  *W = q;
+  *F = (uint32_t)r * (1000000000u / (uint32_t)mult);
+}
+// The wide merge record (key, sub) of the pair under the prioritize operator: ascending
+// (key signed, sub unsigned) is the HostPriorityList order (~ reverses both fields).
+__host__ __device__ __forceinline__ void wide_order_key(int32_t op, int64_t W, uint32_t F,
+                                                        int64_t* key, uint32_t* sub) {
+  *key = op == PAS_OP_GREATER_THAN ? ~W : op == PAS_OP_LESS_THAN ? W : 0;
+  *sub = op == PAS_OP_GREATER_THAN ? ~F : op == PAS_OP_LESS_THAN ? F : 0u;
+}
+
 struct GasSnapshot {
   bool valid = false;
   uint64_t gen = 0;
@@ -339,10 +361,12 @@ int gas_fit_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t
                    const int32_t* d_n_containers, uint32_t* d_res, int64_t ld_res,
                    uint64_t* d_fit, pas_gas_selection* d_side, int64_t side_cap,
                    int64_t* d_side_count, hipStream_t s);
+// (d_sub / d_subs of the top-k and merge launches: the wide records' third array, pas.h;
+// null = the 64-bit records)
 int tas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
                     const int32_t* d_rule_off, const pas_rule* d_prio, const uint64_t* d_cand,
-                    int32_t k, int32_t node_base, int64_t* d_key, int32_t* d_node,
-                    int32_t* d_len, hipStream_t s);
+                    int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
+                    int32_t* d_node, int32_t* d_len, hipStream_t s);
 // The eval prep's grouping alone: pods bucketed by prioritize order row (metric x asc / desc
 // / index), desc[2 pos] = {pod, order * M + metric or -1, present count, 0},
 // desc[2 pos + 1] = {rule_off[pod], rule_off[pod + 1], 0, 0}; keys [P] scratch.  With
@@ -356,13 +380,14 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
                         const uint64_t* d_cand, int32_t max_containers, int32_t i915_index,
                         const int64_t* d_req, const uint32_t* d_req_mask,
                         const int32_t* d_n_containers, int32_t k, int32_t node_base,
-                        int64_t* d_key, int32_t* d_node, int32_t* d_len, hipStream_t s);
+                        int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
+                        hipStream_t s);
 int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
-                      const int64_t* d_keys, const int32_t* d_nodes, int32_t* d_out_node,
-                      int64_t out_ld, int32_t* d_out_len, hipStream_t s);
+                      const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
+                      int32_t* d_out_node, int64_t out_ld, int32_t* d_out_len, hipStream_t s);
 int topk_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t k, int32_t n_shards,
-                      const int64_t* d_keys, const int32_t* d_nodes, int32_t* d_out_node,
-                      int32_t* d_out_len, hipStream_t s);
+                      const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
+                      int32_t* d_out_node, int32_t* d_out_len, hipStream_t s);
 // Bind (fit + commit, release = false) or release of operations grouped by node: order =
 // operation indices sorted by node (stable), seg_off [n_seg + 1] the node segments.
 int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_seg, int32_t max_containers,

@@ -25,7 +25,9 @@
 // as value ranges (LazyRule) and read back per round as broadcast LDS reads.
 //
 // Records: key = order key of the node's value under the pod's operator (tas_topk.hip),
-// node = global id (local + node_base); past len: key INT64_MAX, node INT32_MAX.
+// node = global id (local + node_base); past len: key INT64_MAX, node INT32_MAX.  The kWide
+// instantiations (pas_tas_gas_topk_wide_device) write the wide records (key, sub, node) of
+// pas.h instead and evaluate rules and jumps on wide columns exactly.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -69,6 +71,14 @@ struct LazyTopkParams {
   int64_t* key_out;       // [P][k]
   int32_t* node_out;      // [P][k]
   int32_t* len_out;       // [P]
+  // the wide records (kWide instantiations only): sub_out [P][k]; the wide columns' nanos
+  // [M][N] and flags [M], both null while the snapshot holds no wide column
+  uint32_t* sub_out;
+  const uint32_t* nano;
+  const uint8_t* wide_flag;
+  const uint32_t* sorted_nano;  // [M][R] and fences [M][R/1024], [M][R/32] (the jumps' search)
+  const uint32_t* f1k_nano;
+  const uint32_t* f32_nano;
 };
 
 
@@ -174,18 +184,37 @@ __device__ bool lane_fit(const LazyTopkParams& a, int32_t p, int32_t n) {
 // Positions [lb, ub) of value t (milli) in metric m's ascending column (c present values),
 // found by the pod's 32 lanes in three rounds of loads, as the eval prep's range search does
 // (tas_eval.hip ranges_group): the 1024-stride fences, the 32-stride fences of one block, the
-// 32 values of one 32-block.  lb = values < t, ub = values <= t.
+// 32 values of one 32-block.  lb = values < t, ub = values <= t.  kWide with wcol (the column
+// is wide): the floors come with their nanos (sorted_nano and its fences) and ub counts the
+// pairs <= (t, 0), i.e. lb plus the nodes of whole == t with nano == 0; lb needs no nano.
+template <bool kWide>
 __device__ void half_bounds(const LazyTopkParams& a, int32_t m, int32_t c, int64_t t, int sub,
-                            uint64_t half_mask, int32_t* lb, int32_t* ub) {
+                            uint64_t half_mask, bool wcol, int32_t* lb, int32_t* ub) {
   const int64_t* sv = a.sorted + (int64_t)m * a.R;
   const int64_t* f1 = a.f1k + (int64_t)m * (a.R >> 10);
   const int64_t* f2 = a.f32 + (int64_t)m * (a.R >> 5);
+  // value (v, nano f) <= t: the narrow compare when f is 0
+  auto not_above = [&](int64_t v, uint32_t f) { return v < t || (v == t && f == 0u); };
   const int32_t na = (c + 1023) >> 10, nb = (c + 31) >> 5;
   int32_t cl = 0, cu = 0;
   for (int32_t i0 = 0; i0 < na; i0 += 8 * 32) {
     int64_t v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) v[u] = f1[min(i0 + u * 32 + sub, max(na - 1, 0))];
+    if constexpr (kWide) {
+      uint32_t g[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        g[u] = wcol ? a.f1k_nano[(int64_t)m * (a.R >> 10) + min(i0 + u * 32 + sub, max(na - 1, 0))]
+                    : 0u;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool in = i0 + u * 32 + sub < na;
+        cl += in && v[u] < t;
+        cu += in && not_above(v[u], g[u]);
+      }
+      continue;
+    }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const bool in = i0 + u * 32 + sub < na;
@@ -203,14 +232,22 @@ __device__ void half_bounds(const LazyTopkParams& a, int32_t m, int32_t c, int64
   const int32_t e2l = n1l ? min(32, nb - b1l * 32) : 0, e2u = n1u ? min(32, nb - b1u * 32) : 0;
   const int64_t x2l = f2[b1l * 32 + min(sub, max(e2l - 1, 0))];
   const int64_t x2u = f2[b1u * 32 + min(sub, max(e2u - 1, 0))];
+  uint32_t g2u = 0;
+  if constexpr (kWide)
+    if (wcol) g2u = a.f32_nano[(int64_t)m * (a.R >> 5) + b1u * 32 + min(sub, max(e2u - 1, 0))];
   const int32_t n2l = __popcll(__ballot(sub < e2l && x2l < t) & half_mask);
-  const int32_t n2u = __popcll(__ballot(sub < e2u && x2u <= t) & half_mask);
+  const int32_t n2u = __popcll(
+      __ballot(sub < e2u && (kWide ? not_above(x2u, g2u) : x2u <= t)) & half_mask);
   const int32_t b2l = b1l * 32 + max(n2l - 1, 0), b2u = b1u * 32 + max(n2u - 1, 0);
   const int32_t e3l = n1l ? min(32, c - b2l * 32) : 0, e3u = n1u ? min(32, c - b2u * 32) : 0;
   const int64_t x3l = sv[b2l * 32 + min(sub, max(e3l - 1, 0))];
   const int64_t x3u = sv[b2u * 32 + min(sub, max(e3u - 1, 0))];
+  uint32_t g3u = 0;
+  if constexpr (kWide)
+    if (wcol) g3u = a.sorted_nano[(int64_t)m * a.R + b2u * 32 + min(sub, max(e3u - 1, 0))];
   const int32_t n3l = __popcll(__ballot(sub < e3l && x3l < t) & half_mask);
-  const int32_t n3u = __popcll(__ballot(sub < e3u && x3u <= t) & half_mask);
+  const int32_t n3u = __popcll(
+      __ballot(sub < e3u && (kWide ? not_above(x3u, g3u) : x3u <= t)) & half_mask);
   *lb = n1l ? b2l * 32 + n3l : 0;
   *ub = n1u ? b2u * 32 + n3u : 0;
 }
@@ -255,16 +292,61 @@ __device__ __forceinline__ void compile_rule(const pas_rule& ru, int32_t M,
   out->span = (uint64_t)hi - (uint64_t)lo;
 }
 
+// The same for the wide instantiations, where the rule's column may be wide (pas_internal.h
+// wide_below / wide_equal / wide_above: the target as it is, no scale, no saturation).  The
+// nano of a node matters only where whole == target, so the rule stays the range test on the
+// floor plus a condition on the range's edge value whole == t: LessThan t -> [MIN, t - 1] (no
+// edge); GreaterThan t -> [t, MAX], the edge hits only with nano != 0; Equals t -> [t, t], the
+// edge hits only with nano == 0.  The nano is loaded only by a lane whose floor is the edge.
+constexpr int32_t kEdgeNone = 0, kEdgeNanoNonZero = 1, kEdgeNanoZero = 2;
+__device__ __forceinline__ void compile_rule_wide(const pas_rule& ru, int32_t M,
+                                                  const int64_t* __restrict__ scale_tab,
+                                                  const uint8_t* __restrict__ wide_flag,
+                                                  int32_t* metric, LazyRule* out, int64_t* edge,
+                                                  int32_t* mode) {
+  *edge = 0;
+  *mode = kEdgeNone;
+  if (!(wide_flag && ru.metric >= 0 && ru.metric < M && wide_flag[ru.metric])) {
+    compile_rule(ru, M, scale_tab, metric, out);
+    return;
+  }
+  const int64_t t = ru.target;
+  int64_t lo = 0, hi = -1;  // empty
+  if (ru.op == PAS_OP_LESS_THAN) {
+    if (t > INT64_MIN) lo = INT64_MIN, hi = t - 1;
+  } else if (ru.op == PAS_OP_GREATER_THAN) {
+    lo = t, hi = INT64_MAX;
+    *mode = kEdgeNanoNonZero;
+  } else if (ru.op == PAS_OP_EQUALS) {
+    lo = hi = t;
+    *mode = kEdgeNanoZero;
+  }
+  *edge = t;
+  *metric = lo <= hi ? ru.metric : -1;
+  out->lo = lo;
+  out->span = (uint64_t)hi - (uint64_t)lo;
+}
+
 // (at least 4 waves per SIMD for the register-resident shapes: the gathers need waves in
 // flight)
-template <int KMAX, int QW>
-constexpr int topk_waves() { return KMAX <= 8 && QW <= 3 ? 4 : 1; }
-template <int KMAX, int QW>
-__global__ __launch_bounds__(kTpb) __attribute__((amdgpu_waves_per_eu(topk_waves<KMAX, QW>())))
+// The wide instantiations of those shapes need about 12 more registers at the fit's peak
+// (the wide columns' pointers and the edge test stay live beside the card state) and spill
+// 12 - 52 bytes per lane under the 128-register cap of 4 waves, so they ask for 3 waves (168
+// registers, no scratch): the narrow instantiations keep 4.
+template <int KMAX, int QW, bool kWide>
+constexpr int topk_waves() { return KMAX <= 8 && QW <= 3 ? (kWide ? 3 : 4) : 1; }
+// kWide: the wide records (key, sub, node) in the canonical unit (pas.h), rules and jumps on
+// wide columns; the narrow instantiations (kWide = false) hold none of that code.
+template <int KMAX, int QW, bool kWide>
+__global__ __launch_bounds__(kTpb)
+__attribute__((amdgpu_waves_per_eu(topk_waves<KMAX, QW, kWide>())))
 void tas_gas_topk_kernel(LazyTopkParams a) {
   // the pods' compiled rules, kStageRules per pod (pods of at most that many rules)
   __shared__ LazyRule srule[kPodsPerBlock][kStageRules];
   __shared__ int32_t smetric[kPodsPerBlock][kStageRules];
+  // (kWide) the rules' edge value and mode (compile_rule_wide)
+  __shared__ int64_t sedge[kWide ? kPodsPerBlock : 1][kWide ? kStageRules : 1];
+  __shared__ int32_t smode[kWide ? kPodsPerBlock : 1][kWide ? kStageRules : 1];
   const int lane = threadIdx.x & 63;
   const int half = lane / kPodLanes, sub = lane % kPodLanes;
   // XCD-aware: blocks b and b + 8 share an XCD; each XCD takes a contiguous run of the
@@ -312,6 +394,11 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
   for (int i = 0; i < kSkip; ++i) slo[i] = shi[i] = 0;
   const int ord = d0.y >= 0 ? d0.y / a.M : kOrderIndex;
   const bool sorted_row = c0 > 0 && ord != kOrderIndex;
+  // (kWide) the prioritize column is wide: the jumps below.  (The records read the flag and
+  // the column's multiplier again where they are written: nothing more stays live across
+  // the fit, whose card state fills the registers of the 4-waves shapes.)
+  bool pwide = false;
+  if constexpr (kWide) pwide = c0 > 0 && a.wide_flag && a.wide_flag[pr.metric];
   // The pod's rules are loaded one per lane (32 at a time, a single round trip) and only the
   // ones on the prioritize metric are walked, one per half at a time (a rule by rule scan
   // waited for a load per rule).
@@ -331,9 +418,16 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
     ru.target = __shfl(ru_l.target, src, 64);
     const bool same = (sm >> src) & 1ull;
     int64_t tm = 0;
-    const int sat = target_scaled(ru.target, a.scale_tab, same ? pr.metric : 0, &tm);
+    int sat = target_scaled(ru.target, a.scale_tab, same ? pr.metric : 0, &tm);
+    // A wide prioritize column: the target as it is against the pairs, lb = #(whole < t),
+    // ub = #(pair <= (t, 0)).  The ranges below are then exact for a wide column too: [0, lb)
+    // violates LessThan t, [ub, c) GreaterThan t (the nodes of whole == t with nano != 0
+    // included), [lb, ub) Equals t (whole == t with nano == 0).
+    if constexpr (kWide)
+      if (pwide) tm = ru.target, sat = 0;
     int32_t lb = 0, ub = 0;
-    half_bounds(a, same ? pr.metric : 0, same ? c0 : 0, tm, sub, half_mask, &lb, &ub);
+    half_bounds<kWide>(a, same ? pr.metric : 0, same ? c0 : 0, tm, sub, half_mask, pwide, &lb,
+                       &ub);
     if (sat != 0) lb = ub = sat > 0 ? c0 : 0;
     if (same) {
       // the rule's nodes in ascending positions, mirrored for the descending row
@@ -361,7 +455,17 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
   if (staged) {
     LazyRule cr{0, 0};
     int32_t cm = -1;
-    if (have && r0 + sub < r1) compile_rule(a.rules[r0 + sub], a.M, a.scale_tab, &cm, &cr);
+    if constexpr (kWide) {
+      int64_t ce = 0;
+      int32_t cmode = kEdgeNone;
+      if (have && r0 + sub < r1)
+        compile_rule_wide(a.rules[r0 + sub], a.M, a.scale_tab, a.wide_flag, &cm, &cr, &ce,
+                          &cmode);
+      sedge[pslot][sub] = ce;
+      smode[pslot][sub] = cmode;
+    } else {
+      if (have && r0 + sub < r1) compile_rule(a.rules[r0 + sub], a.M, a.scale_tab, &cm, &cr);
+    }
     srule[pslot][sub] = cr;
     smetric[pslot][sub] = cm;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
@@ -411,9 +515,18 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
 #pragma unroll
         for (int u = 0; u < kRuleBatch; ++u) {
           const LazyRule cr = srule[pslot][min(rb + u, kStageRules - 1)];
-          const bool hit = rb + u < nr && m[u] >= 0 &&
-                           (uint64_t)v[u] - (uint64_t)cr.lo <= cr.span &&
-                           ((pw[u] >> (m[u] & 63)) & 1ull);
+          bool hit = rb + u < nr && m[u] >= 0 &&
+                     (uint64_t)v[u] - (uint64_t)cr.lo <= cr.span &&
+                     ((pw[u] >> (m[u] & 63)) & 1ull);
+          if constexpr (kWide) {
+            // the range's edge on a wide column: the node's nano decides (a rare gather of
+            // the metric-major nano column, by the lanes on the edge only)
+            const int32_t md = smode[pslot][min(rb + u, kStageRules - 1)];
+            if (hit && md != kEdgeNone && v[u] == sedge[pslot][min(rb + u, kStageRules - 1)]) {
+              const uint32_t f = a.nano[(int64_t)m[u] * a.N + n];
+              hit = (f != 0u) == (md == kEdgeNanoNonZero);
+            }
+          }
           viol = viol || hit;
         }
       }
@@ -435,6 +548,19 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
         const pas_rule rule = ru[u];
         if (rb + u >= r1 || rule.metric < 0 || rule.metric >= a.M || rule.op < 0 || rule.op > 2)
           continue;
+        if constexpr (kWide) {
+          if (a.wide_flag && a.wide_flag[rule.metric]) {
+            const int64_t t = rule.target;
+            uint32_t f = 0;
+            if (v[u] == t && rule.op != PAS_OP_LESS_THAN)
+              f = a.nano[(int64_t)rule.metric * a.N + n];
+            const bool wh = rule.op == PAS_OP_LESS_THAN      ? wide_below(v[u], f, t)
+                            : rule.op == PAS_OP_GREATER_THAN ? wide_above(v[u], f, t)
+                                                             : wide_equal(v[u], f, t);
+            viol = viol || (wh && ((pw[u] >> (rule.metric & 63)) & 1ull));
+            continue;
+          }
+        }
         int64_t tm = 0;
         const int sat = target_scaled(rule.target, a.scale_tab, rule.metric, &tm);
         bool hit;
@@ -451,7 +577,17 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
       const int32_t rank = kept + __popcll(keep & below);
       if (rank < k) {
         nodes[rank] = n + a.node_base;
-        keys[rank] = order_key(pr.op, mcol[n]);
+        if constexpr (kWide) {
+          // the canonical pair of the node's value (one 64-bit division per kept record of a
+          // narrow column, none per node walked)
+          int64_t W = mcol[n];
+          uint32_t F = 0;
+          if (a.wide_flag && a.wide_flag[pr.metric]) F = a.nano[(int64_t)pr.metric * a.N + n];
+          else canonical_pair(W, a.scale_tab[2 * pr.metric], &W, &F);
+          wide_order_key(pr.op, W, F, &keys[rank], &a.sub_out[(int64_t)p * k + rank]);
+        } else {
+          keys[rank] = order_key(pr.op, mcol[n]);
+        }
       }
     }
     kept += active ? __popcll(keep) : 0;
@@ -460,6 +596,7 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
   const int32_t len = min(kept, k);
   for (int32_t i = len + sub; i < k; i += kPodLanes) {
     keys[i] = INT64_MAX;
+    if constexpr (kWide) a.sub_out[(int64_t)p * k + i] = UINT32_MAX;
     nodes[i] = INT32_MAX;
   }
   if (sub == 0) a.len_out[p] = len;
@@ -499,6 +636,22 @@ __global__ __launch_bounds__(kTpb) void transpose_present_kernel(
   }
 }
 
+template <bool kWide>
+void topk_dispatch(const LazyTopkParams& a, unsigned grid, hipStream_t s) {
+  if (a.K <= 8) {
+    switch (a.Q) {
+      case 1: tas_gas_topk_kernel<8, 1, kWide><<<grid, kTpb, 0, s>>>(a); break;
+      case 2: tas_gas_topk_kernel<8, 2, kWide><<<grid, kTpb, 0, s>>>(a); break;
+      case 3: tas_gas_topk_kernel<8, 3, kWide><<<grid, kTpb, 0, s>>>(a); break;
+      default: tas_gas_topk_kernel<8, kMaxRes, kWide><<<grid, kTpb, 0, s>>>(a); break;
+    }
+  } else if (a.K <= 16) {
+    tas_gas_topk_kernel<16, kMaxRes, kWide><<<grid, kTpb, 0, s>>>(a);
+  } else {
+    tas_gas_topk_kernel<PAS_GAS_MAX_CARDS, kMaxRes, kWide><<<grid, kTpb, 0, s>>>(a);
+  }
+}
+
 }  // namespace
 
 int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
@@ -506,7 +659,8 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
                         const uint64_t* d_cand, int32_t max_containers, int32_t i915_index,
                         const int64_t* d_req, const uint32_t* d_req_mask,
                         const int32_t* d_n_containers, int32_t k, int32_t node_base,
-                        int64_t* d_key, int32_t* d_node, int32_t* d_len, hipStream_t s) {
+                        int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
+                        hipStream_t s) {
   if (n_pods == 0) return PAS_OK;
   TasSnapshot& t = ctx->tas;
   const GasSnapshot& g = ctx->gas;
@@ -576,19 +730,15 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
   a.key_out = d_key;
   a.node_out = d_node;
   a.len_out = d_len;
+  a.sub_out = d_sub;
+  a.nano = t.n_wide > 0 ? t.nano : nullptr;
+  a.wide_flag = t.n_wide > 0 ? t.wide_flag : nullptr;
+  a.sorted_nano = t.sorted_nano;
+  a.f1k_nano = t.f1k_nano;
+  a.f32_nano = t.f32_nano;
   const unsigned grid = (unsigned)((n_pods + kPodsPerBlock - 1) / kPodsPerBlock);
-  if (a.K <= 8) {
-    switch (a.Q) {
-      case 1: tas_gas_topk_kernel<8, 1><<<grid, kTpb, 0, s>>>(a); break;
-      case 2: tas_gas_topk_kernel<8, 2><<<grid, kTpb, 0, s>>>(a); break;
-      case 3: tas_gas_topk_kernel<8, 3><<<grid, kTpb, 0, s>>>(a); break;
-      default: tas_gas_topk_kernel<8, kMaxRes><<<grid, kTpb, 0, s>>>(a); break;
-    }
-  } else if (a.K <= 16) {
-    tas_gas_topk_kernel<16, kMaxRes><<<grid, kTpb, 0, s>>>(a);
-  } else {
-    tas_gas_topk_kernel<PAS_GAS_MAX_CARDS, kMaxRes><<<grid, kTpb, 0, s>>>(a);
-  }
+  if (d_sub) topk_dispatch<true>(a, grid, s);
+  else topk_dispatch<false>(a, grid, s);
   timing_end(ctx, s, &tl);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;

@@ -29,51 +29,89 @@ constexpr int kTile = kTpb * kItems;
 constexpr int64_t kKeyNone = INT64_MAX;
 constexpr int32_t kNodeNone = INT32_MAX;
 
-__device__ __forceinline__ bool before(int64_t ka, int32_t na, int64_t kb, int32_t nb) {
-  return ka < kb || (ka == kb && na < nb);
+// A merge record: (key, node), or with kWide (key, sub, node) (pas.h: the wide records).
+template <bool kWide>
+struct Rec {
+  int64_t k;
+  int32_t n;
+};
+template <>
+struct Rec<true> {
+  int64_t k;
+  uint32_t s;
+  int32_t n;
+};
+
+__device__ __forceinline__ bool before(const Rec<false>& a, const Rec<false>& b) {
+  return a.k < b.k || (a.k == b.k && a.n < b.n);
+}
+__device__ __forceinline__ bool before(const Rec<true>& a, const Rec<true>& b) {
+  return a.k < b.k || (a.k == b.k && (a.s < b.s || (a.s == b.s && a.n < b.n)));
 }
 
 // A round's input: record i of run s of pod p at base + s * s_stride + p * p_stride + i; runs
 // s >= n_real are empty (every record a sentinel).
+template <bool kWide>
 struct Runs {
   const int64_t* key;
   const int32_t* node;
   int64_t s_stride, p_stride;
   int32_t n_real;
 };
+template <>
+struct Runs<true> {
+  const int64_t* key;
+  const int32_t* node;
+  int64_t s_stride, p_stride;
+  int32_t n_real;
+  const uint32_t* sub;
+};
 
+template <bool kWide>
 struct RunRef {
   const int64_t* key;
   const int32_t* node;
   bool real;
 };
+template <>
+struct RunRef<true> {
+  const int64_t* key;
+  const int32_t* node;
+  bool real;
+  const uint32_t* sub;
+};
 
-__device__ __forceinline__ RunRef run_ref(const Runs& in, int32_t p, int32_t s) {
+template <bool kWide>
+__device__ __forceinline__ RunRef<kWide> run_ref(const Runs<kWide>& in, int32_t p, int32_t s) {
   const int64_t off = (int64_t)s * in.s_stride + (int64_t)p * in.p_stride;
-  return {in.key + off, in.node + off, s < in.n_real};
+  if constexpr (kWide) return {in.key + off, in.node + off, s < in.n_real, in.sub + off};
+  else return {in.key + off, in.node + off, s < in.n_real};
 }
 
-__device__ __forceinline__ void load(const RunRef& r, int64_t i, int64_t* k, int32_t* n) {
+template <bool kWide>
+__device__ __forceinline__ Rec<kWide> load(const RunRef<kWide>& r, int64_t i) {
+  Rec<kWide> x;
   if (r.real) {
-    *k = r.key[i];
-    *n = r.node[i];
+    x.k = r.key[i];
+    if constexpr (kWide) x.s = r.sub[i];
+    x.n = r.node[i];
   } else {
-    *k = kKeyNone;
-    *n = kNodeNone;
+    x.k = kKeyNone;
+    if constexpr (kWide) x.s = UINT32_MAX;
+    x.n = kNodeNone;
   }
+  return x;
 }
 
 // Records of run A among the first d outputs of the stable merge of A and B (width w each;
 // A first on equal records): the merge path's cut on diagonal d.
-__device__ int64_t cut(const RunRef& a, const RunRef& b, int64_t w, int64_t d) {
+template <bool kWide>
+__device__ int64_t cut(const RunRef<kWide>& a, const RunRef<kWide>& b, int64_t w, int64_t d) {
   int64_t lo = d > w ? d - w : 0, hi = d < w ? d : w;
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;
-    int64_t ka, kb;
-    int32_t na, nb;
-    load(a, mid, &ka, &na);
-    load(b, d - mid - 1, &kb, &nb);
-    if (!before(kb, nb, ka, na)) lo = mid + 1;  // A[mid] precedes B[d - mid - 1]
+    const Rec<kWide> ra = load(a, mid), rb = load(b, d - mid - 1);
+    if (!before(rb, ra)) lo = mid + 1;  // A[mid] precedes B[d - mid - 1]
     else hi = mid;
   }
   return lo;
@@ -81,46 +119,56 @@ __device__ int64_t cut(const RunRef& a, const RunRef& b, int64_t w, int64_t d) {
 
 // The cuts of every tile boundary of a round, [P][n_pairs][tiles + 1], one thread each (the
 // dependent binary-search loads of all boundaries in flight at once, ahead of the merge).
-__global__ void cuts_kernel(Runs in, int64_t w, int32_t n_pairs, int32_t tiles, int64_t n_cuts,
-                            int64_t* __restrict__ cuts) {
+template <bool kWide>
+__global__ void cuts_kernel(Runs<kWide> in, int64_t w, int32_t n_pairs, int32_t tiles,
+                            int64_t n_cuts, int64_t* __restrict__ cuts) {
   const int64_t t = (int64_t)blockIdx.x * kTpb + threadIdx.x;
   if (t >= n_cuts) return;
   const int32_t e = (int32_t)(t % (tiles + 1));
   const int32_t m = (int32_t)((t / (tiles + 1)) % n_pairs);
   const int32_t p = (int32_t)(t / ((int64_t)(tiles + 1) * n_pairs));
-  const RunRef A = run_ref(in, p, 2 * m), B = run_ref(in, p, 2 * m + 1);
+  const RunRef<kWide> A = run_ref(in, p, 2 * m), B = run_ref(in, p, 2 * m + 1);
   cuts[t] = cut(A, B, w, min((int64_t)e * kTile, 2 * w));
 }
 
 // One round: pairs (2m, 2m + 1) of runs of width w -> run m of width 2w.  Blocks: (pod, pair,
-// tile) in x.  Output: out_key/out_node [P][...] with row pitch out_pitch, or (final round,
-// out_key null) the node ids only, sentinels as -1, positions < out_cols.
-__global__ __launch_bounds__(kTpb) void merge_round_kernel(Runs in, int64_t w, int32_t n_pairs,
-                                                           int32_t tiles,
+// tile) in x.  Output: out_key/out_node (and out_sub with kWide) [P][...] with row pitch
+// out_pitch, or (final round, out_key null) the node ids only, sentinels as -1, positions
+// < out_cols.
+template <bool kWide>
+__global__ __launch_bounds__(kTpb) void merge_round_kernel(Runs<kWide> in, int64_t w,
+                                                           int32_t n_pairs, int32_t tiles,
                                                            const int64_t* __restrict__ cuts,
                                                            int64_t* out_key, int32_t* out_node,
-                                                           int64_t out_pitch, int64_t out_cols) {
+                                                           int64_t out_pitch, int64_t out_cols,
+                                                           uint32_t* out_sub) {
   __shared__ int64_t sk[kTile];
+  __shared__ uint32_t ss[kWide ? kTile : 1];
   __shared__ int32_t sn[kTile];
   const int64_t b = blockIdx.x;
   const int32_t tile = (int32_t)(b % tiles);
   const int32_t m = (int32_t)((b / tiles) % n_pairs);
   const int32_t p = (int32_t)(b / ((int64_t)tiles * n_pairs));
-  const RunRef A = run_ref(in, p, 2 * m), B = run_ref(in, p, 2 * m + 1);
+  const RunRef<kWide> A = run_ref(in, p, 2 * m), B = run_ref(in, p, 2 * m + 1);
   const int64_t d0 = (int64_t)tile * kTile, d1 = min(d0 + kTile, 2 * w);
   const int64_t* bc = cuts + (b / tiles) * (tiles + 1) + tile;
   const int64_t a0 = bc[0], a1 = bc[1];
   const int64_t b0 = d0 - a0, b1 = d1 - a1;
   const int32_t na = (int32_t)(a1 - a0), nb = (int32_t)(b1 - b0);
   for (int32_t i = threadIdx.x; i < na + nb; i += kTpb) {
-    int64_t k;
-    int32_t n;
-    if (i < na) load(A, a0 + i, &k, &n);
-    else load(B, b0 + i - na, &k, &n);
-    sk[i] = k;
-    sn[i] = n;
+    const Rec<kWide> x = i < na ? load(A, a0 + i) : load(B, b0 + i - na);
+    sk[i] = x.k;
+    if constexpr (kWide) ss[i] = x.s;
+    sn[i] = x.n;
   }
   __syncthreads();
+  auto staged = [&](int32_t i) {
+    Rec<kWide> x;
+    x.k = sk[i];
+    if constexpr (kWide) x.s = ss[i];
+    x.n = sn[i];
+    return x;
+  };
   // this lane's outputs [t0, t0 + kItems) of the tile: its cut inside the staged pieces
   const int32_t t0 = threadIdx.x * kItems;
   const int32_t total = na + nb;
@@ -129,7 +177,7 @@ __global__ __launch_bounds__(kTpb) void merge_round_kernel(Runs in, int64_t w, i
   while (lo < hi) {
     const int32_t mid = (lo + hi) >> 1;
     const int32_t j = na + t0 - mid - 1;
-    if (!before(sk[j], sn[j], sk[mid], sn[mid])) lo = mid + 1;
+    if (!before(staged(j), staged(mid))) lo = mid + 1;
     else hi = mid;
   }
   int32_t i = lo, j = t0 - lo;
@@ -139,11 +187,12 @@ __global__ __launch_bounds__(kTpb) void merge_round_kernel(Runs in, int64_t w, i
 #pragma unroll
   for (int u = 0; u < kItems; ++u) {
     if (t0 + u >= total) break;
-    const bool take_a = i < na && (j >= nb || !before(sk[na + j], sn[na + j], sk[i], sn[i]));
+    const bool take_a = i < na && (j >= nb || !before(staged(na + j), staged(i)));
     const int32_t s = take_a ? i++ : na + j++;
     const int64_t o = o0 + u;
     if (rk) {
       rk[o] = sk[s];
+      if constexpr (kWide) out_sub[(int64_t)p * out_pitch + o] = ss[s];
       rn[o] = sn[s];
     } else if (o < out_cols) {  // final round: node ids, -1 past the list
       rn[o] = sn[s] != kNodeNone ? sn[s] : -1;
@@ -152,13 +201,14 @@ __global__ __launch_bounds__(kTpb) void merge_round_kernel(Runs in, int64_t w, i
 }
 
 // The list lengths: the number of real records, i.e. the sum of the shards' lengths.
-__global__ void list_len_kernel(int32_t n_pods, Runs in, int32_t n_runs, int64_t w,
+template <bool kWide>
+__global__ void list_len_kernel(int32_t n_pods, Runs<kWide> in, int32_t n_runs, int64_t w,
                                 int32_t* __restrict__ out_len) {
   const int32_t p = blockIdx.x * kTpb + threadIdx.x;
   if (p >= n_pods) return;
   int64_t total = 0;
   for (int32_t s = 0; s < n_runs; ++s) {
-    const RunRef r = run_ref(in, p, s);
+    const RunRef<kWide> r = run_ref(in, p, s);
     if (!r.real) continue;
     int64_t lo = 0, hi = w;  // first sentinel of the run (records are sorted, sentinels last)
     while (lo < hi) {
@@ -181,20 +231,19 @@ __global__ void single_run_kernel(int32_t n_pods, const int32_t* __restrict__ no
   out_node[p * out_pitch + i] = n != kNodeNone ? n : -1;
 }
 
-}  // namespace
-
-int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
-                      const int64_t* d_keys, const int32_t* d_nodes, int32_t* d_out_node,
-                      int64_t out_ld, int32_t* d_out_len, hipStream_t s) {
-  if (n_pods == 0) return PAS_OK;
+template <bool kWide>
+int list_merge_run(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
+                   const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
+                   int32_t* d_out_node, int64_t out_ld, int32_t* d_out_len, hipStream_t s) {
   int32_t rounds = 0;
   while ((1 << rounds) < n_shards) ++rounds;
   const int64_t sp = (int64_t)1 << rounds;  // runs after padding
   const int64_t row = sp * width;           // records per pod in the intermediate rows
   const int64_t cols = (int64_t)n_shards * width;
-  Runs in{d_keys, d_nodes, (int64_t)n_pods * width, width, n_shards};
-  list_len_kernel<<<(n_pods + kTpb - 1) / kTpb, kTpb, 0, s>>>(n_pods, in, n_shards, width,
-                                                             d_out_len);
+  Runs<kWide> in{d_keys, d_nodes, (int64_t)n_pods * width, width, n_shards};
+  if constexpr (kWide) in.sub = d_subs;
+  list_len_kernel<kWide><<<(n_pods + kTpb - 1) / kTpb, kTpb, 0, s>>>(n_pods, in, n_shards, width,
+                                                                    d_out_len);
   PAS_HIP(ctx, hipGetLastError());
   if (rounds == 0) {  // one shard: no merge, no scratch
     const int64_t n = (int64_t)n_pods * width;
@@ -204,18 +253,21 @@ int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t wi
     return PAS_OK;
   }
   // the tile cuts of a round, then ping-pong rows [P][sp * width] for the rounds before the
-  // last.  A round has n_pairs * (tiles + 1) <= sp * width / kTile + 2 * n_pairs cuts per pod.
+  // last (keys | nodes | with kWide subs, 4 more bytes per record).  A round has
+  // n_pairs * (tiles + 1) <= sp * width / kTile + 2 * n_pairs cuts per pod.
   int acq = PAS_OK;
   SlotScope sc(ctx, s, 0, &acq);
   if (!sc.slot) return acq;
   int64_t* key_buf[2] = {nullptr, nullptr};
   int32_t* node_buf[2] = {nullptr, nullptr};
+  uint32_t* sub_buf[2] = {nullptr, nullptr};
   const int64_t max_cuts = (int64_t)n_pods * ((row + kTile - 1) / kTile + 2 * sp + 2);
   int64_t* cut_buf = nullptr;
   {
     const size_t half = rounds > 1 ? (size_t)n_pods * row : 0;
-    const size_t need =
-        2 * half * (sizeof(int64_t) + sizeof(int32_t)) + sizeof(int64_t) * (size_t)max_cuts;
+    const size_t need = 2 * half * (sizeof(int64_t) + sizeof(int32_t) +
+                                    (kWide ? sizeof(uint32_t) : 0)) +
+                        sizeof(int64_t) * (size_t)max_cuts;
     // the stream's slot buffer: merges on other streams may run beside this one
     int rc = PAS_OK;
     char* base = static_cast<char*>(slot_buf(ctx, sc.slot, kBufMerge, need, s, &rc));
@@ -225,15 +277,17 @@ int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t wi
     key_buf[1] = key_buf[0] + half;
     node_buf[0] = reinterpret_cast<int32_t*>(key_buf[1] + half);
     node_buf[1] = node_buf[0] + half;
+    sub_buf[0] = reinterpret_cast<uint32_t*>(node_buf[1] + half);
+    sub_buf[1] = sub_buf[0] + half;
   }
-  auto round = [&](const Runs& rin, int64_t w, int32_t n_pairs, int64_t* ok, int32_t* on,
-                   int64_t pitch) -> int {
+  auto round = [&](const Runs<kWide>& rin, int64_t w, int32_t n_pairs, int64_t* ok,
+                   uint32_t* os, int32_t* on, int64_t pitch) -> int {
     const int32_t tiles = (int32_t)((2 * w + kTile - 1) / kTile);
     const int64_t n_cuts = (int64_t)n_pods * n_pairs * (tiles + 1);
-    cuts_kernel<<<(unsigned)((n_cuts + kTpb - 1) / kTpb), kTpb, 0, s>>>(rin, w, n_pairs, tiles,
-                                                                       n_cuts, cut_buf);
-    merge_round_kernel<<<(unsigned)((int64_t)n_pods * n_pairs * tiles), kTpb, 0, s>>>(
-        rin, w, n_pairs, tiles, cut_buf, ok, on, pitch, cols);
+    cuts_kernel<kWide><<<(unsigned)((n_cuts + kTpb - 1) / kTpb), kTpb, 0, s>>>(
+        rin, w, n_pairs, tiles, n_cuts, cut_buf);
+    merge_round_kernel<kWide><<<(unsigned)((int64_t)n_pods * n_pairs * tiles), kTpb, 0, s>>>(
+        rin, w, n_pairs, tiles, cut_buf, ok, on, pitch, cols, os);
     PAS_HIP(ctx, hipGetLastError());
     return PAS_OK;
   };
@@ -242,12 +296,26 @@ int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t wi
     const int32_t n_pairs = (int32_t)(sp >> (r + 1));
     const bool last = r == rounds - 1;
     if (int rc = round(in, w, n_pairs, last ? nullptr : key_buf[r & 1],
-                       last ? d_out_node : node_buf[r & 1], last ? out_ld : row))
+                       last ? nullptr : sub_buf[r & 1], last ? d_out_node : node_buf[r & 1],
+                       last ? out_ld : row))
       return rc;
     // the next round reads this round's rows: run i of width 2w at row offset i * 2w
-    in = Runs{key_buf[r & 1], node_buf[r & 1], 2 * w, row, (int32_t)(sp >> (r + 1))};
+    in = Runs<kWide>{key_buf[r & 1], node_buf[r & 1], 2 * w, row, (int32_t)(sp >> (r + 1))};
+    if constexpr (kWide) in.sub = sub_buf[r & 1];
   }
   return PAS_OK;
+}
+
+}  // namespace
+
+int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
+                      const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
+                      int32_t* d_out_node, int64_t out_ld, int32_t* d_out_len, hipStream_t s) {
+  if (n_pods == 0) return PAS_OK;
+  return d_subs ? list_merge_run<true>(ctx, n_pods, n_shards, width, d_keys, d_subs, d_nodes,
+                                       d_out_node, out_ld, d_out_len, s)
+                : list_merge_run<false>(ctx, n_pods, n_shards, width, d_keys, nullptr, d_nodes,
+                                        d_out_node, out_ld, d_out_len, s);
 }
 
 }  // namespace pas

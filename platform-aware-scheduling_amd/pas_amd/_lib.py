@@ -217,6 +217,19 @@ SIGNATURES = {
     "pas_topk_merge_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "pas_list_merge_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P,
                                       _P]),
+    "pas_tas_topk_wide_device": (
+        c_int,
+        [_P, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P],
+    ),
+    "pas_tas_gas_topk_wide_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int32, c_int32, _P, _P, _P, _P, _P],
+    ),
+    "pas_topk_merge_wide_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                           _P]),
+    "pas_list_merge_wide_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                           c_int64, _P, _P]),
     "pas_encode_host_priority_list": (
         c_int, [c_int32, _P, POINTER(c_char_p), c_char_p, c_int64, POINTER(c_int64)]),
     "pas_encode_tas_filter_result": (

@@ -643,3 +643,49 @@ class Context:
                                            _dptr(nodes_t), _dptr(out_node_t), out_ld,
                                            _dptr(out_len_t), _stream(stream))
         self._check(rc, "pas_list_merge_device")
+
+    # ------------------------------------------------------------------ wide merge records
+    def tas_topk_wide_device(self, gen: int, n_pods: int, n_rules: int, rules_t, rule_off_t,
+                             prio_t, cand_t, k: int, node_base: int, key_t, sub_t, node_t, len_t,
+                             stream=None):
+        """tas_topk_device with wide records (pas_tas_topk_wide_device): key_t int64 [P][k],
+        sub_t uint32-sized [P][k] (torch.int32 storage), node_t int32 [P][k], len_t int32 [P];
+        exact on snapshots with wide columns and across shards of different column forms."""
+        rc = self._l.pas_tas_topk_wide_device(self._h, gen, n_pods, n_rules, _dptr(rules_t),
+                                              _dptr(rule_off_t), _dptr(prio_t), _dptr(cand_t), k,
+                                              node_base, _dptr(key_t), _dptr(sub_t),
+                                              _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_topk_wide_device")
+
+    def tas_gas_topk_wide_device(self, tas_gen: int, gas_gen: int, n_pods: int, n_rules: int,
+                                 rules_t, rule_off_t, prio_t, cand_t, max_containers: int,
+                                 i915_index: int, req_t, mask_t, ncont_t, k: int, node_base: int,
+                                 key_t, sub_t, node_t, len_t, stream=None):
+        """tas_gas_topk_device with wide records (pas_tas_gas_topk_wide_device)."""
+        rc = self._l.pas_tas_gas_topk_wide_device(
+            self._h, tas_gen, gas_gen, n_pods, n_rules, _dptr(rules_t), _dptr(rule_off_t),
+            _dptr(prio_t), _dptr(cand_t), max_containers, i915_index, _dptr(req_t),
+            _dptr(mask_t), _dptr(ncont_t), k, node_base, _dptr(key_t), _dptr(sub_t),
+            _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_gas_topk_wide_device")
+
+    def topk_merge_wide_device(self, n_pods: int, k: int, n_shards: int, keys_t, subs_t, nodes_t,
+                               out_node_t, out_len_t, stream=None):
+        """Merge of [n_shards][P][k] wide records into the global first-k lists
+        (n_shards * k <= 4096)."""
+        rc = self._l.pas_topk_merge_wide_device(self._h, n_pods, k, n_shards, _dptr(keys_t),
+                                                _dptr(subs_t), _dptr(nodes_t),
+                                                _dptr(out_node_t), _dptr(out_len_t),
+                                                _stream(stream))
+        self._check(rc, "pas_topk_merge_wide_device")
+
+    def list_merge_wide_device(self, n_pods: int, n_shards: int, width: int, keys_t, subs_t,
+                               nodes_t, out_node_t, out_len_t, out_ld: int = 0, stream=None):
+        """Merge of [n_shards][P][width] whole-shard wide records (tas_topk_wide_device with
+        k = width) into the cluster's full lists out_node [P][>= n_shards * width]."""
+        out_ld = out_ld or n_shards * width
+        rc = self._l.pas_list_merge_wide_device(self._h, n_pods, n_shards, width, _dptr(keys_t),
+                                                _dptr(subs_t), _dptr(nodes_t),
+                                                _dptr(out_node_t), out_ld, _dptr(out_len_t),
+                                                _stream(stream))
+        self._check(rc, "pas_list_merge_wide_device")

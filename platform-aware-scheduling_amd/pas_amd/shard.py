@@ -95,8 +95,10 @@ class ShardedFullList:
     int32 global node ids, -1 past len, lens [p1 - p0] int32) for the pods this rank owns
     (pod_slice)."""
 
-    def __init__(self, ctx, width: int, world: int, rank: int, node_base: int, device="cuda"):
+    def __init__(self, ctx, width: int, world: int, rank: int, node_base: int, device="cuda",
+                 wide: bool = False):
         self.ctx, self.width, self.world, self.rank = ctx, width, world, rank
+        self.wide = wide  # wide merge records (pas.h); every rank must pass the same value
         self.node_base = node_base
         self.device = device
         self._bufs = {}
@@ -118,21 +120,33 @@ class ShardedFullList:
         ln = self._buf("len", (world * per,), torch.int32)
         key[n_pods:].fill_(2**63 - 1)
         node[n_pods:].fill_(2**31 - 1)
+        sub = None
+        if self.wide:  # uint32 records in int32 storage: UINT32_MAX is -1
+            sub = self._buf("sub", (world * per, w), torch.int32)
+            sub[n_pods:].fill_(-1)
         if on_gpu and stream != cur:
             stream.wait_stream(cur)
-        self.ctx.tas_topk_device(gen, n_pods, n_rules, rules_t, rule_off_t, prio_t, cand_t, w,
-                                 self.node_base, key, node, ln, stream)
+        if self.wide:
+            self.ctx.tas_topk_wide_device(gen, n_pods, n_rules, rules_t, rule_off_t, prio_t,
+                                          cand_t, w, self.node_base, key, sub, node, ln, stream)
+        else:
+            self.ctx.tas_topk_device(gen, n_pods, n_rules, rules_t, rule_off_t, prio_t, cand_t,
+                                     w, self.node_base, key, node, ln, stream)
         if on_gpu and stream != cur:
             cur.wait_stream(stream)
         # [owner rank][its pods][w] -> [shard][my pods][w]
         keys_in = _all_to_all(key.view(world, per, w), world)
         nodes_in = _all_to_all(node.view(world, per, w), world)
+        subs_in = _all_to_all(sub.view(world, per, w), world) if self.wide else None
         if on_gpu and stream != cur:
             stream.wait_stream(cur)
         p0, p1 = pod_slice(n_pods, world, self.rank)
         out_node = self._buf("out_node", (per, world * w), torch.int32)
         out_len = self._buf("out_len", (per,), torch.int32)
-        if per:
+        if per and self.wide:
+            self.ctx.list_merge_wide_device(per, world, w, keys_in, subs_in, nodes_in, out_node,
+                                            out_len, stream=stream)
+        elif per:
             self.ctx.list_merge_device(per, world, w, keys_in, nodes_in, out_node, out_len,
                                        stream=stream)
         if on_gpu and stream != cur:
@@ -157,8 +171,12 @@ class ShardedTopK:
     cluster; None = the default group)."""
 
     def __init__(self, ctx, k: int, world: int, rank: int, node_base: int, device="cuda",
-                 group=None):
+                 group=None, wide: bool = False):
         self.ctx, self.k, self.world, self.rank = ctx, k, world, rank
+        # wide merge records (pas.h): exact with wide columns and with shards that hold a
+        # metric in different forms.  Explicit, not derived from the rank's snapshot: every
+        # rank of the group must use the same record form.
+        self.wide = wide
         self.node_base = node_base
         self.device = device
         self.group = group
@@ -172,9 +190,14 @@ class ShardedTopK:
         """`stream`: the torch.cuda.Stream the kernels run on (None = torch's current stream).
         The collectives run on torch's current stream, so the two are ordered with
         wait_stream in both directions when they differ."""
-        def records(key, node, ln, s):
-            self.ctx.tas_topk_device(gen, n_pods, n_rules, rules_t, rule_off_t, prio_t, cand_t,
-                                     self.k, self.node_base, key, node, ln, s)
+        def records(key, sub, node, ln, s):
+            if self.wide:
+                self.ctx.tas_topk_wide_device(gen, n_pods, n_rules, rules_t, rule_off_t, prio_t,
+                                              cand_t, self.k, self.node_base, key, sub, node, ln,
+                                              s)
+            else:
+                self.ctx.tas_topk_device(gen, n_pods, n_rules, rules_t, rule_off_t, prio_t,
+                                         cand_t, self.k, self.node_base, key, node, ln, s)
         return self._run(n_pods, records, stream)
 
     def run_tas_gas(self, tas_gen: int, gas_gen: int, n_pods: int, n_rules: int, rules_t,
@@ -183,11 +206,17 @@ class ShardedTopK:
         """The combined TAS + GAS top-k (BASELINE configs[4]): the shard's records over the
         nodes that pass the pod's dontschedule filter and fit its GPU request
         (pas_tas_gas_topk_device on the rank's resident TAS and GAS snapshots), merged."""
-        def records(key, node, ln, s):
-            self.ctx.tas_gas_topk_device(tas_gen, gas_gen, n_pods, n_rules, rules_t, rule_off_t,
-                                         prio_t, cand_t, max_containers, i915_index, req_t,
-                                         mask_t, ncont_t, self.k, self.node_base, key, node, ln,
-                                         s)
+        def records(key, sub, node, ln, s):
+            if self.wide:
+                self.ctx.tas_gas_topk_wide_device(tas_gen, gas_gen, n_pods, n_rules, rules_t,
+                                                  rule_off_t, prio_t, cand_t, max_containers,
+                                                  i915_index, req_t, mask_t, ncont_t, self.k,
+                                                  self.node_base, key, sub, node, ln, s)
+            else:
+                self.ctx.tas_gas_topk_device(tas_gen, gas_gen, n_pods, n_rules, rules_t,
+                                             rule_off_t, prio_t, cand_t, max_containers,
+                                             i915_index, req_t, mask_t, ncont_t, self.k,
+                                             self.node_base, key, node, ln, s)
         return self._run(n_pods, records, stream)
 
     def _run(self, n_pods, records, stream):
@@ -199,19 +228,25 @@ class ShardedTopK:
         key = self._buf("key", (n_pods, k), torch.int64)
         node = self._buf("node", (n_pods, k), torch.int32)
         ln = self._buf("len", (n_pods,), torch.int32)
+        sub = self._buf("sub", (n_pods, k), torch.int32) if self.wide else None
         if on_gpu and stream != cur:
             stream.wait_stream(cur)  # the caller's inputs (rules, candidates) are written
-        records(key, node, ln, stream)
+        records(key, sub, node, ln, stream)
         if on_gpu and stream != cur:
             cur.wait_stream(stream)  # records written before the all-gather reads them
         keys_all = _all_gather(key, self.world, self.group)
         nodes_all = _all_gather(node, self.world, self.group)
+        subs_all = _all_gather(sub, self.world, self.group) if self.wide else None
         if on_gpu and stream != cur:
             stream.wait_stream(cur)  # gathered records complete before the merge reads them
         out_node = self._buf("out_node", (n_pods, k), torch.int32)
         out_len = self._buf("out_len", (n_pods,), torch.int32)
-        self.ctx.topk_merge_device(n_pods, k, self.world, keys_all, nodes_all, out_node, out_len,
-                                   stream)
+        if self.wide:
+            self.ctx.topk_merge_wide_device(n_pods, k, self.world, keys_all, subs_all, nodes_all,
+                                            out_node, out_len, stream)
+        else:
+            self.ctx.topk_merge_device(n_pods, k, self.world, keys_all, nodes_all, out_node,
+                                       out_len, stream)
         if on_gpu and stream != cur:
             cur.wait_stream(stream)  # the caller reads the merged lists on its stream
         return out_node, out_len
@@ -277,7 +312,8 @@ class GridTopK:
     collective call), in the same order."""
 
     def __init__(self, ctx, k: int, world: int, rank: int, node_shards: int, n_pods: int,
-                 n_nodes: int, rules, rule_off, prio, req, mask, ncont, device="cuda"):
+                 n_nodes: int, rules, rule_off, prio, req, mask, ncont, device="cuda",
+                 wide: bool = False):
         import numpy as np
         self.ctx, self.k, self.world, self.rank = ctx, k, world, rank
         self.s = node_shards
@@ -294,7 +330,8 @@ class GridTopK:
                 grp = dist.new_group(list(range(gi * self.s, (gi + 1) * self.s)))
                 if gi == self.group_id:
                     pg = grp
-        self.topk = ShardedTopK(ctx, k, self.s, self.shard_id, self.n0, device, group=pg)
+        self.topk = ShardedTopK(ctx, k, self.s, self.shard_id, self.n0, device, group=pg,
+                                wide=wide)
 
         def dev(a):
             return torch.from_numpy(np.ascontiguousarray(a)).to(device)
