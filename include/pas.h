@@ -517,6 +517,54 @@ int pas_gas_bind_counts(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_
                         uint32_t* res_out, int32_t* status_out,
                         int64_t* counts_out /*[n_binds][max_containers][max_cards]*/);
 
+/* Batch placement: the pods of a batch bound in order, each along its row of candidate
+ * nodes, e.g. the top_node / top_len of pas_tas_gas_topk_device or the out_node / out_len
+ * of pas_topk_merge_device, unchanged.  The call is exactly this loop over the resident
+ * usage (N = the snapshot's node count), every bind seeing the binds before it as the
+ * reference's pod-after-pod bindNode calls do (scheduler.go:385-445):
+ *
+ *   for p in 0 .. n_pods-1:                      pod order is the priority order
+ *     place_node[p] = -1; place_rank[p] = -1; res_out[p] = 0
+ *     for j in 0 .. min(k, cand_len ? cand_len[p] : k) - 1:
+ *       n = cand_node[p * ld + j] - node_base
+ *       if n < 0 or n >= N: continue             -1 / INT32_MAX padding, other shards' ids
+ *       the single bind pas_gas_bind(pod p, node n) on the current usage
+ *       if its status is PAS_GAS_OK:             committed
+ *         place_node[p] = n + node_base; place_rank[p] = j; res_out[p] = its word; break
+ *
+ * A pod that fits nowhere changes nothing; a node repeated within a row is tried again.
+ * cards_out [n_pods][64] with n_sel_out [n_pods] (both or neither) and counts_out
+ * [n_pods][max_containers][max_cards] are optional and mean what they mean in
+ * pas_gas_bind_ex / pas_gas_bind_counts for the placing bind (zeros for unplaced pods).
+ * *n_placed (optional) = pods placed; *n_rounds (optional) = device rounds taken, a
+ * diagnostic.  The snapshot moves from gen_from (PAS_ESTALE otherwise, nothing changed) to
+ * gen_to.  PAS_EINVAL for k < 1, ld < k, and in the host form n_containers out of range or
+ * mask bits >= n_res.  The _device form takes device pointers (n_placed / n_rounds stay host
+ * pointers) and cannot validate the arrays: it reads d_n_containers[p] clamped into
+ * [0, max_containers] and d_cand_len[p] clamped into [0, k], and skips every candidate id
+ * outside the shard.
+ * BOTH forms return only when the placement is complete: the work runs in rounds on the
+ * stream and the host decides after each round whether another is needed, so the call
+ * synchronizes the stream (as pas_gas_bind does); the _device form only saves the copies.
+ * If a HIP call fails, or the round bound sum(row lengths) + 1 trips, after commits began,
+ * the call returns PAS_EDEVICE and the GAS snapshot is invalid (later calls: PAS_ENOSNAP)
+ * until the next pas_gas_snapshot_set[_device]: no half-committed snapshot stays valid. */
+int pas_gas_place(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_pods,
+                  int32_t max_containers, int32_t i915_index, const int64_t* req,
+                  const uint32_t* req_mask, const int32_t* n_containers, int32_t k, int32_t ld,
+                  int32_t node_base, const int32_t* cand_node /*[n_pods][ld]*/,
+                  const int32_t* cand_len, int32_t* place_node, int32_t* place_rank,
+                  uint32_t* res_out, uint8_t* cards_out, int32_t* n_sel_out,
+                  int64_t* counts_out, int32_t* n_placed, int32_t* n_rounds);
+int pas_gas_place_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_pods,
+                         int32_t max_containers, int32_t i915_index, const int64_t* d_req,
+                         const uint32_t* d_req_mask, const int32_t* d_n_containers, int32_t k,
+                         int32_t ld, int32_t node_base, const int32_t* d_cand_node,
+                         const int32_t* d_cand_len, int32_t* d_place_node,
+                         int32_t* d_place_rank, uint32_t* d_res_out, uint8_t* d_cards_out,
+                         int32_t* d_n_sel_out, int64_t* d_counts_out, int32_t* n_placed,
+                         int32_t* n_rounds, void* hip_stream);
+
 /* Pods leaving nodes: Cache.adjustPodResources(remove) (node_resource_cache.go:240-287) with
  * each pod's annotation, in call order.  Container c of release r has cards_per_container
  * [r][c] cards (its "gas-container-cards" segment), listed in container order in

@@ -271,6 +271,7 @@ void pas_destroy(pas_ctx* ctx) {
   if (ctx->gas.derived_sync.ev) (void)hipEventDestroy(ctx->gas.derived_sync.ev);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->gas_sync_fault) (void)hipHostFree(ctx->gas_sync_fault);
+  if (ctx->place_host) (void)hipHostFree(ctx->place_host);
   for (AuxSlot& a : ctx->aux_slot) {
     if (a.p) (void)hipFree(a.p);
     if (a.gas_counts) (void)hipFree(a.gas_counts);
@@ -1063,6 +1064,141 @@ int pas_gas_release_counts(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
                     max_containers, -1, req, req_mask, n_containers, nullptr, nullptr, 1,
                     nullptr, status_out, nullptr, nullptr, nullptr, counts ? counts : &kNone,
                     "pas_gas_release_counts");
+}
+
+// What pas_gas_place and pas_gas_place_device share: the checks a host can make on either
+// form's scalars and pointers.
+static int gas_place_check(pas_ctx* ctx, uint64_t gen_from, int32_t n_pods,
+                           int32_t max_containers, int32_t i915_index, const void* req,
+                           const void* req_mask, const void* n_containers, int32_t k, int32_t ld,
+                           const void* cand_node, const void* place_node, const void* place_rank,
+                           const void* res_out, const void* cards_out, const void* n_sel_out,
+                           const char* fn) {
+  int rc = check_gas_gen(ctx, gen_from);
+  if (rc) return rc;
+  if (n_pods < 0 || max_containers < 0 || i915_index >= ctx->gas.n_res || i915_index < -1 ||
+      k < 1 || ld < k)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  if ((cards_out == nullptr) != (n_sel_out == nullptr))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": cards_out and n_sel_out go together");
+  if (n_pods > 0 && (!n_containers || !cand_node || !place_node || !place_rank || !res_out ||
+                     (max_containers > 0 && (!req || !req_mask))))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  return PAS_OK;
+}
+
+// The rounds, then the generation step; a failure after commits began leaves no valid
+// snapshot behind.
+static int gas_place_finish(pas_ctx* ctx, int rc, bool began, uint64_t gen_to) {
+  if (rc) {
+    if (began) {
+      ctx->gas.valid = false;
+      if (rc != PAS_EDEVICE) rc = set_error(ctx, PAS_EDEVICE, ctx->err);
+    }
+    return rc;
+  }
+  ctx->gas.gen = gen_to;
+  ++ctx->gas.epoch;
+  return PAS_OK;
+}
+
+int pas_gas_place_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_pods,
+                         int32_t max_containers, int32_t i915_index, const int64_t* d_req,
+                         const uint32_t* d_req_mask, const int32_t* d_n_containers, int32_t k,
+                         int32_t ld, int32_t node_base, const int32_t* d_cand_node,
+                         const int32_t* d_cand_len, int32_t* d_place_node,
+                         int32_t* d_place_rank, uint32_t* d_res_out, uint8_t* d_cards_out,
+                         int32_t* d_n_sel_out, int64_t* d_counts_out, int32_t* n_placed,
+                         int32_t* n_rounds, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = gas_place_check(ctx, gen_from, n_pods, max_containers, i915_index, d_req, d_req_mask,
+                           d_n_containers, k, ld, d_cand_node, d_place_node, d_place_rank,
+                           d_res_out, d_cards_out, d_n_sel_out, "pas_gas_place_device");
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  bool began = false;
+  rc = gas_place_launch(ctx, n_pods, max_containers, i915_index, d_req, d_req_mask,
+                        d_n_containers, k, ld, node_base, d_cand_node, d_cand_len, d_place_node,
+                        d_place_rank, d_res_out, d_cards_out, d_n_sel_out, d_counts_out,
+                        n_placed, n_rounds, &began, pick_stream(ctx, hip_stream));
+  return gas_place_finish(ctx, rc, began, gen_to);
+}
+
+int pas_gas_place(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_pods,
+                  int32_t max_containers, int32_t i915_index, const int64_t* req,
+                  const uint32_t* req_mask, const int32_t* n_containers, int32_t k, int32_t ld,
+                  int32_t node_base, const int32_t* cand_node, const int32_t* cand_len,
+                  int32_t* place_node, int32_t* place_rank, uint32_t* res_out,
+                  uint8_t* cards_out, int32_t* n_sel_out, int64_t* counts_out,
+                  int32_t* n_placed, int32_t* n_rounds) {
+  if (!ctx) return PAS_EINVAL;
+  const char* fn = "pas_gas_place";
+  int rc = gas_place_check(ctx, gen_from, n_pods, max_containers, i915_index, req, req_mask,
+                           n_containers, k, ld, cand_node, place_node, place_rank, res_out,
+                           cards_out, n_sel_out, fn);
+  if (rc) return rc;
+  const int32_t Q = ctx->gas.n_res, K = ctx->gas.max_cards;
+  for (int32_t p = 0; p < n_pods; ++p) {
+    if (n_containers[p] < 0 || n_containers[p] > max_containers)
+      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": n_containers out of range");
+    for (int32_t c = 0; c < n_containers[p]; ++c)
+      if ((req_mask[(int64_t)p * max_containers + c] & ~PAS_REQ_UNKNOWN_KIND) >> Q)
+        return set_error(ctx, PAS_EINVAL, std::string(fn) + ": mask bit >= n_res");
+  }
+  if ((rc = activate(ctx))) return rc;
+  const size_t P = (size_t)n_pods, C = (size_t)max_containers;
+  const bool counts = counts_out && C > 0;
+  const size_t b_req = sizeof(int64_t) * P * C * Q, b_mask = sizeof(uint32_t) * P * C;
+  const size_t b_pod = sizeof(int32_t) * P, b_cand = sizeof(int32_t) * P * (size_t)ld;
+  const size_t b_sel = cards_out ? P * PAS_GAS_MAX_SELECTIONS : 0;
+  const size_t b_cnt = counts ? sizeof(int64_t) * P * C * (size_t)K : 0;
+  if ((rc = ensure_scratch(ctx, carve_size({b_req, b_mask, b_pod, b_cand, b_pod, b_pod, b_pod,
+                                            b_pod, b_sel, b_pod, b_cnt}))))
+    return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int64_t* d_req = cv.take<int64_t>(P * C * Q);
+  uint32_t* d_mask = cv.take<uint32_t>(P * C);
+  int32_t* d_nc = cv.take<int32_t>(P);
+  int32_t* d_cand = cv.take<int32_t>(P * (size_t)ld);
+  int32_t* d_len = cv.take<int32_t>(P);
+  int32_t* d_node = cv.take<int32_t>(P);
+  int32_t* d_rank = cv.take<int32_t>(P);
+  uint32_t* d_res = cv.take<uint32_t>(P);
+  uint8_t* d_sel = cv.take<uint8_t>(b_sel);
+  int32_t* d_nsel = cv.take<int32_t>(P);
+  int64_t* d_cnt = cv.take<int64_t>(b_cnt / sizeof(int64_t));
+  hipStream_t s = ctx->stream;
+  if (n_pods > 0) {
+    if (C > 0) {
+      PAS_HIP(ctx, hipMemcpyAsync(d_req, req, b_req, hipMemcpyHostToDevice, s));
+      PAS_HIP(ctx, hipMemcpyAsync(d_mask, req_mask, b_mask, hipMemcpyHostToDevice, s));
+    }
+    PAS_HIP(ctx, hipMemcpyAsync(d_nc, n_containers, b_pod, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_cand, cand_node, b_cand, hipMemcpyHostToDevice, s));
+    if (cand_len) PAS_HIP(ctx, hipMemcpyAsync(d_len, cand_len, b_pod, hipMemcpyHostToDevice, s));
+  }
+  bool began = false;
+  rc = gas_place_launch(ctx, n_pods, max_containers, i915_index, d_req, d_mask, d_nc, k, ld,
+                        node_base, d_cand, cand_len ? d_len : nullptr, d_node, d_rank, d_res,
+                        cards_out ? d_sel : nullptr, cards_out ? d_nsel : nullptr,
+                        counts ? d_cnt : nullptr, n_placed, n_rounds, &began, s);
+  if (!rc && n_pods > 0) {
+    const hipError_t e = [&] {
+      hipError_t r = hipMemcpyAsync(place_node, d_node, b_pod, hipMemcpyDeviceToHost, s);
+      if (r == hipSuccess) r = hipMemcpyAsync(place_rank, d_rank, b_pod, hipMemcpyDeviceToHost, s);
+      if (r == hipSuccess) r = hipMemcpyAsync(res_out, d_res, b_pod, hipMemcpyDeviceToHost, s);
+      if (r == hipSuccess && cards_out) {
+        r = hipMemcpyAsync(cards_out, d_sel, b_sel, hipMemcpyDeviceToHost, s);
+        if (r == hipSuccess) r = hipMemcpyAsync(n_sel_out, d_nsel, b_pod, hipMemcpyDeviceToHost, s);
+      }
+      if (r == hipSuccess && counts)
+        r = hipMemcpyAsync(counts_out, d_cnt, b_cnt, hipMemcpyDeviceToHost, s);
+      if (r == hipSuccess) r = hipStreamSynchronize(s);
+      return r;
+    }();
+    if (e != hipSuccess) rc = check_hip(ctx, e, "pas_gas_place: copy of the results");
+  }
+  return gas_place_finish(ctx, rc, began, gen_to);
 }
 
 int pas_gas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* used_out) {

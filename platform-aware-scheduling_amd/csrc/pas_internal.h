@@ -189,7 +189,8 @@ enum SlotBuf {
   kBufGpass = 0,  // pass bitmaps of clusters past the LDS bitmap (tas_eval)
   kBufMerge = 1,  // cut list and ping-pong rows of the full-list merge (tas_list_merge.hip)
   kBufLabel = 2,  // per-workgroup partial counts of the label plan (tas_labels.hip)
-  kSlotBufs = 3
+  kBufPlace = 3,  // cursors, keys, blockers and sort storage of a placement (gas_place.hip)
+  kSlotBufs = 4
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -273,6 +274,7 @@ struct pas_ctx {
   int gas_sync_mode = -1;
   uint32_t* gas_sync_fault = nullptr;
   int gas_force_timeouts = 0;  // PAS_GAS_FORCE_TIMEOUT: the next n flag-mode fits time out
+  void* place_host = nullptr;  // pas_gas_place: the round counts' read-back (host-pinned)
   // timing
   int timing = 0;  // 0 off, PAS_TIMING_SPAN, PAS_TIMING_KERNELS (pas_set_timing)
   std::vector<pas::TimedLaunch> pending;
@@ -397,6 +399,16 @@ int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_seg, int32_t max_con
                       const int32_t* d_cards, int32_t cards_stride, uint32_t* d_res,
                       int32_t* d_status, uint8_t* d_cards_out, int32_t* d_nsel_out,
                       int64_t* d_counts_out, const int64_t* d_counts, hipStream_t s);
+// Batch placement (gas_place.hip): the rounds of pas_gas_place_device on s, returning when the
+// placement is complete.  *began: commits were launched (an error past that point leaves
+// the resident usage half committed: the caller invalidates the snapshot).
+int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t i915_index,
+                     const int64_t* d_req, const uint32_t* d_mask, const int32_t* d_ncont,
+                     int32_t k, int32_t ld, int32_t node_base, const int32_t* d_cand,
+                     const int32_t* d_cand_len, int32_t* d_place_node, int32_t* d_place_rank,
+                     uint32_t* d_res, uint8_t* d_cards_out, int32_t* d_nsel_out,
+                     int64_t* d_counts_out, int32_t* n_placed, int32_t* n_rounds,
+                     bool* began, hipStream_t s);
 // Policy names of the deschedule strategies (updateNodeLabels keys its non-violated set by
 // name, deschedule/enforce.go:89-134).  A name is represented by its first strategy k
 // (canonical); bit k of canon marks those.  Names held by one strategy are the bits of single;

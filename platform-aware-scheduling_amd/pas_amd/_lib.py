@@ -192,6 +192,16 @@ SIGNATURES = {
         [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
          _P],
     ),
+    "pas_gas_place": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, c_int32, c_int32, _P, _P, _P, c_int32, c_int32,
+         c_int32, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(c_int32), POINTER(c_int32)],
+    ),
+    "pas_gas_place_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, c_int32, c_int32, _P, _P, _P, c_int32, c_int32,
+         c_int32, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(c_int32), POINTER(c_int32), _P],
+    ),
     "pas_gas_release": (
         c_int,
         [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P],

@@ -523,6 +523,58 @@ class Context:
         self._check(rc, "pas_gas_bind_ex")
         return res, st, cards, nsel
 
+    def gas_place(self, gen_from: int, gen_to: int, req: np.ndarray, req_mask: np.ndarray,
+                  n_containers: np.ndarray, i915_index: int, cand_node, cand_len=None,
+                  k: Optional[int] = None, node_base: int = 0, selections: bool = False,
+                  counts: bool = False, rounds: bool = False):
+        """Batch placement (pas_gas_place): pod p, in order, binds to the first node of its row
+        cand_node[p, :k] (cut to cand_len[p]) that takes it on the usage the pods before it
+        left.  Returns (place_node [P], place_rank [P], result words [P], n_placed), then
+        (cards [P][64], n_sel [P]) with selections=True, counts [P][C][K] with counts=True and
+        the number of device rounds with rounds=True, in that order."""
+        req = np.ascontiguousarray(req, dtype=np.int64)
+        p, c, q = req.shape
+        req_mask = np.ascontiguousarray(req_mask, dtype=np.uint32)
+        n_containers = np.ascontiguousarray(n_containers, dtype=np.int32)
+        cand_node = np.ascontiguousarray(cand_node, dtype=np.int32)
+        assert cand_node.ndim == 2 and cand_node.shape[0] == p, "cand_node is [P][ld]"
+        ld = cand_node.shape[1]
+        k = ld if k is None else k
+        if cand_len is not None:
+            cand_len = np.ascontiguousarray(cand_len, dtype=np.int32)
+        node = np.zeros(p, np.int32)
+        rank = np.zeros(p, np.int32)
+        res = np.zeros(p, np.uint32)
+        cards = np.zeros((p, _lib.PAS_GAS_MAX_SELECTIONS), np.uint8) if selections else None
+        nsel = np.zeros(p, np.int32) if selections else None
+        cnt = np.zeros((p, c, self.gas_shape[1]), np.int64) if counts else None
+        n_placed, n_rounds = c_int32(0), c_int32(0)
+        rc = self._l.pas_gas_place(self._h, gen_from, gen_to, p, c, i915_index, _ptr(req),
+                                   _ptr(req_mask), _ptr(n_containers), k, ld, node_base,
+                                   _ptr(cand_node), _ptr(cand_len), _ptr(node), _ptr(rank),
+                                   _ptr(res), _ptr(cards), _ptr(nsel), _ptr(cnt),
+                                   byref(n_placed), byref(n_rounds))
+        self._check(rc, "pas_gas_place")
+        out = (node, rank, res, n_placed.value)
+        out += (cards, nsel) if selections else ()
+        out += (cnt,) if counts else ()
+        return out + ((n_rounds.value,) if rounds else ())
+
+    def gas_place_device(self, gen_from: int, gen_to: int, n_pods: int, max_containers: int,
+                         i915_index: int, req_t, mask_t, ncont_t, k: int, ld: int,
+                         node_base: int, cand_t, len_t, place_node_t, place_rank_t, res_t,
+                         cards_t=None, nsel_t=None, counts_t=None, stream=None):
+        """pas_gas_place_device on device tensors (len_t, cards_t / nsel_t and counts_t may be
+        None); returns (n_placed, device rounds) once the placement is complete."""
+        n_placed, n_rounds = c_int32(0), c_int32(0)
+        rc = self._l.pas_gas_place_device(
+            self._h, gen_from, gen_to, n_pods, max_containers, i915_index, _dptr(req_t),
+            _dptr(mask_t), _dptr(ncont_t), k, ld, node_base, _dptr(cand_t), _dptr(len_t),
+            _dptr(place_node_t), _dptr(place_rank_t), _dptr(res_t), _dptr(cards_t),
+            _dptr(nsel_t), _dptr(counts_t), byref(n_placed), byref(n_rounds), _stream(stream))
+        self._check(rc, "pas_gas_place_device")
+        return n_placed.value, n_rounds.value
+
     def gas_release(self, gen_from: int, gen_to: int, pods, nodes, req: np.ndarray,
                     req_mask: np.ndarray, n_containers: np.ndarray, cards_per_container,
                     cards) -> np.ndarray:
