@@ -596,6 +596,78 @@ int pas_gas_release_counts(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
                            const int64_t* counts /*[n_releases][max_containers][max_cards]*/,
                            int32_t* status_out);
 
+/* Pod events: the third way the resident usage changes, and the one that keeps it true when
+ * this process is not the only writer.  Cache.handlePod (node_resource_cache.go:493-538)
+ * sees a pod that already carries a "gas-container-cards" annotation (bound by another
+ * extender replica, by an earlier run, or met in the informer's initial list) and calls
+ * adjustPodResources(add) straight from the annotation: no fit, no capacity check, only
+ * addRM's checks; a completed pod gets adjustPodResources(remove).  One call applies an
+ * ordered batch of such events in place; its large case is the cold-start rebuild (zero
+ * usage, then every running pod's annotation as one ADD batch).
+ *
+ * Event e is (ev_kind[e], pod ev_pod[e], node ev_node[e]); req / req_mask / n_containers
+ * describe the pods as for pas_gas_fit.  Its annotation has the layout of
+ * pas_gas_release_ex with a row length the caller chooses: container c lists
+ * cards_per_container[e][c] cards, stored consecutively in cards[e][0 .. cards_ld), in
+ * container order, as ranks into the node's label cards.  A rank that is negative or >= the
+ * node's card count names a card the label does not list (a node with n_cards <= 0 lists
+ * none).  Events are applied in call order: events on one node see each other in that order,
+ * events on different nodes are independent.  status_out[e] is PAS_GAS_OK or the error, and
+ * an event that fails changes nothing (all or nothing per event).
+ *
+ * PAS_GAS_EV_ADD (checkPodResourceAdjustment then adjustPodResources, :190-287; addRM / add,
+ * resource_map.go:38-53,77-98; divide, :129-145), for containers c in order with numCards =
+ * cards_per_container[e][c] > 0: r[q] = req[p][c][q] / numCards (truncating; numCards counts
+ * every listed card, also those outside the label) for the kinds q of the container's mask.
+ * For each listed card in list order and each masked kind: r[q] < 0 is PAS_GAS_ERR_INPUT;
+ * otherwise, on a label card, used + r[q] < 0 (the sum wraps as Go's does) is
+ * PAS_GAS_ERR_OVERFLOW; a card listed several times is added to several times.  The first
+ * failing (container, listed card) decides the status.  Within one card the reference's
+ * order is Go-map order; here a negative amount is reported before an overflow.  A card
+ * outside the label is checked for the negative amount and otherwise skipped: the reference
+ * would keep usage for a card no fit ever reads.  PAS_REQ_UNKNOWN_KIND is ignored on ADD: the
+ * reference adds a key no capacity map has, and because that key's amount is not carried in
+ * the batch, its errInput on a negative value is not reproduced.  There is no capacity
+ * check: usage may end above capacity, which every fit treats as "does not fit".
+ *
+ * PAS_GAS_EV_REMOVE is exactly pas_gas_release_ex on the node's current usage, with rows of
+ * cards_ld: clamp at 0; PAS_GAS_ERR_INPUT for a negative amount, a card outside the label,
+ * or PAS_REQ_UNKNOWN_KIND on a non-empty segment.
+ *
+ * gen_from is checked (PAS_ESTALE, nothing changed) and the snapshot moves to gen_to in the
+ * call.  The host form validates as pas_gas_release does, PAS_EINVAL for: an event kind
+ * outside {0, 1}, a node or pod index out of range, n_containers out of range, mask bits >=
+ * n_res, a negative card count, a pod's counts summing past cards_ld, cards_ld < 1.  It
+ * uploads, runs the _device form's path (the grouping by node is a device sort in both),
+ * waits and copies status_out back; a HIP failure in that last step, after the commit kernel
+ * was enqueued, returns PAS_EDEVICE and leaves the GAS snapshot invalid (PAS_ENOSNAP until the
+ * next pas_gas_snapshot_set), since the statuses of what ran are lost.
+ * The _device form takes device pointers, is asynchronous on hip_stream and moves the
+ * generation once the commit kernel is enqueued; it does not wait for the device (its sort
+ * storage is per stream and allocated when a larger batch first needs it).  A HIP failure
+ * before that launch leaves the snapshot and its generation untouched.  It cannot validate
+ * the arrays: an event whose kind, node or pod is out of range gets PAS_GAS_ERR_INPUT and
+ * changes nothing, n_containers is read clamped into [0, max_containers], negative card
+ * counts read as 0, and an event whose running card offset would pass cards_ld gets
+ * PAS_GAS_ERR_INPUT; no array is read or written outside its bounds.  As for every snapshot
+ * change, the caller orders the call after readers on other streams. */
+#define PAS_GAS_EV_ADD 0    /* podAdded / podUpdated: adjustPodResources(add) */
+#define PAS_GAS_EV_REMOVE 1 /* podCompleted / podDeleted: adjustPodResources(remove) */
+int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
+                  const int32_t* ev_kind, const int32_t* ev_pod, const int32_t* ev_node,
+                  int32_t n_pods, int32_t max_containers, const int64_t* req,
+                  const uint32_t* req_mask, const int32_t* n_containers,
+                  const int32_t* cards_per_container /*[n_events][max_containers]*/,
+                  const int32_t* cards /*[n_events][cards_ld]*/, int32_t cards_ld,
+                  int32_t* status_out /*[n_events]*/);
+int pas_gas_apply_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
+                         const int32_t* d_ev_kind, const int32_t* d_ev_pod,
+                         const int32_t* d_ev_node, int32_t n_pods, int32_t max_containers,
+                         const int64_t* d_req, const uint32_t* d_req_mask,
+                         const int32_t* d_n_containers,
+                         const int32_t* d_cards_per_container, const int32_t* d_cards,
+                         int32_t cards_ld, int32_t* d_status_out, void* hip_stream);
+
 /* Read back the resident usage used[N][K][Q] and its generation. */
 int pas_gas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* used_out);
 

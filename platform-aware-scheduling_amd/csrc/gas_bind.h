@@ -4,6 +4,8 @@
 // node's current usage, then adjustPodResources(add) with the resulting annotation.  Both
 // the pair-list commit (gas_commit.hip) and the batch placement (gas_place.hip) call it, so
 // an operation gives the same word, selections and usage whichever call carries it.
+// release_one and adopt_one are the reference's adjustPodResources(remove / add) from an
+// annotation, shared the same way by the release kernel and the event path (gas_commit.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,9 +37,9 @@ struct BindArgs {
   const int64_t* req;      // [n_pods][C][Q]
   const uint32_t* mask;    // [n_pods][C]
   const int32_t* ncont;    // [n_pods]
-  const int32_t* cpc;      // release: [n_ops][C] cards per container
-  const int32_t* cards;    // release: [n_ops][cards_stride]
-  int32_t cards_stride;    // 8 (pas_gas_release) or PAS_GAS_MAX_SELECTIONS (_ex)
+  const int32_t* cpc;      // release / apply: [n_ops][C] cards per container
+  const int32_t* cards;    // release / apply: [n_ops][cards_stride]
+  int32_t cards_stride;    // 8 (pas_gas_release), PAS_GAS_MAX_SELECTIONS (_ex), cards_ld (apply)
   uint32_t* res_out;       // bind: [n_ops]
   int32_t* status;         // [n_ops]
   uint8_t* cards_out;      // bind_ex: [n_ops][PAS_GAS_MAX_SELECTIONS] or null
@@ -136,6 +138,129 @@ __device__ __forceinline__ bool bind_one(const BindArgs& a, int64_t (&u)[KMAX][k
   for (int k = 0; k < K; ++k)
     for (int q = 0; q < Q; ++q) u[k][q] = w[k][q];
   return true;
+}
+
+// adjustPodResources(remove) (node_resource_cache.go:236-287, subtractRM resource_map.go:
+// 55-73,103-127) of operation `op` (pod p, ncont containers) on the node's usage u: true and u
+// advanced, false (errInput) and u untouched.  The annotation is a.counts (counts per
+// container and card) or a.cpc / a.cards; a card list that would run past its row is errInput
+// (the host entry points reject it before the launch).
+template <int KMAX>
+__device__ __forceinline__ bool release_one(const BindArgs& a, int64_t (&u)[KMAX][kBindMaxRes],
+                                            int32_t ncard, int32_t p, int32_t ncont,
+                                            int64_t op) {
+  const int32_t K = a.K, Q = a.Q, C = a.C;
+  int64_t w[KMAX][kBindMaxRes];  // checkPodResourceAdjustment's copy
+  for (int k = 0; k < K; ++k)
+    for (int q = 0; q < Q; ++q) w[k][q] = u[k][q];
+  bool ok = true;
+  int32_t off = 0;
+  if (a.counts) {  // the annotation as counts per container and card (any length)
+    const int64_t* cnt = a.counts + op * C * K;
+    for (int32_t c = 0; ok && c < ncont; ++c) {
+      int64_t kc = 0;  // numCards (the host checked that the sum does not overflow)
+      for (int k = 0; k < K; ++k) kc += cnt[(int64_t)c * K + k];
+      if (kc <= 0) continue;  // empty annotation segment
+      const int64_t b = (int64_t)p * C + c;
+      const uint32_t m = a.mask[b];
+      if (m & PAS_REQ_UNKNOWN_KIND) ok = false;
+      int64_t r[kBindMaxRes];
+      for (int q = 0; q < Q; ++q) r[q] = a.req[b * Q + q] / kc;  // divide(numCards)
+      for (int k = 0; ok && k < K; ++k) {
+        const int64_t t = cnt[(int64_t)c * K + k];
+        if (t <= 0) continue;
+        for (int q = 0; q < Q; ++q) {
+          if (!((m >> q) & 1u)) continue;
+          if (r[q] < 0 || k >= ncard) {  // negative amount / a card the label lacks
+            ok = false;
+            break;
+          }
+          w[k][q] = subtract_times(w[k][q], r[q], t);
+        }
+      }
+    }
+  }
+  for (int32_t c = 0; !a.counts && ok && c < ncont; ++c) {
+    const int32_t kc = a.cpc[op * C + c];
+    if (kc <= 0) continue;  // empty annotation segment
+    if ((int64_t)off + kc > a.cards_stride) {  // the list would leave its row
+      ok = false;
+      break;
+    }
+    const int64_t b = (int64_t)p * C + c;
+    const uint32_t m = a.mask[b];
+    int64_t r[kBindMaxRes];
+    for (int q = 0; q < Q; ++q) r[q] = a.req[b * Q + q] / kc;  // divide(numCards)
+    // subtractRM of a key no card map has (a kind outside the snapshot) -> errInput
+    if (m & PAS_REQ_UNKNOWN_KIND) ok = false;
+    for (int32_t j = 0; ok && j < kc; ++j) {
+      const int32_t k = a.cards[op * a.cards_stride + off + j];
+      const bool known = k >= 0 && k < ncard;
+      for (int q = 0; q < Q; ++q) {
+        if (!((m >> q) & 1u)) continue;
+        // subtract: negative amount or a key the card lacks -> errInput
+        if (r[q] < 0 || !known) {
+          ok = false;
+          break;
+        }
+        const int64_t v = (int64_t)((uint64_t)w[k][q] - (uint64_t)r[q]);  // Go wraps
+        w[k][q] = v < 0 ? 0 : v;  // capped to zero
+      }
+    }
+    off += kc;
+  }
+  if (!ok) return false;
+  for (int k = 0; k < K; ++k)
+    for (int q = 0; q < Q; ++q) u[k][q] = w[k][q];
+  return true;
+}
+
+// adjustPodResources(add) straight from an annotation (Cache.handlePod's podAdded /
+// podUpdated, node_resource_cache.go:190-287,493-538): no fit and no capacity check, only
+// addRM's checks (resource_map.go:38-53,77-98).  Container c lists a.cpc[op][c] cards, stored
+// consecutively in a.cards[op][..] as ranks into the node's label cards; request / numCards
+// (divide, :129-145) goes to each listed card, a card listed twice twice.  The status of the
+// first failing (container, listed card) is returned and u is untouched: a negative amount is
+// PAS_GAS_ERR_INPUT (reported before an overflow on the same card, where the reference follows
+// Go-map order), a sum that wraps below zero PAS_GAS_ERR_OVERFLOW.  A rank outside the label
+// (negative or >= ncard) counts towards numCards and is otherwise skipped: no fit reads such
+// a card.  PAS_REQ_UNKNOWN_KIND is ignored (the key's amount is not in the batch).  A card
+// list that would run past its row is PAS_GAS_ERR_INPUT.
+template <int KMAX>
+__device__ __forceinline__ int32_t adopt_one(const BindArgs& a, int64_t (&u)[KMAX][kBindMaxRes],
+                                             int32_t ncard, int32_t p, int32_t ncont,
+                                             int64_t op) {
+  const int32_t K = a.K, Q = a.Q, C = a.C;
+  int64_t w[KMAX][kBindMaxRes];  // checkPodResourceAdjustment's copy
+  for (int k = 0; k < K; ++k)
+    for (int q = 0; q < Q; ++q) w[k][q] = u[k][q];
+  int32_t off = 0;
+  for (int32_t c = 0; c < ncont; ++c) {
+    const int32_t kc = a.cpc[op * C + c];
+    if (kc <= 0) continue;  // empty annotation segment
+    if ((int64_t)off + kc > a.cards_stride) return PAS_GAS_ERR_INPUT;
+    const int64_t b = (int64_t)p * C + c;
+    const uint32_t m = a.mask[b];
+    int64_t r[kBindMaxRes];
+    for (int q = 0; q < Q; ++q) {
+      r[q] = a.req[b * Q + q] / kc;  // divide(numCards)
+      if (((m >> q) & 1u) && r[q] < 0) return PAS_GAS_ERR_INPUT;  // add: value < 0
+    }
+    for (int32_t j = 0; j < kc; ++j) {
+      const int32_t k = a.cards[op * a.cards_stride + off + j];
+      if (k < 0 || k >= ncard) continue;  // a card the label does not list
+      for (int q = 0; q < Q; ++q) {
+        if (!((m >> q) & 1u)) continue;
+        const int64_t v = (int64_t)((uint64_t)w[k][q] + (uint64_t)r[q]);  // Go wraps
+        if (v < 0) return PAS_GAS_ERR_OVERFLOW;
+        w[k][q] = v;
+      }
+    }
+    off += kc;
+  }
+  for (int k = 0; k < K; ++k)
+    for (int q = 0; q < Q; ++q) u[k][q] = w[k][q];
+  return PAS_GAS_OK;
 }
 
 }  // namespace pas

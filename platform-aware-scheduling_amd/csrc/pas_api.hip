@@ -1066,6 +1066,131 @@ int pas_gas_release_counts(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
                     "pas_gas_release_counts");
 }
 
+// What pas_gas_apply and pas_gas_apply_device share: the checks a host can make on either
+// form's scalars and pointers.
+static int gas_apply_check(pas_ctx* ctx, uint64_t gen_from, int32_t n_events, const void* ev_kind,
+                           const void* ev_pod, const void* ev_node, int32_t n_pods,
+                           int32_t max_containers, const void* req, const void* req_mask,
+                           const void* n_containers, const void* cpc, const void* cards,
+                           int32_t cards_ld, const void* status_out, const char* fn) {
+  int rc = check_gas_gen(ctx, gen_from);
+  if (rc) return rc;
+  if (n_events < 0 || n_pods < 0 || max_containers < 0 || cards_ld < 1)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  if (n_events > 0 && (!ev_kind || !ev_pod || !ev_node || !status_out || !cards ||
+                       (n_pods > 0 && !n_containers) ||
+                       (max_containers > 0 && (!cpc || (n_pods > 0 && (!req || !req_mask))))))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  return PAS_OK;
+}
+
+int pas_gas_apply_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
+                         const int32_t* d_ev_kind, const int32_t* d_ev_pod,
+                         const int32_t* d_ev_node, int32_t n_pods, int32_t max_containers,
+                         const int64_t* d_req, const uint32_t* d_req_mask,
+                         const int32_t* d_n_containers, const int32_t* d_cards_per_container,
+                         const int32_t* d_cards, int32_t cards_ld, int32_t* d_status_out,
+                         void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = gas_apply_check(ctx, gen_from, n_events, d_ev_kind, d_ev_pod, d_ev_node, n_pods,
+                           max_containers, d_req, d_req_mask, d_n_containers,
+                           d_cards_per_container, d_cards, cards_ld, d_status_out,
+                           "pas_gas_apply_device");
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  if ((rc = gas_apply_launch(ctx, n_events, d_ev_kind, d_ev_pod, d_ev_node, n_pods,
+                             max_containers, d_req, d_req_mask, d_n_containers,
+                             d_cards_per_container, d_cards, cards_ld, d_status_out,
+                             pick_stream(ctx, hip_stream))))
+    return rc;
+  ctx->gas.gen = gen_to;
+  ++ctx->gas.epoch;
+  return PAS_OK;
+}
+
+int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
+                  const int32_t* ev_kind, const int32_t* ev_pod, const int32_t* ev_node,
+                  int32_t n_pods, int32_t max_containers, const int64_t* req,
+                  const uint32_t* req_mask, const int32_t* n_containers,
+                  const int32_t* cards_per_container, const int32_t* cards, int32_t cards_ld,
+                  int32_t* status_out) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_gas_apply";
+  int rc = gas_apply_check(ctx, gen_from, n_events, ev_kind, ev_pod, ev_node, n_pods,
+                           max_containers, req, req_mask, n_containers, cards_per_container,
+                           cards, cards_ld, status_out, fn.c_str());
+  if (rc) return rc;
+  const int32_t Q = ctx->gas.n_res, N = ctx->gas.n_nodes;
+  for (int32_t e = 0; e < n_events; ++e) {
+    if (ev_kind[e] != PAS_GAS_EV_ADD && ev_kind[e] != PAS_GAS_EV_REMOVE)
+      return set_error(ctx, PAS_EINVAL, fn + ": event kind out of range");
+    if (ev_node[e] < 0 || ev_node[e] >= N || ev_pod[e] < 0 || ev_pod[e] >= n_pods)
+      return set_error(ctx, PAS_EINVAL, fn + ": node or pod index out of range");
+    const int32_t p = ev_pod[e];
+    if (n_containers[p] < 0 || n_containers[p] > max_containers)
+      return set_error(ctx, PAS_EINVAL, fn + ": n_containers out of range");
+    int64_t sel = 0;
+    for (int32_t c = 0; c < n_containers[p]; ++c) {
+      if ((req_mask[(int64_t)p * max_containers + c] & ~PAS_REQ_UNKNOWN_KIND) >> Q)
+        return set_error(ctx, PAS_EINVAL, fn + ": mask bit >= n_res");
+      const int64_t v = cards_per_container[(int64_t)e * max_containers + c];
+      if (v < 0) return set_error(ctx, PAS_EINVAL, fn + ": negative card count");
+      sel += v;  // at most max_containers * INT32_MAX
+    }
+    if (sel > cards_ld)
+      return set_error(ctx, PAS_EINVAL, fn + ": more than cards_ld cards for one pod");
+  }
+  if ((rc = activate(ctx))) return rc;
+  const size_t E = (size_t)n_events, P = (size_t)n_pods, C = (size_t)max_containers;
+  const size_t b_req = sizeof(int64_t) * P * C * Q, b_mask = sizeof(uint32_t) * P * C;
+  const size_t b_pod = sizeof(int32_t) * P, b_ev = sizeof(int32_t) * E;
+  const size_t b_cpc = sizeof(int32_t) * E * C, b_cards = sizeof(int32_t) * E * (size_t)cards_ld;
+  if ((rc = ensure_scratch(ctx, carve_size({b_req, b_mask, b_pod, b_ev, b_ev, b_ev, b_cpc,
+                                            b_cards, b_ev}))))
+    return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int64_t* d_req = cv.take<int64_t>(P * C * Q);
+  uint32_t* d_mask = cv.take<uint32_t>(P * C);
+  int32_t* d_nc = cv.take<int32_t>(P);
+  int32_t* d_kind = cv.take<int32_t>(E);
+  int32_t* d_pod = cv.take<int32_t>(E);
+  int32_t* d_node = cv.take<int32_t>(E);
+  int32_t* d_cpc = cv.take<int32_t>(E * C);
+  int32_t* d_cards = cv.take<int32_t>(E * (size_t)cards_ld);
+  int32_t* d_status = cv.take<int32_t>(E);
+  hipStream_t s = ctx->stream;
+  if (n_events > 0) {
+    if (b_req) {
+      PAS_HIP(ctx, hipMemcpyAsync(d_req, req, b_req, hipMemcpyHostToDevice, s));
+      PAS_HIP(ctx, hipMemcpyAsync(d_mask, req_mask, b_mask, hipMemcpyHostToDevice, s));
+    }
+    if (b_pod) PAS_HIP(ctx, hipMemcpyAsync(d_nc, n_containers, b_pod, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_kind, ev_kind, b_ev, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_pod, ev_pod, b_ev, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_node, ev_node, b_ev, hipMemcpyHostToDevice, s));
+    if (b_cpc)
+      PAS_HIP(ctx, hipMemcpyAsync(d_cpc, cards_per_container, b_cpc, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_cards, cards, b_cards, hipMemcpyHostToDevice, s));
+    // the _device form's path: grouping and commit on the device
+    if ((rc = gas_apply_launch(ctx, n_events, d_kind, d_pod, d_node, n_pods, max_containers,
+                               d_req, d_mask, d_nc, d_cpc, d_cards, cards_ld, d_status, s)))
+      return rc;
+    // the kernel is enqueued: a failure from here on leaves a snapshot of unknown content
+    const hipError_t e = [&] {
+      hipError_t r = hipMemcpyAsync(status_out, d_status, b_ev, hipMemcpyDeviceToHost, s);
+      if (r == hipSuccess) r = hipStreamSynchronize(s);
+      return r;
+    }();
+    if (e != hipSuccess) {
+      ctx->gas.valid = false;
+      return check_hip(ctx, e, "pas_gas_apply: copy of the statuses");
+    }
+  }
+  ctx->gas.gen = gen_to;
+  ++ctx->gas.epoch;
+  return PAS_OK;
+}
+
 // What pas_gas_place and pas_gas_place_device share: the checks a host can make on either
 // form's scalars and pointers.
 static int gas_place_check(pas_ctx* ctx, uint64_t gen_from, int32_t n_pods,

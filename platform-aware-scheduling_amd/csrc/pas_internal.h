@@ -190,7 +190,8 @@ enum SlotBuf {
   kBufMerge = 1,  // cut list and ping-pong rows of the full-list merge (tas_list_merge.hip)
   kBufLabel = 2,  // per-workgroup partial counts of the label plan (tas_labels.hip)
   kBufPlace = 3,  // cursors, keys, blockers and sort storage of a placement (gas_place.hip)
-  kSlotBufs = 4
+  kBufApply = 4,  // sort keys, event order and sort storage of an event batch (gas_commit.hip)
+  kSlotBufs = 5
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -399,6 +400,14 @@ int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_seg, int32_t max_con
                       const int32_t* d_cards, int32_t cards_stride, uint32_t* d_res,
                       int32_t* d_status, uint8_t* d_cards_out, int32_t* d_nsel_out,
                       int64_t* d_counts_out, const int64_t* d_counts, hipStream_t s);
+// Pod events (pas_gas_apply[_device]) on device arrays: grouped by node on the device (stable
+// radix sort, storage from the stream's slot) and applied in call order, all enqueued on s.
+// Nothing of the snapshot has changed when it returns an error.
+int gas_apply_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
+                     const int32_t* d_pod, const int32_t* d_node, int32_t n_pods,
+                     int32_t max_containers, const int64_t* d_req, const uint32_t* d_mask,
+                     const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
+                     int32_t cards_ld, int32_t* d_status, hipStream_t s);
 // Batch placement (gas_place.hip): the rounds of pas_gas_place_device on s, returning when the
 // placement is complete.  *began: commits were launched (an error past that point leaves
 // the resident usage half committed: the caller invalidates the snapshot).

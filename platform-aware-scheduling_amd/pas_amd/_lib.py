@@ -59,6 +59,8 @@ PAS_GAS_OK = 0
 PAS_GAS_WONT_FIT = 1
 PAS_GAS_ERR_INPUT = 2
 PAS_GAS_ERR_OVERFLOW = 3
+PAS_GAS_EV_ADD = 0
+PAS_GAS_EV_REMOVE = 1
 
 PAS_K_TAS_EVAL = 1
 PAS_K_TAS_VIOLATIONS = 2
@@ -213,6 +215,16 @@ SIGNATURES = {
     "pas_gas_release_ex": (
         c_int,
         [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P],
+    ),
+    "pas_gas_apply": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P,
+         c_int32, _P],
+    ),
+    "pas_gas_apply_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P,
+         c_int32, _P, _P],
     ),
     "pas_gas_snapshot_get": (c_int, [_P, POINTER(c_uint64), _P]),
     "pas_tas_topk_device": (

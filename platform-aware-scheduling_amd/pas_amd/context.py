@@ -617,6 +617,44 @@ class Context:
         self._check(rc, "pas_gas_release_counts")
         return st
 
+    def gas_apply(self, gen_from: int, gen_to: int, kinds, pods, nodes, req: np.ndarray,
+                  req_mask: np.ndarray, n_containers: np.ndarray, cards_per_container,
+                  cards) -> np.ndarray:
+        """Pod events in order (pas_gas_apply): kinds[e] is PAS_GAS_EV_ADD (adjustPodResources
+        (add) from the annotation: no fit, no capacity check) or PAS_GAS_EV_REMOVE
+        (pas_gas_release_ex) of pod pods[e] on node nodes[e].  cards_per_container is [E][C],
+        cards [E][cards_ld] with any row length cards_ld >= 1; returns statuses [E]."""
+        req = np.ascontiguousarray(req, dtype=np.int64)
+        p, c, q = req.shape
+        req_mask = np.ascontiguousarray(req_mask, dtype=np.uint32)
+        n_containers = np.ascontiguousarray(n_containers, dtype=np.int32)
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        pods = np.ascontiguousarray(pods, dtype=np.int32)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        e = len(kinds)
+        assert pods.shape == (e,) and nodes.shape == (e,)
+        cpc = np.ascontiguousarray(cards_per_container, dtype=np.int32).reshape(e, c)
+        cards = np.ascontiguousarray(cards, dtype=np.int32)
+        assert cards.ndim == 2 and cards.shape[0] == e, "cards is [E][cards_ld]"
+        st = np.zeros(e, np.int32)
+        rc = self._l.pas_gas_apply(self._h, gen_from, gen_to, e, _ptr(kinds), _ptr(pods),
+                                   _ptr(nodes), p, c, _ptr(req), _ptr(req_mask),
+                                   _ptr(n_containers), _ptr(cpc), _ptr(cards), cards.shape[1],
+                                   _ptr(st))
+        self._check(rc, "pas_gas_apply")
+        return st
+
+    def gas_apply_device(self, gen_from: int, gen_to: int, n_events: int, kinds_t, pods_t,
+                         nodes_t, n_pods: int, max_containers: int, req_t, mask_t, ncont_t,
+                         cpc_t, cards_t, cards_ld: int, status_t, stream=None):
+        """pas_gas_apply_device on device tensors: asynchronous on the stream, the statuses are
+        in status_t once the stream has run."""
+        rc = self._l.pas_gas_apply_device(
+            self._h, gen_from, gen_to, n_events, _dptr(kinds_t), _dptr(pods_t), _dptr(nodes_t),
+            n_pods, max_containers, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), _dptr(cpc_t),
+            _dptr(cards_t), cards_ld, _dptr(status_t), _stream(stream))
+        self._check(rc, "pas_gas_apply_device")
+
     def gas_snapshot_get(self):
         """(generation, used [N][K][Q]) of the resident GAS snapshot."""
         n, k, q = self.gas_shape

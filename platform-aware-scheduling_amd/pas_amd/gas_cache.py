@@ -1,0 +1,224 @@
+"""GasCache: the reference cache's pod event path over the device-resident GAS usage.
+
+The reference's Cache (gpu-aware-scheduling/pkg/gpuscheduler/node_resource_cache.go) learns
+about pods from an informer: addPodToCache / updatePodInCache / deletePodFromCache (:305-400)
+queue work items, and handlePod (:493-538) turns each into adjustPodResources(add / remove)
+straight from the pod's "gas-container-cards" annotation, keyed by its annotatedPods set.  That
+is how the usage stays true when pods are bound by another extender replica, by an earlier run,
+or are met in the informer's initial list.  Here the same decisions are made on the host and
+the arithmetic runs on the device: events queue up and flush() sends them as ordered
+pas_gas_apply batches, so the usage never leaves the device.
+"""
+import json
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .snapshot import parse_annotation
+
+CARD_ANNOTATION = "gas-container-cards"  # cardAnnotationName (scheduler.go)
+
+POD_ADDED, POD_UPDATED, POD_COMPLETED, POD_DELETED = "added", "updated", "completed", "deleted"
+
+# outcomes of one work item (handlePod's err, or why nothing was adjusted)
+OK = "ok"                # adjustPodResources succeeded (annotatedPods changed)
+SKIPPED = "skipped"      # "annotation already present" / "annotation already gone"
+BAD_ARGS = "bad_args"    # errBadArgs: segment count != container count, or no node name
+ERR_INPUT = "input"      # errInput (PAS_GAS_ERR_INPUT)
+ERR_OVERFLOW = "overflow"  # errOverflow (PAS_GAS_ERR_OVERFLOW)
+_STATUS = {_lib.PAS_GAS_OK: OK, _lib.PAS_GAS_ERR_INPUT: ERR_INPUT,
+           _lib.PAS_GAS_ERR_OVERFLOW: ERR_OVERFLOW}
+
+
+def pod_key(pod: dict) -> str:
+    """getKey (node_resource_cache.go:451-453): namespace & name."""
+    meta = pod.get("metadata") or {}
+    return (meta.get("namespace") or "") + "&" + (meta.get("name") or "")
+
+
+def is_completed_pod(pod: dict) -> bool:
+    """isCompletedPod (utils.go:52-71): a deletion timestamp, or phase Failed / Succeeded."""
+    if (pod.get("metadata") or {}).get("deletionTimestamp") is not None:
+        return True
+    return (pod.get("status") or {}).get("phase") in ("Failed", "Succeeded")
+
+
+def _annotation_of(pod: dict) -> Optional[str]:
+    return ((pod.get("metadata") or {}).get("annotations") or {}).get(CARD_ANNOTATION)
+
+
+class GasCache:
+    """The event path of the reference's Cache over a context's resident GAS snapshot.
+
+    `ctx` holds the snapshot of generation `gen` built by snapshot.gas_snapshot_from_nodes over
+    `node_names` with `card_names` and `kinds`; n_cards / cap are that snapshot's (rebuild
+    uploads them again with zero usage).  Pods are v1.Pod JSON objects.  `requests(pod)`
+    returns (req [C][Q] int64, req_mask [C] uint32, n_containers), containerRequests
+    (utils.go:14-32); the default decodes the pod through pas_decode_pod_requests.
+
+    add_pod / update_pod / delete_pod are the informer's handlers: they only queue.  flush()
+    handles the queue in order as handlePod does and returns [(key, action, outcome)] per
+    item.  Every decision reads annotatedPods as it stands when the item is handled, and
+    annotatedPods changes only when the adjustment succeeded, so one pas_gas_apply batch
+    holds at most one event per pod key: a second item for a key closes the batch, and its
+    decision is made once the first batch's statuses are known.  deletePodFromCache's own
+    look at annotatedPods (:384-391, taken when the informer calls, whatever the worker has
+    handled by then) is made at the same point, as if the worker had caught up.
+
+    A segment count that differs from the container count (or an empty node name) is
+    errBadArgs (:192-196): answered here, nothing is sent.  An annotation without cards adjusts
+    nothing and succeeds without a device call.  A node the snapshot does not hold has no
+    usage to adjust: the item succeeds without a device call, where the reference would keep
+    usage that no fit reads.
+
+    The podDeleted quirk is reproduced as it is: the reference's podDeleted item carries no
+    annotation (:393-399), so handlePod removes "".  strings.Split("", "|") is one empty
+    segment: a pod with one container gets a no-op and its key is forgotten; a pod with
+    several containers gets errBadArgs and its key stays.  Only podCompleted (an update of a
+    pod that isCompletedPod) releases usage.
+
+    note_bind(pod, annotation) records a pod this process bound itself: bindNode's
+    adjustPodResources(add) sets annotatedPods too, so the informer's later update for that
+    pod is skipped instead of being added twice."""
+
+    def __init__(self, ctx, gen: int, node_names: Sequence[str],
+                 card_names: Sequence[Sequence[str]], kinds: Sequence[str],
+                 n_cards=None, cap=None,
+                 requests: Optional[Callable[[dict], Tuple[np.ndarray, np.ndarray, int]]] = None):
+        self.ctx, self.gen = ctx, gen
+        self.node_index = {n: i for i, n in enumerate(node_names)}
+        self.card_names = card_names
+        self.kinds = list(kinds)
+        self.n_cards, self.cap = n_cards, cap
+        self._requests = requests if requests is not None else self._decode_requests
+        self.annotated: Dict[str, str] = {}  # annotatedPods
+        self._queue: List[Tuple[str, dict, str]] = []  # (action, pod, annotation)
+
+    def _decode_requests(self, pod: dict):
+        from . import wire
+        req, mask, ncont, _ = wire.decode_pod_requests(json.dumps(pod).encode(), self.kinds)
+        return req[0], mask[0], int(ncont[0])
+
+    # ------------------------------------------------------------ informer handlers
+    def add_pod(self, pod: dict):
+        """addPodToCache (:305-327): a pod without the annotation waits for its update."""
+        annotation = _annotation_of(pod)
+        if annotation is not None:
+            self._queue.append((POD_ADDED, pod, annotation))
+
+    def update_pod(self, old_pod: Optional[dict], new_pod: dict):
+        """updatePodInCache (:329-357): podUpdated, or podCompleted for a completed pod."""
+        annotation = _annotation_of(new_pod)
+        if annotation is not None:
+            action = POD_COMPLETED if is_completed_pod(new_pod) else POD_UPDATED
+            self._queue.append((action, new_pod, annotation))
+
+    def delete_pod(self, pod: dict):
+        """deletePodFromCache (:359-400): the item carries no annotation."""
+        self._queue.append((POD_DELETED, pod, ""))
+
+    def note_bind(self, pod: dict, annotation: str):
+        """A bind of this process (pas_gas_bind* / pas_gas_place*) already committed the
+        pod's usage: adjustPodResources(add) in bindNode sets annotatedPods[key]."""
+        self.annotated[pod_key(pod)] = annotation
+
+    # ------------------------------------------------------------ the worker
+    def _plan(self, action: str, pod: dict, annotation: str):
+        """handlePod's switch and adjustPodResources' argument check for one item: an outcome
+        answered on the host, or the device event (kind, node, req, mask, ncont, cpc, ranks)."""
+        key = pod_key(pod)
+        add = action in (POD_ADDED, POD_UPDATED)
+        if add == (key in self.annotated):  # already present / already gone
+            return SKIPPED
+        req, mask, ncont = self._requests(pod)
+        segments = annotation.split("|")
+        node_name = (pod.get("spec") or {}).get("nodeName") or ""
+        if len(segments) != ncont or node_name == "":
+            return BAD_ARGS
+        node = self.node_index.get(node_name)
+        names = self.card_names[node] if node is not None else []
+        cpc, ranks = parse_annotation(annotation, names)
+        if node is None or not ranks:
+            return OK
+        kind = _lib.PAS_GAS_EV_ADD if add else _lib.PAS_GAS_EV_REMOVE
+        return kind, node, req, mask, ncont, cpc, ranks
+
+    def _settle(self, key: str, action: str, annotation: str, outcome: str):
+        if outcome == OK:
+            if action in (POD_ADDED, POD_UPDATED):
+                self.annotated[key] = annotation
+            else:
+                self.annotated.pop(key, None)
+
+    def _send(self, batch) -> List[int]:
+        """One pas_gas_apply call for the batch's events, pod e = event e."""
+        e = len(batch)
+        q = len(self.kinds)
+        c = max(1, max(ev[4] for ev in batch))
+        ld = max(1, max(len(ev[6]) for ev in batch))
+        req = np.zeros((e, c, q), np.int64)
+        mask = np.zeros((e, c), np.uint32)
+        ncont = np.zeros(e, np.int32)
+        cpc = np.zeros((e, c), np.int32)
+        cards = np.full((e, ld), -1, np.int32)
+        kinds = np.zeros(e, np.int32)
+        nodes = np.zeros(e, np.int32)
+        for i, (kind, node, r, m, nc, pc, ranks) in enumerate(batch):
+            kinds[i], nodes[i], ncont[i] = kind, node, nc
+            req[i, :nc] = np.asarray(r, np.int64).reshape(-1, q)[:nc]
+            mask[i, :nc] = np.asarray(m, np.uint32)[:nc]
+            cpc[i, :nc] = pc
+            cards[i, :len(ranks)] = ranks
+        st = self.ctx.gas_apply(self.gen, self.gen + 1, kinds, np.arange(e, dtype=np.int32),
+                                nodes, req, mask, ncont, cpc, cards)
+        self.gen += 1
+        return [int(s) for s in st]
+
+    def flush(self) -> List[Tuple[str, str, str]]:
+        """Handle the queued items in order; [(key, action, outcome)] per item."""
+        queue, self._queue = self._queue, []
+        results: List[Optional[Tuple[str, str, str]]] = [None] * len(queue)
+        batch, slots, keys = [], [], set()
+
+        def close():
+            if batch:
+                for (i, key, action, annotation), s in zip(slots, self._send(batch)):
+                    outcome = _STATUS.get(s, ERR_INPUT)
+                    self._settle(key, action, annotation, outcome)
+                    results[i] = (key, action, outcome)
+            batch.clear()
+            slots.clear()
+            keys.clear()
+
+        for i, (action, pod, annotation) in enumerate(queue):
+            key = pod_key(pod)
+            if key in keys:  # its decision needs the first event's status
+                close()
+            plan = self._plan(action, pod, annotation)
+            if isinstance(plan, str):
+                self._settle(key, action, annotation, plan)
+                results[i] = (key, action, plan)
+                continue
+            batch.append(plan)
+            slots.append((i, key, action, annotation))
+            keys.add(key)
+        close()
+        return results  # type: ignore[return-value]
+
+    def rebuild(self, pods: Sequence[dict]) -> List[Tuple[str, str, str]]:
+        """The cold start: zero usage, then every annotated pod as the informer's initial
+        list delivers it (addPodToCache each, so one ADD batch unless a key repeats)."""
+        if self.n_cards is None or self.cap is None:
+            raise ValueError("rebuild needs the snapshot's n_cards and cap")
+        n_cards = np.ascontiguousarray(self.n_cards, np.int32)
+        cap = np.ascontiguousarray(self.cap, np.int64)
+        k = max([1] + [len(c) for c in self.card_names])
+        self.gen += 1
+        self.ctx.gas_snapshot_set(self.gen, n_cards, cap,
+                                  np.zeros((len(n_cards), k, len(self.kinds)), np.int64))
+        self.annotated.clear()
+        self._queue = []
+        for pod in pods:
+            self.add_pod(pod)
+        return self.flush()

@@ -186,3 +186,20 @@ def annotation_counts(counts, n_containers: int, card_names: Sequence[str]) -> s
         out.append(",".join(card_names[k] for k in range(len(card_names))
                             for _ in range(int(counts[c][k]))))
     return "|".join(out)
+
+
+def parse_annotation(annotation: str, card_names: Sequence[str]):
+    """The inverse of annotation(): (cards_per_container, ranks) of a "gas-container-cards"
+    value as adjustPodResources reads it (node_resource_cache.go:241,253-256): strings.Split
+    on "|" gives the containers' segments (one for "", as Go's Split does), strings.Split on
+    "," a segment's card names.  An empty segment is 0 cards.  ranks lists the containers'
+    cards consecutively as ranks into card_names (the node's label cards in rank order); a
+    name not in card_names, the "" inside "a,,b" included, is rank -1 and still counts towards
+    its container's numCards."""
+    rank = {name: r for r, name in enumerate(card_names)}
+    cards_per_container, ranks = [], []
+    for segment in annotation.split("|"):
+        names = segment.split(",") if segment else []
+        cards_per_container.append(len(names))
+        ranks.extend(rank.get(name, -1) for name in names)
+    return cards_per_container, ranks
