@@ -391,7 +391,17 @@ typedef struct pas_gas_selection {
  *                                       cards in the usage map but not in the label are
  *                                       left out (skipped at :230-234)
  * max_cards <= PAS_GAS_MAX_CARDS (64), n_res <= PAS_GAS_MAX_RES.  The host form rejects
- * n_cards[n] > max_cards (PAS_EINVAL); the _device form stores such a count as max_cards. */
+ * n_cards[n] > max_cards (PAS_EINVAL); the _device form stores such a count as max_cards.
+ *
+ * Parked card slots.  A node's row used[n][0 .. max_cards) holds its label cards in slots
+ * [0, n_cards[n]); the slots at and past n_cards[n] (all of them for n_cards[n] <= 0) are
+ * parked: no fit, bind, placement, release or event reads or changes them (a card rank >=
+ * n_cards[n] is "a card the label does not list": PAS_GAS_EV_ADD skips it, PAS_GAS_EV_REMOVE
+ * and the releases report PAS_GAS_ERR_INPUT).  They may carry the usage of cards the label
+ * does not list at the moment, as the reference's nodeStatuses keeps it by card name
+ * (node_resource_cache.go:259-272): pas_gas_snapshot_set[_device] stores them as given,
+ * pas_gas_snapshot_get returns them, and only pas_gas_nodes_update[_device] and
+ * pas_gas_snapshot_resize move them.  Parked usage therefore changes only by being moved. */
 int pas_gas_snapshot_set(pas_ctx* ctx, uint64_t gen, int32_t n_nodes, int32_t max_cards,
                          int32_t n_res, const int32_t* n_cards, const int64_t* cap_per_gpu,
                          const int64_t* used);
@@ -670,6 +680,65 @@ int pas_gas_apply_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
 
 /* Read back the resident usage used[N][K][Q] and its generation. */
 int pas_gas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* used_out);
+/* Read back the resident n_cards [N] and cap_per_gpu [N][Q] and the generation. */
+int pas_gas_snapshot_get_nodes(pas_ctx* ctx, uint64_t* gen, int32_t* n_cards_out /*[N]*/,
+                               int64_t* cap_out /*[N][Q]*/);
+/* Generation and shape of the resident GAS snapshot (PAS_ENOSNAP without one); any output may
+ * be NULL. */
+int pas_gas_snapshot_info(const pas_ctx* ctx, uint64_t* gen, int32_t* n_nodes,
+                          int32_t* max_cards, int32_t* n_res);
+
+/* Node events on the resident GAS snapshot, applied in call order.  The reference fetches the
+ * node from the lister on every fit (scheduler.go:282-300), so a changed label or allocatable
+ * is seen by the next request, and it keeps the usage by node and card name for ever
+ * (node_resource_cache.go:64,259-272,474-491).  Here update u rewrites node slot upd_node[u]:
+ *   n_cards[n]  = upd_n_cards[u]   -1 node not in the lister (FetchNode error, :282-288),
+ *                                   0 label missing (:290-298), 1..max_cards label cards
+ *   cap[n][q]   = upd_cap[u][q]    any int64 (AsInt64(allocatable) / len(label split))
+ *   used[n][k]  = old used[n][upd_src[u][k]] for every kind when 0 <= upd_src[u][k] < max_cards,
+ *                 zeros otherwise (a card first seen: addEmptyResourceMaps, :269-275)
+ * for all k in [0, max_cards): label cards first, in sort.Strings order, then the parked cards
+ * (see pas_gas_snapshot_set).  The whole old row is read before any slot is written (upd_src
+ * may be any permutation).  Several updates of one node see each other in call order: upd_src
+ * of a later one indexes the row the earlier one left.  Updates of different nodes are
+ * independent.  status_out[u] = PAS_GAS_OK, or PAS_GAS_ERR_INPUT and that update changes
+ * nothing.  gen_from is checked (PAS_ESTALE, nothing changed); the snapshot moves to gen_to.
+ *
+ * The host form validates, PAS_EINVAL for: a node outside [0, n_nodes), n_cards outside
+ * [-1, max_cards], a src >= max_cards, a non-negative src repeated within one row (one card's
+ * usage must not be duplicated).  It uploads, runs the _device form's path, waits and copies
+ * status_out back; a HIP failure after the kernel was enqueued returns PAS_EDEVICE and leaves
+ * the GAS snapshot invalid (PAS_ENOSNAP until the next pas_gas_snapshot_set), as pas_gas_apply.
+ * The _device form takes device pointers, is asynchronous on hip_stream and moves the
+ * generation once the kernel is enqueued (its sort storage is per stream and allocated when a
+ * larger batch first needs it).  It cannot validate the arrays: an update whose node is out of
+ * range or whose n_cards is outside [-1, max_cards] gets PAS_GAS_ERR_INPUT and changes nothing;
+ * a src outside [0, max_cards) reads as "zero usage"; a repeated src copies twice (a caller
+ * bug, but no memory outside the row is touched); nothing outside the resident arrays and the
+ * call's arrays is read or written.  The next fit derives its per-snapshot values again.  As
+ * for every snapshot change, the caller orders the call after readers on other streams. */
+int pas_gas_nodes_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_updates,
+                         const int32_t* upd_node, const int32_t* upd_n_cards,
+                         const int64_t* upd_cap /*[n_updates][n_res]*/,
+                         const int32_t* upd_src /*[n_updates][max_cards]*/,
+                         int32_t* status_out /*[n_updates]*/);
+int pas_gas_nodes_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                int32_t n_updates, const int32_t* d_upd_node,
+                                const int32_t* d_upd_n_cards, const int64_t* d_upd_cap,
+                                const int32_t* d_upd_src, int32_t* d_status_out,
+                                void* hip_stream);
+
+/* Grow the resident snapshot in place: n_nodes_new >= n_nodes and max_cards_new >= max_cards,
+ * PAS_EINVAL for a smaller value (PAS_ECAPACITY past PAS_GAS_MAX_CARDS).  Content is kept (the
+ * rows are re-pitched on the device, no host copy); new node slots have n_cards -1, cap 0 and
+ * usage 0; new card slots are zero.  gen_from is checked (PAS_ESTALE) and the snapshot moves
+ * to gen_to.  Synchronous on hip_stream: the old storage is freed after the copy kernel has
+ * finished.  When the new storage cannot be allocated the old snapshot stays valid and
+ * untouched (PAS_ENOMEM).  pas_tas_gas_topk*_device still needs both snapshots to hold the
+ * same number of nodes: a caller that grows the GAS snapshot sets its next TAS snapshot with
+ * the same number of slots (spare slots: no present bit). */
+int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                            int32_t n_nodes_new, int32_t max_cards_new, void* hip_stream);
 
 /* ------------------------------------------------------------------------- */
 /* Node-sharded snapshots                                  */

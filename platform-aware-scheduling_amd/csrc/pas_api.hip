@@ -1340,6 +1340,182 @@ int pas_gas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* used_out) {
   return PAS_OK;
 }
 
+int pas_gas_snapshot_info(const pas_ctx* ctx, uint64_t* gen, int32_t* n_nodes, int32_t* max_cards,
+                          int32_t* n_res) {
+  if (!ctx) return PAS_EINVAL;
+  if (!ctx->gas.valid) return PAS_ENOSNAP;
+  if (gen) *gen = ctx->gas.gen;
+  if (n_nodes) *n_nodes = ctx->gas.n_nodes;
+  if (max_cards) *max_cards = ctx->gas.max_cards;
+  if (n_res) *n_res = ctx->gas.n_res;
+  return PAS_OK;
+}
+
+int pas_gas_snapshot_get_nodes(pas_ctx* ctx, uint64_t* gen, int32_t* n_cards_out,
+                               int64_t* cap_out) {
+  if (!ctx) return PAS_EINVAL;
+  if (!ctx->gas.valid) return set_error(ctx, PAS_ENOSNAP, "no GAS snapshot uploaded");
+  const GasSnapshot& g = ctx->gas;
+  const size_t N = (size_t)g.n_nodes;
+  if (N && (!n_cards_out || !cap_out))
+    return set_error(ctx, PAS_EINVAL, "pas_gas_snapshot_get_nodes: null output");
+  int rc = activate(ctx);
+  if (rc) return rc;
+  if (N) {
+    PAS_HIP(ctx, hipMemcpyAsync(n_cards_out, g.n_cards, sizeof(int32_t) * N,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    PAS_HIP(ctx, hipMemcpyAsync(cap_out, g.cap, sizeof(int64_t) * N * g.n_res,
+                                hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PAS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (gen) *gen = g.gen;
+  return PAS_OK;
+}
+
+// What pas_gas_nodes_update and pas_gas_nodes_update_device share: the checks a host can make
+// on either form's scalars and pointers.
+static int gas_nodes_check(pas_ctx* ctx, uint64_t gen_from, int32_t n_updates,
+                           const void* upd_node, const void* upd_n_cards, const void* upd_cap,
+                           const void* upd_src, const void* status_out, const char* fn) {
+  int rc = check_gas_gen(ctx, gen_from);
+  if (rc) return rc;
+  if (n_updates < 0) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  if (n_updates > 0 && (!upd_node || !upd_n_cards || !upd_cap || !upd_src || !status_out))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  return PAS_OK;
+}
+
+int pas_gas_nodes_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                int32_t n_updates, const int32_t* d_upd_node,
+                                const int32_t* d_upd_n_cards, const int64_t* d_upd_cap,
+                                const int32_t* d_upd_src, int32_t* d_status_out,
+                                void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = gas_nodes_check(ctx, gen_from, n_updates, d_upd_node, d_upd_n_cards, d_upd_cap,
+                           d_upd_src, d_status_out, "pas_gas_nodes_update_device");
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  if ((rc = gas_nodes_update_launch(ctx, n_updates, d_upd_node, d_upd_n_cards, d_upd_cap,
+                                    d_upd_src, d_status_out, pick_stream(ctx, hip_stream))))
+    return rc;
+  ctx->gas.gen = gen_to;
+  ++ctx->gas.epoch;
+  return PAS_OK;
+}
+
+int pas_gas_nodes_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_updates,
+                         const int32_t* upd_node, const int32_t* upd_n_cards,
+                         const int64_t* upd_cap, const int32_t* upd_src, int32_t* status_out) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_gas_nodes_update";
+  int rc = gas_nodes_check(ctx, gen_from, n_updates, upd_node, upd_n_cards, upd_cap, upd_src,
+                           status_out, fn.c_str());
+  if (rc) return rc;
+  const int32_t N = ctx->gas.n_nodes, K = ctx->gas.max_cards, Q = ctx->gas.n_res;
+  for (int32_t u = 0; u < n_updates; ++u) {
+    if (upd_node[u] < 0 || upd_node[u] >= N)
+      return set_error(ctx, PAS_EINVAL, fn + ": node index out of range");
+    if (upd_n_cards[u] < -1 || upd_n_cards[u] > K)
+      return set_error(ctx, PAS_EINVAL, fn + ": n_cards outside [-1, max_cards]");
+    uint64_t seen = 0;  // K <= 64 source slots
+    for (int32_t k = 0; k < K; ++k) {
+      const int32_t s = upd_src[(int64_t)u * K + k];
+      if (s < 0) continue;
+      if (s >= K) return set_error(ctx, PAS_EINVAL, fn + ": src >= max_cards");
+      if (seen >> s & 1) return set_error(ctx, PAS_EINVAL, fn + ": a src slot repeats in a row");
+      seen |= uint64_t(1) << s;
+    }
+  }
+  if ((rc = activate(ctx))) return rc;
+  const size_t U = (size_t)n_updates;
+  const size_t b_u = sizeof(int32_t) * U, b_cap = sizeof(int64_t) * U * Q;
+  const size_t b_src = sizeof(int32_t) * U * K;
+  if ((rc = ensure_scratch(ctx, carve_size({b_u, b_u, b_cap, b_src, b_u})))) return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int32_t* d_node = cv.take<int32_t>(U);
+  int32_t* d_nc = cv.take<int32_t>(U);
+  int64_t* d_cap = cv.take<int64_t>(U * Q);
+  int32_t* d_src = cv.take<int32_t>(U * K);
+  int32_t* d_status = cv.take<int32_t>(U);
+  hipStream_t s = ctx->stream;
+  if (n_updates > 0) {
+    PAS_HIP(ctx, hipMemcpyAsync(d_node, upd_node, b_u, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_nc, upd_n_cards, b_u, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_cap, upd_cap, b_cap, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_src, upd_src, b_src, hipMemcpyHostToDevice, s));
+    // the _device form's path: grouping and the rows' rewrite on the device
+    if ((rc = gas_nodes_update_launch(ctx, n_updates, d_node, d_nc, d_cap, d_src, d_status, s)))
+      return rc;
+    // the kernel is enqueued: a failure from here on leaves a snapshot of unknown content
+    const hipError_t e = [&] {
+      hipError_t r = hipMemcpyAsync(status_out, d_status, b_u, hipMemcpyDeviceToHost, s);
+      if (r == hipSuccess) r = hipStreamSynchronize(s);
+      return r;
+    }();
+    if (e != hipSuccess) {
+      ctx->gas.valid = false;
+      return check_hip(ctx, e, "pas_gas_nodes_update: copy of the statuses");
+    }
+  }
+  ctx->gas.gen = gen_to;
+  ++ctx->gas.epoch;
+  return PAS_OK;
+}
+
+int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                            int32_t n_nodes_new, int32_t max_cards_new, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_gas_gen(ctx, gen_from);
+  if (rc) return rc;
+  GasSnapshot& g = ctx->gas;
+  if (n_nodes_new < g.n_nodes || max_cards_new < g.max_cards)
+    return set_error(ctx, PAS_EINVAL, "pas_gas_snapshot_resize: the snapshot only grows");
+  if (max_cards_new > PAS_GAS_MAX_CARDS)
+    return set_error(ctx, PAS_ECAPACITY, "pas_gas_snapshot_resize: max_cards <= 64 supported");
+  if (n_nodes_new == g.n_nodes && max_cards_new == g.max_cards) {
+    g.gen = gen_to;
+    return PAS_OK;
+  }
+  if ((rc = activate(ctx))) return rc;
+  hipStream_t s = pick_stream(ctx, hip_stream);
+  const size_t nn = (size_t)std::max(n_nodes_new, 1), Q = (size_t)g.n_res;
+  int32_t* n_cards = nullptr;
+  int64_t *cap = nullptr, *used = nullptr;
+  void *derived = nullptr, *free_t = nullptr;
+  hipError_t e = hipMalloc(&n_cards, sizeof(int32_t) * nn);
+  if (e == hipSuccess) e = hipMalloc(&cap, sizeof(int64_t) * nn * Q);
+  if (e == hipSuccess) e = hipMalloc(&used, sizeof(int64_t) * nn * (size_t)max_cards_new * Q);
+  if (e == hipSuccess) e = hipMalloc(&derived, 64 + sizeof(int32_t) * nn);
+  if (e == hipSuccess) e = hipMalloc(&free_t, sizeof(int64_t) * PAS_GAS_PACKED * Q * nn);
+  if (e == hipSuccess) {
+    rc = gas_repitch_launch(ctx, n_nodes_new, max_cards_new, n_cards, cap, used, s);
+    // the old storage is freed below: its readers (the copy, and earlier calls of the host
+    // forms on the context's stream) have finished by then
+    if (!rc) e = hipStreamSynchronize(s);
+    if (!rc && e == hipSuccess && s != ctx->stream) e = hipStreamSynchronize(ctx->stream);
+  }
+  if (rc || e != hipSuccess) {  // the resident snapshot was only read: it stays as it is
+    for (void* p : {(void*)n_cards, (void*)cap, (void*)used, derived, free_t})
+      if (p) (void)hipFree(p);
+    return rc ? rc : check_hip(ctx, e, "pas_gas_snapshot_resize");
+  }
+  free_ptr(reinterpret_cast<void*&>(g.n_cards));
+  free_ptr(reinterpret_cast<void*&>(g.cap));
+  free_ptr(reinterpret_cast<void*&>(g.used));
+  free_ptr(g.derived);
+  free_ptr(g.free_t);
+  g.n_cards = n_cards;
+  g.cap = cap;
+  g.used = used;
+  g.derived = derived;
+  g.free_t = free_t;
+  g.n_nodes = n_nodes_new;
+  g.max_cards = max_cards_new;
+  g.gen = gen_to;
+  ++g.epoch;  // the next fit derives its values again, into the new storage
+  return PAS_OK;
+}
+
 // Host path of pas_gas_fit / pas_gas_fit_ex: validates, uploads the batch, runs the fit and
 // copies the words (and side records) back.
 static int gas_fit_host(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_t max_containers,

@@ -191,7 +191,8 @@ enum SlotBuf {
   kBufLabel = 2,  // per-workgroup partial counts of the label plan (tas_labels.hip)
   kBufPlace = 3,  // cursors, keys, blockers and sort storage of a placement (gas_place.hip)
   kBufApply = 4,  // sort keys, event order and sort storage of an event batch (gas_commit.hip)
-  kSlotBufs = 5
+  kBufNodes = 5,  // the same of a batch of node updates (gas_nodes.hip)
+  kSlotBufs = 6
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -408,6 +409,17 @@ int gas_apply_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
                      int32_t max_containers, const int64_t* d_req, const uint32_t* d_mask,
                      const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
                      int32_t cards_ld, int32_t* d_status, hipStream_t s);
+// Node updates (pas_gas_nodes_update[_device], gas_nodes.hip) on device arrays: grouped by node
+// on the device and applied in call order, all enqueued on s.  Nothing of the snapshot has
+// changed when it returns an error.
+int gas_nodes_update_launch(pas_ctx* ctx, int32_t n_updates, const int32_t* d_node,
+                            const int32_t* d_n_cards, const int64_t* d_cap,
+                            const int32_t* d_src, int32_t* d_status, hipStream_t s);
+// The resident n_cards / cap / used copied into storage of n_nodes_new x max_cards_new (both
+// >= the resident shape), new nodes -1 / 0 / 0 and new card slots 0; reads the snapshot only.
+int gas_repitch_launch(pas_ctx* ctx, int32_t n_nodes_new, int32_t max_cards_new,
+                       int32_t* d_n_cards_new, int64_t* d_cap_new, int64_t* d_used_new,
+                       hipStream_t s);
 // Batch placement (gas_place.hip): the rounds of pas_gas_place_device on s, returning when the
 // placement is complete.  *began: commits were launched (an error past that point leaves
 // the resident usage half committed: the caller invalidates the snapshot).

@@ -664,6 +664,59 @@ class Context:
                     "pas_gas_snapshot_get")
         return g.value, used
 
+    def gas_snapshot_info(self):
+        """(generation, n_nodes, max_cards, n_res) of the resident GAS snapshot."""
+        g, n, k, q = c_uint64(), c_int32(), c_int32(), c_int32()
+        self._check(self._l.pas_gas_snapshot_info(self._h, byref(g), byref(n), byref(k),
+                                                  byref(q)), "pas_gas_snapshot_info")
+        return g.value, n.value, k.value, q.value
+
+    def gas_snapshot_get_nodes(self):
+        """(generation, n_cards [N], cap [N][Q]) of the resident GAS snapshot."""
+        n, _, q = self.gas_shape
+        n_cards = np.zeros(n, np.int32)
+        cap = np.zeros((n, q), np.int64)
+        g = c_uint64()
+        self._check(self._l.pas_gas_snapshot_get_nodes(self._h, byref(g), _ptr(n_cards),
+                                                       _ptr(cap)), "pas_gas_snapshot_get_nodes")
+        return g.value, n_cards, cap
+
+    def gas_nodes_update(self, gen_from: int, gen_to: int, nodes, n_cards, cap, src) -> np.ndarray:
+        """Node events in order (pas_gas_nodes_update): update u gives node slot nodes[u] the
+        card count n_cards[u], the capacities cap[u] [Q] and the usage row gathered through
+        src[u] [max_cards] (slot k takes the old slot src[u][k], zeros for a negative one);
+        returns statuses [U]."""
+        n, k, q = self.gas_shape
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        u = len(nodes)
+        n_cards = np.ascontiguousarray(n_cards, dtype=np.int32)
+        cap = np.ascontiguousarray(cap, dtype=np.int64).reshape(u, q)
+        src = np.ascontiguousarray(src, dtype=np.int32).reshape(u, k)
+        assert n_cards.shape == (u,)
+        st = np.zeros(u, np.int32)
+        rc = self._l.pas_gas_nodes_update(self._h, gen_from, gen_to, u, _ptr(nodes),
+                                          _ptr(n_cards), _ptr(cap), _ptr(src), _ptr(st))
+        self._check(rc, "pas_gas_nodes_update")
+        return st
+
+    def gas_nodes_update_device(self, gen_from: int, gen_to: int, n_updates: int, nodes_t,
+                                n_cards_t, cap_t, src_t, status_t, stream=None):
+        """pas_gas_nodes_update_device on device tensors: asynchronous on the stream, the
+        statuses are in status_t once the stream has run."""
+        rc = self._l.pas_gas_nodes_update_device(
+            self._h, gen_from, gen_to, n_updates, _dptr(nodes_t), _dptr(n_cards_t),
+            _dptr(cap_t), _dptr(src_t), _dptr(status_t), _stream(stream))
+        self._check(rc, "pas_gas_nodes_update_device")
+
+    def gas_snapshot_resize(self, gen_from: int, gen_to: int, n_nodes: int, max_cards: int,
+                            stream=None):
+        """Grow the resident GAS snapshot on the device (pas_gas_snapshot_resize); gas_shape
+        follows."""
+        self._check(self._l.pas_gas_snapshot_resize(self._h, gen_from, gen_to, n_nodes,
+                                                    max_cards, _stream(stream)),
+                    "pas_gas_snapshot_resize")
+        self.gas_shape = (n_nodes, max_cards, self.gas_shape[2])
+
     def gas_fit_device(self, gen: int, n_pods: int, max_containers: int, i915_index: int, req_t,
                        mask_t, ncont_t, res_t, stream=None):
         rc = self._l.pas_gas_fit_device(self._h, gen, n_pods, max_containers, i915_index,

@@ -224,6 +224,16 @@ class GASExtender:
         self.pods = pods if pods is not None else {}
         self.i915 = self.kinds.index(I915) if I915 in self.kinds else -1
 
+    def nodes_changed(self, node_names: Sequence[Optional[str]]):
+        """The snapshot's slots after node events (GasCache.node_names: slot -> name, None for
+        a spare slot): node_index and the decode's name table follow.  card_names is shared
+        with the cache by reference and has changed in place already."""
+        self.node_names = [n if n is not None else "" for n in node_names]
+        self.node_index = {n: i for i, n in enumerate(node_names) if n is not None}
+        # a spare slot is listed as "": a request naming "" meets n_cards -1, which fits nothing,
+        # as the FetchNode error of an unknown node
+        self.name_table = wire.NameTable(self.node_names)
+
     def _requests(self, pod_json: bytes):
         """containerRequests (utils.go:14-32) through pas_decode_pod_requests: gpu.intel.com/
         requests as AsInt64 (ok ignored) in the pas_gas_fit layout, plus each container's

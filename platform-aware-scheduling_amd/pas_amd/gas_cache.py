@@ -15,11 +15,14 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .snapshot import parse_annotation
+from .snapshot import card_remap, gas_node_row, parse_annotation
 
 CARD_ANNOTATION = "gas-container-cards"  # cardAnnotationName (scheduler.go)
 
 POD_ADDED, POD_UPDATED, POD_COMPLETED, POD_DELETED = "added", "updated", "completed", "deleted"
+NODE_ADDED, NODE_UPDATED, NODE_DELETED = "node_added", "node_updated", "node_deleted"
+_NODE_ACTIONS = (NODE_ADDED, NODE_UPDATED, NODE_DELETED)
+CARD_TIERS = (8, 16, _lib.PAS_GAS_MAX_CARDS)  # the kernels' max_cards tiers
 
 # outcomes of one work item (handlePod's err, or why nothing was adjusted)
 OK = "ok"                # adjustPodResources succeeded (annotatedPods changed)
@@ -46,6 +49,25 @@ def is_completed_pod(pod: dict) -> bool:
 
 def _annotation_of(pod: dict) -> Optional[str]:
     return ((pod.get("metadata") or {}).get("annotations") or {}).get(CARD_ANNOTATION)
+
+
+def _node_name(node: dict) -> str:
+    return (node.get("metadata") or {}).get("name") or ""
+
+
+def _node_dict(node: dict) -> dict:
+    """A v1.Node object as snapshot.gas_node_row reads a node."""
+    return {"labels": (node.get("metadata") or {}).get("labels") or {},
+            "allocatable": (node.get("status") or {}).get("allocatable") or {}}
+
+
+def _tier(cards: int) -> int:
+    """The smallest max_cards tier that holds `cards` label cards."""
+    for t in CARD_TIERS:
+        if cards <= t:
+            return t
+    raise _lib.PasError(_lib.PAS_ECAPACITY,
+                        f"{cards} cards > {_lib.PAS_GAS_MAX_CARDS} (PAS_GAS_MAX_CARDS)")
 
 
 class GasCache:
@@ -80,20 +102,64 @@ class GasCache:
 
     note_bind(pod, annotation) records a pod this process bound itself: bindNode's
     adjustPodResources(add) sets annotatedPods too, so the informer's later update for that
-    pod is skipped instead of being added twice."""
+    pod is skipped instead of being added twice.
+
+    Node events.  add_node / update_node / delete_node take v1.Node JSON objects
+    (metadata.name, metadata.labels, status.allocatable) and queue into the same queue, and
+    flush() keeps the informer's order: a node item closes the open pod batch, consecutive
+    node items go out as one pas_gas_nodes_update batch (one node may repeat in it), and pod
+    items after a node item compute their card ranks from the card names as of that point.
+    A node item reports (name, action, OK) or "dropped: card, ..." for parked cards lost.
+
+    Slots are stable.  node_names[slot] is the slot's name, None for a spare slot
+    (n_cards -1).  card_names[slot] lists the label cards in rank order and parked[slot] the
+    parked cards behind them (snapshot.card_remap): a card that leaves the label keeps its
+    usage in a parked slot and has it again when the label lists it again, as the reference's
+    nodeStatuses keeps it by card name.  A deleted node keeps its slot and name with n_cards
+    -1 and every card parked, so its usage is there when the name returns; a new name takes a
+    spare slot.  The snapshot grows on the device (pas_gas_snapshot_resize) when no spare slot
+    is left, by max(64, N / 8) slots rounded up to 64, and when a label lists more cards than
+    max_cards, to the next of 8 / 16 / 64; parking never grows it.  card_names is changed in
+    place (a GASExtender sharing the list sees the changes; GASExtender.nodes_changed takes
+    the new node_names)."""
 
     def __init__(self, ctx, gen: int, node_names: Sequence[str],
                  card_names: Sequence[Sequence[str]], kinds: Sequence[str],
                  n_cards=None, cap=None,
                  requests: Optional[Callable[[dict], Tuple[np.ndarray, np.ndarray, int]]] = None):
         self.ctx, self.gen = ctx, gen
-        self.node_index = {n: i for i, n in enumerate(node_names)}
+        self.node_names: List[Optional[str]] = list(node_names)
+        self.node_index = {n: i for i, n in enumerate(node_names) if n is not None}
         self.card_names = card_names
+        self.parked: List[List[str]] = [[] for _ in self.node_names]
+        self.max_cards: Optional[int] = None  # resolved by the first node event (_k)
         self.kinds = list(kinds)
         self.n_cards, self.cap = n_cards, cap
+        self._rows_owned = False  # n_cards / cap are copies this cache may write
         self._requests = requests if requests is not None else self._decode_requests
         self.annotated: Dict[str, str] = {}  # annotatedPods
-        self._queue: List[Tuple[str, dict, str]] = []  # (action, pod, annotation)
+        self._queue: List[Tuple[str, dict, str]] = []  # (action, pod or node, annotation)
+
+    @classmethod
+    def from_nodes(cls, ctx, gen: int, nodes: Sequence[dict], kinds: Sequence[str],
+                   spare_nodes: int = 0, **kw) -> "GasCache":
+        """A cache over a fresh snapshot of the v1.Node objects `nodes` (zero usage) plus
+        spare_nodes spare slots, uploaded as generation gen; max_cards is the smallest of
+        8 / 16 / 64 that holds the largest label."""
+        rows = [gas_node_row(_node_dict(node), kinds) for node in nodes]
+        names: List[Optional[str]] = [_node_name(node) for node in nodes]
+        n, q = len(rows) + int(spare_nodes), len(kinds)
+        k = _tier(max([1] + [len(cards) for _, _, cards in rows]))
+        n_cards = np.full(n, -1, np.int32)
+        cap = np.zeros((n, q), np.int64)
+        for i, (nc, c, _) in enumerate(rows):
+            n_cards[i], cap[i] = nc, c
+        card_names = [cards for _, _, cards in rows] + [[] for _ in range(int(spare_nodes))]
+        ctx.gas_snapshot_set(gen, n_cards, cap, np.zeros((n, k, q), np.int64))
+        self = cls(ctx, gen, names + [None] * int(spare_nodes), card_names, kinds,
+                   n_cards=n_cards, cap=cap, **kw)
+        self.max_cards = k
+        return self
 
     def _decode_requests(self, pod: dict):
         from . import wire
@@ -122,6 +188,96 @@ class GasCache:
         """A bind of this process (pas_gas_bind* / pas_gas_place*) already committed the
         pod's usage: adjustPodResources(add) in bindNode sets annotatedPods[key]."""
         self.annotated[pod_key(pod)] = annotation
+
+    def add_node(self, node: dict):
+        """A node the lister now knows (or knows again)."""
+        self._queue.append((NODE_ADDED, node, ""))
+
+    def update_node(self, old_node: Optional[dict], new_node: dict):
+        """A changed node: its cards label or its allocatable."""
+        self._queue.append((NODE_UPDATED, new_node, ""))
+
+    def delete_node(self, node: dict):
+        """A node the lister no longer knows: every fit on it is the FetchNode error."""
+        self._queue.append((NODE_DELETED, node, ""))
+
+    # ------------------------------------------------------------ node items
+    def _k(self) -> int:
+        """max_cards of the resident snapshot."""
+        if self.max_cards is None:
+            shape = getattr(self.ctx, "gas_shape", None)
+            self.max_cards = int(shape[1]) if shape and shape[1] else \
+                max([1] + [len(c) for c in self.card_names])
+        return self.max_cards
+
+    def _grow(self, n_nodes: int, max_cards: int):
+        """pas_gas_snapshot_resize, and the host tables with it."""
+        self.ctx.gas_snapshot_resize(self.gen, self.gen + 1, n_nodes, max_cards)
+        self.gen += 1
+        extra = n_nodes - len(self.node_names)
+        self.node_names.extend([None] * extra)
+        self.card_names.extend([] for _ in range(extra))  # in place: the extender shares it
+        self.parked.extend([] for _ in range(extra))
+        if self.n_cards is not None and self.cap is not None:
+            self.n_cards = np.concatenate([np.asarray(self.n_cards, np.int32),
+                                           np.full(extra, -1, np.int32)])
+            cap = np.asarray(self.cap, np.int64)
+            self.cap = np.concatenate([cap, np.zeros((extra, cap.shape[1]), np.int64)])
+            self._rows_owned = True
+        self.max_cards = max_cards
+
+    def _plan_node(self, action: str, node: dict, send_pending):
+        """One node item on the host tables: (outcome, update) with update = (slot, n_cards,
+        cap [Q], src [max_cards]) or None when nothing is sent.  send_pending() sends the node
+        updates planned so far; it runs before the snapshot has to grow."""
+        name = _node_name(node)
+        slot = self.node_index.get(name)
+        if action == NODE_DELETED:
+            if slot is None:
+                return OK, None  # a node the snapshot never held
+            n_cards, cap, cards = -1, np.zeros(len(self.kinds), np.int64), []
+        else:
+            n_cards, cap, cards = gas_node_row(_node_dict(node), self.kinds)
+        k, n = self._k(), len(self.node_names)
+        spare = None
+        if slot is None:
+            spare = next((i for i, nm in enumerate(self.node_names) if nm is None), None)
+        grow_n = slot is None and spare is None
+        if grow_n or len(cards) > k:
+            send_pending()
+            if grow_n:
+                spare = n
+                n += (max(64, n // 8) + 63) // 64 * 64
+            self._grow(n, _tier(len(cards)) if len(cards) > k else k)
+            k = self.max_cards
+        if slot is None:
+            slot = spare
+            self.node_names[slot] = name
+            self.node_index[name] = slot
+        old_slots = list(self.card_names[slot]) + self.parked[slot]
+        if action == NODE_DELETED:  # the row stays where it is, every card parked
+            src, slots, dropped = list(range(k)), old_slots, []
+        else:
+            src, slots, dropped = card_remap(old_slots, cards, k)
+        self.card_names[slot] = slots[:len(cards)]
+        self.parked[slot] = slots[len(cards):]
+        if self.n_cards is not None and self.cap is not None:
+            if not self._rows_owned:  # the caller's arrays stay as they are
+                self.n_cards = np.array(self.n_cards, np.int32)
+                self.cap = np.array(self.cap, np.int64)
+                self._rows_owned = True
+            self.n_cards[slot], self.cap[slot] = n_cards, cap
+        outcome = OK if not dropped else "dropped: " + ", ".join(dropped)
+        return outcome, (slot, n_cards, cap, src)
+
+    def _send_nodes(self, updates) -> List[int]:
+        """One pas_gas_nodes_update call for the planned updates, in order."""
+        st = self.ctx.gas_nodes_update(self.gen, self.gen + 1, [u[0] for u in updates],
+                                       [u[1] for u in updates],
+                                       np.array([u[2] for u in updates], np.int64),
+                                       np.array([u[3] for u in updates], np.int32))
+        self.gen += 1
+        return [int(s) for s in st]
 
     # ------------------------------------------------------------ the worker
     def _plan(self, action: str, pod: dict, annotation: str):
@@ -191,7 +347,26 @@ class GasCache:
             slots.clear()
             keys.clear()
 
+        node_batch, node_slots = [], []  # planned node updates and their (i, name, action, outcome)
+
+        def close_nodes():
+            if node_batch:
+                for (i, name, action, outcome), s in zip(node_slots, self._send_nodes(node_batch)):
+                    results[i] = (name, action, outcome if s == _lib.PAS_GAS_OK else ERR_INPUT)
+            node_batch.clear()
+            node_slots.clear()
+
         for i, (action, pod, annotation) in enumerate(queue):
+            if action in _NODE_ACTIONS:
+                close()  # a node item closes the open pod batch
+                outcome, update = self._plan_node(action, pod, close_nodes)
+                if update is None:
+                    results[i] = (_node_name(pod), action, outcome)
+                else:
+                    node_batch.append(update)
+                    node_slots.append((i, _node_name(pod), action, outcome))
+                continue
+            close_nodes()  # the pod's ranks and its event follow the node updates
             key = pod_key(pod)
             if key in keys:  # its decision needs the first event's status
                 close()
@@ -204,6 +379,7 @@ class GasCache:
             slots.append((i, key, action, annotation))
             keys.add(key)
         close()
+        close_nodes()
         return results  # type: ignore[return-value]
 
     def rebuild(self, pods: Sequence[dict]) -> List[Tuple[str, str, str]]:
@@ -213,10 +389,13 @@ class GasCache:
             raise ValueError("rebuild needs the snapshot's n_cards and cap")
         n_cards = np.ascontiguousarray(self.n_cards, np.int32)
         cap = np.ascontiguousarray(self.cap, np.int64)
-        k = max([1] + [len(c) for c in self.card_names])
+        # the current slots: max_cards as node events left it (parked usage starts at zero too)
+        k = self.max_cards if self.max_cards is not None else \
+            max([1] + [len(c) for c in self.card_names])
         self.gen += 1
         self.ctx.gas_snapshot_set(self.gen, n_cards, cap,
                                   np.zeros((len(n_cards), k, len(self.kinds)), np.int64))
+        self.parked = [[] for _ in self.node_names]
         self.annotated.clear()
         self._queue = []
         for pod in pods:

@@ -123,38 +123,73 @@ def gas_snapshot_from_nodes(nodes: Sequence[Optional[dict]], kinds: Sequence[str
     q = len(kinds)
     n = len(nodes)
     n_cards = np.zeros(n, np.int32)
+    cap = np.zeros((n, q), np.int64)
     card_names: List[List[str]] = []
     for i, node in enumerate(nodes):
-        labels = (node.get("labels") or {}) if node is not None else {}
-        if node is None or GPU_LIST_LABEL not in labels:
-            n_cards[i] = -1 if node is None else 0
-            card_names.append([])
-            continue
-        cards = go_sort_strings(set(labels[GPU_LIST_LABEL].split(".")))
+        n_cards[i], cap[i], cards = gas_node_row(node, kinds)
         if len(cards) > max_cards:
             raise _lib.PasError(_lib.PAS_ECAPACITY,
                                 f"node {i}: {len(cards)} cards > {max_cards} (PAS_GAS_MAX_CARDS)")
-        n_cards[i] = len(cards)
         card_names.append(cards)
     k = max([1] + [len(c) for c in card_names])
-    cap = np.zeros((n, q), np.int64)
     used = np.zeros((n, k, q), np.int64)
     for i, node in enumerate(nodes):
         if n_cards[i] <= 0:
             continue
-        gpu_count = len(node["labels"][GPU_LIST_LABEL].split("."))
-        alloc = node.get("allocatable") or {}
-        for j, kind in enumerate(kinds):
-            if kind in alloc and kind.startswith(RESOURCE_PREFIX):
-                # resourceMap.divide: Go integer division truncates toward zero
-                value = quantity_as_int64(alloc[kind])
-                share = abs(value) // gpu_count
-                cap[i, j] = -share if value < 0 else share
         usage: Dict[str, Dict[str, int]] = node.get("usage") or {}
         for r, card in enumerate(card_names[i]):
             for j, kind in enumerate(kinds):
                 used[i, r, j] = int(usage.get(card, {}).get(kind, 0))
     return n_cards, cap, used, card_names
+
+
+def gas_node_row(node: Optional[dict], kinds: Sequence[str]):
+    """(n_cards, cap_per_gpu [Q] int64, cards) of one node dict as gas_snapshot_from_nodes reads
+    it ({"labels": ..., "allocatable": ...}, or None for a node the lister does not know):
+    its row of n_cards / cap_per_gpu and its label cards in rank order.  The card count is not
+    checked against a snapshot's max_cards."""
+    cap = np.zeros(len(kinds), np.int64)
+    labels = (node.get("labels") or {}) if node is not None else {}
+    if node is None or GPU_LIST_LABEL not in labels:
+        return (-1 if node is None else 0), cap, []
+    cards = go_sort_strings(set(labels[GPU_LIST_LABEL].split(".")))
+    gpu_count = len(labels[GPU_LIST_LABEL].split("."))
+    alloc = node.get("allocatable") or {}
+    for j, kind in enumerate(kinds):
+        if kind in alloc and kind.startswith(RESOURCE_PREFIX):
+            # resourceMap.divide: Go integer division truncates toward zero
+            value = quantity_as_int64(alloc[kind])
+            share = abs(value) // gpu_count
+            cap[j] = -share if value < 0 else share
+    return len(cards), cap, cards
+
+
+def card_remap(old_slots: Sequence[str], new_label_cards: Sequence[str], max_cards: int):
+    """The slot map of a node whose label now lists new_label_cards, for
+    pas_gas_nodes_update: (src [max_cards], new_slots, dropped).
+
+    old_slots / new_slots name the cards of the row's slots: the label cards in sort.Strings
+    order, then the parked cards (cards with usage the label does not list at the moment;
+    the reference keeps them by name in nodeStatuses).  src[k] is the old slot whose usage
+    slot k takes, -1 for a card first seen (zero usage) and for the unused slots.  Cards that
+    leave the label are parked behind the label cards; parked cards the label lists again
+    return to their rank with their usage.  The parked cards stay ordered most recently parked
+    first; when label and parked cards exceed max_cards the oldest parked cards that do not
+    fit are dropped and returned (their usage is lost, where the reference would remember it).
+    Parking never needs more than max_cards slots; a label of more than max_cards cards is a
+    ValueError (the snapshot has to grow first)."""
+    label = go_sort_strings(set(new_label_cards))
+    if len(label) > max_cards:
+        raise ValueError(f"{len(label)} label cards > max_cards {max_cards}")
+    listed = set(label)
+    # cards that just left the label stand before the cards parked earlier
+    parked = [c for c in old_slots if c not in listed]
+    keep = max_cards - len(label)
+    parked, dropped = parked[:keep], parked[keep:]
+    new_slots = label + parked
+    old_index = {c: k for k, c in enumerate(old_slots)}
+    src = [old_index.get(c, -1) for c in new_slots] + [-1] * (max_cards - len(new_slots))
+    return src, new_slots, dropped
 
 
 def annotation(word: int, container_i915: Sequence[int], card_names: Sequence[str],
