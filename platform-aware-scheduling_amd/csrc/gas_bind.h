@@ -5,7 +5,8 @@
 // the pair-list commit (gas_commit.hip) and the batch placement (gas_place.hip) call it, so
 // an operation gives the same word, selections and usage whichever call carries it.
 // release_one and adopt_one are the reference's adjustPodResources(remove / add) from an
-// annotation, shared the same way by the release kernel and the event path (gas_commit.hip).
+// annotation, shared the same way by the walker kernel's release and event forms
+// (gas_commit.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,9 +29,7 @@ __device__ __forceinline__ bool kind_fits(int64_t need, int64_t cap, int64_t use
 struct BindArgs {
   int32_t K, Q, C, i915;
   const int32_t* order;    // operation indices sorted by node (stable)
-  const int32_t* seg_off;  // [n_seg + 1] into order
   const int32_t* op_pod;
-  const int32_t* op_node;
   const int32_t* n_cards;
   const int64_t* cap;
   int64_t* used;

@@ -1,4 +1,4 @@
-// gas_commit.hip — bind-time commit of GAS card selections into the resident snapshot.
+// gas_commit.hip — bind, release and pod events committed into the resident GAS snapshot.
 //
 // GASExtender.bindNode (gpu-aware-scheduling/pkg/gpuscheduler/scheduler.go:385-445) runs
 // runSchedulingLogic for the pod on the chosen node once more (:417-421), then
@@ -6,127 +6,57 @@
 // request divided by the container's card count to each card of its annotation segment, all
 // or nothing (checkPodResourceAdjustment on a copy first, :187-238).  A pod leaving the node
 // runs adjustPodResources(remove): subtractRM per card (resource_map.go:55-73, 103-127: a
-// negative amount or a key the card lacks is an input error; results clamp at zero).
+// negative amount or a key the card lacks is an input error; results clamp at zero).  The event
+// path (pas_gas_apply[_device]) is Cache.handlePod's adjustPodResources(add / remove) straight
+// from a pod's annotation (node_resource_cache.go:493-538), one ordered batch of pod events.
 //
-// Here both patch the device-resident used[N][K][Q] in place, so the frozen snapshot stays
-// consistent across binds without a re-upload.  The host sorts the operations by node
-// (stable); one thread owns each node and applies that node's operations in call order, so
-// operations on one node see each other exactly as the reference's serialised binds do.
-// This is latency work (a few thousand operations per call at most), not a hot kernel.
-//
-// The event path (pas_gas_apply[_device]) is the third writer: Cache.handlePod's
-// adjustPodResources(add / remove) straight from a pod's annotation (node_resource_cache.go:
-// 493-538), one ordered batch of pod events.  Its grouping runs on the device: a key kernel
-// gives event e the key node[e] (N for an event whose kind, node or pod is out of range), a
-// stable radix sort of (key, e) over the bits N needs makes one run per node with the events
-// in call order, and one thread per run walks it on the node's usage held by that thread.  Its
-// large case is the cold-start rebuild: every running pod's annotation as one ADD batch.
+// All three patch the device-resident used[N][K][Q] in place, so the frozen snapshot stays
+// consistent without a re-upload, and all three run one kernel, gas_walk_kernel: the
+// operations arrive sorted by node (stable: one run per node, in call order), one thread owns
+// each run (run_owner, gas_group.h) and applies it on the node's usage held by that thread, so
+// operations on one node see each other exactly as the reference's serialised calls do.  What
+// differs is who sorts.  Bind and release are latency work (a single pair per call is the
+// common case): the host sorts and uploads the sorted keys, so no key kernel and no rocprim
+// launch stands before the walker.  Events group on the device (NodeRuns, gas_group.h: an
+// event whose kind, node or pod is out of range gets the key N); their large case is the
+// cold-start rebuild, every running pod's annotation as one ADD batch.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "gas_bind.h"
-#include "gas_runs.h"
+#include "gas_group.h"
 #include "pas_internal.h"
 
 namespace pas {
 namespace {
 
-constexpr int kTpb = 64;
 constexpr int kMaxRes = kBindMaxRes;
 
-// KMAX: the snapshot's max_cards rounded up to 8 / 16 / 64 (the per-thread copies live in
-// registers for the common shapes, in scratch for 64-card snapshots).
-template <int KMAX>
-__global__ __launch_bounds__(kTpb) void gas_bind_kernel(int32_t n_seg, BindArgs a) {
-  const int32_t sgi = blockIdx.x * kTpb + threadIdx.x;
-  if (sgi >= n_seg) return;
-  const int32_t K = a.K, Q = a.Q;
-  const int32_t n = a.op_node[a.order[a.seg_off[sgi]]];
-  const int32_t ncard = min(a.n_cards[n], K);
-  int64_t* un = a.used + (int64_t)n * K * Q;
-  int64_t u[KMAX][kMaxRes], cap[kMaxRes];
-  for (int k = 0; k < K; ++k)
-    for (int q = 0; q < Q; ++q) u[k][q] = un[k * Q + q];
-  for (int q = 0; q < Q; ++q) cap[q] = a.cap[(int64_t)n * Q + q];
-  for (int32_t i = a.seg_off[sgi]; i < a.seg_off[sgi + 1]; ++i) {
-    const int32_t op = a.order[i];
-    const int32_t p = a.op_pod[op];
-    // the bind itself (gas_bind.h), on the register copy
-    a.status[op] = bind_one<KMAX>(a, u, cap, ncard, p, a.ncont[p], op) ? PAS_GAS_OK
-                                                                      : PAS_GAS_WONT_FIT;
-  }
-  for (int k = 0; k < K; ++k)
-    for (int q = 0; q < Q; ++q) un[k * Q + q] = u[k][q];
-}
+enum class Op { kBind, kRelease, kEvents };
 
-template <int KMAX>
-__global__ __launch_bounds__(kTpb) void gas_release_kernel(int32_t n_seg, BindArgs a) {
-  const int32_t sgi = blockIdx.x * kTpb + threadIdx.x;
-  if (sgi >= n_seg) return;
-  const int32_t K = a.K, Q = a.Q;
-  const int32_t n = a.op_node[a.order[a.seg_off[sgi]]];
-  const int32_t ncard = max(0, min(a.n_cards[n], K));
-  int64_t* un = a.used + (int64_t)n * K * Q;
-  int64_t u[KMAX][kMaxRes];
-  for (int k = 0; k < K; ++k)
-    for (int q = 0; q < Q; ++q) u[k][q] = un[k * Q + q];
-  for (int32_t i = a.seg_off[sgi]; i < a.seg_off[sgi + 1]; ++i) {
-    const int32_t op = a.order[i];
-    const int32_t p = a.op_pod[op];
-    // the release itself (gas_bind.h), on the register copy
-    a.status[op] = release_one<KMAX>(a, u, ncard, p, a.ncont[p], op) ? PAS_GAS_OK
-                                                                      : PAS_GAS_ERR_INPUT;
-  }
-  for (int k = 0; k < K; ++k)
-    for (int q = 0; q < Q; ++q) un[k * Q + q] = u[k][q];
-}
+// Sorted positions per workgroup.  Events: 1 024 (against 256 and against no compaction,
+// DESIGN.md): their runs are long, so a workgroup has few owners.  Bind and release: 64, one
+// wave.  Their batches are a few thousand operations over as many nodes, so nearly every
+// position is a head, and workgroups of 1 024 would put the whole batch on four compute units
+// (measured: the 4 096-bind call a quarter slower).
+template <Op OP>
+constexpr int kWalkTpb = OP == Op::kEvents ? 1024 : 64;
 
-// Event e's sort key: its node, or N (sorts last) when kind, node or pod is out of range.
-__global__ __launch_bounds__(256) void gas_apply_key_kernel(
-    int32_t n_ev, int32_t N, int32_t n_pods, const int32_t* __restrict__ kind,
-    const int32_t* __restrict__ pod, const int32_t* __restrict__ node,
-    uint32_t* __restrict__ key, int32_t* __restrict__ idx) {
-  const int32_t e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n_ev) return;
-  const int32_t k = kind[e], p = pod[e], n = node[e];
-  const bool ok = (k == PAS_GAS_EV_ADD || k == PAS_GAS_EV_REMOVE) && n >= 0 && n < N && p >= 0 &&
-                  p < n_pods;
-  key[e] = ok ? (uint32_t)n : (uint32_t)N;
-  idx[e] = e;
-}
-
-// One thread per sorted position finds the heads: a position whose key differs from the one
-// before it starts a node's run (a position whose key is N reports its own event).  Runs
-// average many events, so the heads are few and scattered: the workgroup compacts them (their
-// order is free, every node has one owner) and its first threads walk one run each, applying
-// its events in order, so the walking lanes share waves and the other waves leave at once
-// (4 x the rebuild's speed against a walk from the head's own lane).  a.order =
-// the sorted event indices, key = the sorted keys; a.op_pod / a.ncont / a.cpc / a.cards are
-// read as the _device form's contract says (n_containers clamped, negative counts 0, a list
-// past cards_ld errInput).
-constexpr int kApplyTpb = 1024;
-template <int KMAX>
-__global__ __launch_bounds__(kApplyTpb) void gas_apply_kernel(int32_t n_ev, int32_t N,
-                                                              const uint32_t* __restrict__ key,
-                                                              const int32_t* __restrict__ kind,
-                                                              BindArgs a) {
-  __shared__ int32_t heads[kApplyTpb];
-  __shared__ int32_t n_heads;
-  if (threadIdx.x == 0) n_heads = 0;
-  __syncthreads();
-  const int64_t pos = (int64_t)blockIdx.x * kApplyTpb + threadIdx.x;
-  if (pos < n_ev) {
-    const uint32_t kp = key[pos];
-    if (kp >= (uint32_t)N)  // an event out of range
-      a.status[a.order[pos]] = PAS_GAS_ERR_INPUT;
-    else if (pos == 0 || key[pos - 1] != kp)
-      heads[atomicAdd(&n_heads, 1)] = (int32_t)pos;
-  }
-  __syncthreads();
-  if ((int32_t)threadIdx.x >= n_heads) return;
-  const int32_t i = heads[threadIdx.x];
+// The owner of a run loads the node's usage, applies the run's operations in order (gas_bind.h)
+// and stores the usage once.  a.order = the sorted operation indices, key = the sorted keys,
+// kind = the events' kinds (kEvents only).  a.op_pod / a.ncont / a.cpc / a.cards are read as
+// the events' _device form's contract says (n_containers clamped, negative counts 0, a list
+// past cards_stride errInput); the host forms have validated them.
+template <int KMAX, Op OP>
+__global__ __launch_bounds__(kWalkTpb<OP>) void gas_walk_kernel(int32_t n_ops, int32_t N,
+                                                                const uint32_t* __restrict__ key,
+                                                                const int32_t* __restrict__ kind,
+                                                                BindArgs a) {
+  constexpr int kTpb = kWalkTpb<OP>;
+  const int64_t pos = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  bool bad;
+  const int32_t i = run_owner<kTpb>(pos, n_ops, N, key, &bad);
+  if (bad) a.status[a.order[pos]] = PAS_GAS_ERR_INPUT;  // an event out of range
+  if (i < 0) return;
   const uint32_t n = key[i];
   const int32_t K = a.K, Q = a.Q;
   const int32_t ncard = max(0, min(a.n_cards[n], K));
@@ -134,18 +64,41 @@ __global__ __launch_bounds__(kApplyTpb) void gas_apply_kernel(int32_t n_ev, int3
   int64_t u[KMAX][kMaxRes];
   for (int k = 0; k < K; ++k)
     for (int q = 0; q < Q; ++q) u[k][q] = un[k * Q + q];
-  for (int32_t j = i; j < n_ev && key[j] == n; ++j) {
-    const int32_t e = a.order[j];
-    const int32_t p = a.op_pod[e];
+  [[maybe_unused]] int64_t cap[kMaxRes];
+  if constexpr (OP == Op::kBind)
+    for (int q = 0; q < Q; ++q) cap[q] = a.cap[(int64_t)n * Q + q];
+  for (int32_t j = i; j < n_ops && key[j] == n; ++j) {
+    const int32_t op = a.order[j];
+    const int32_t p = a.op_pod[op];
     const int32_t ncont = max(0, min(a.ncont[p], a.C));
-    if (kind[e] == PAS_GAS_EV_ADD)
-      a.status[e] = adopt_one<KMAX>(a, u, ncard, p, ncont, e);
+    if constexpr (OP == Op::kBind)
+      a.status[op] = bind_one<KMAX>(a, u, cap, ncard, p, ncont, op) ? PAS_GAS_OK
+                                                                    : PAS_GAS_WONT_FIT;
+    else if (OP == Op::kEvents && kind[op] == PAS_GAS_EV_ADD)
+      a.status[op] = adopt_one<KMAX>(a, u, ncard, p, ncont, op);
     else
-      a.status[e] = release_one<KMAX>(a, u, ncard, p, ncont, e) ? PAS_GAS_OK
-                                                                 : PAS_GAS_ERR_INPUT;
+      a.status[op] = release_one<KMAX>(a, u, ncard, p, ncont, op) ? PAS_GAS_OK
+                                                                  : PAS_GAS_ERR_INPUT;
   }
   for (int k = 0; k < K; ++k)
     for (int q = 0; q < Q; ++q) un[k * Q + q] = u[k][q];
+}
+
+// The walker over n_ops sorted positions; `a` gets the snapshot's fields here.
+template <Op OP>
+int walk_launch(pas_ctx* ctx, int32_t n_ops, const uint32_t* d_key, const int32_t* d_kind,
+                BindArgs a, hipStream_t s) {
+  const GasSnapshot& g = ctx->gas;
+  a.K = g.max_cards, a.Q = g.n_res;
+  a.n_cards = g.n_cards, a.cap = g.cap, a.used = g.used;
+  constexpr int kTpb = kWalkTpb<OP>;
+  const unsigned blocks = (unsigned)(((size_t)n_ops + kTpb - 1) / kTpb);
+  card_tier(g.max_cards, [&](auto km) {
+    gas_walk_kernel<decltype(km)::value, OP><<<blocks, kTpb, 0, s>>>(n_ops, g.n_nodes, d_key,
+                                                                     d_kind, a);
+  });
+  PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
 }
 
 }  // namespace
@@ -156,78 +109,37 @@ int gas_apply_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
                      const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
                      int32_t cards_ld, int32_t* d_status, hipStream_t s) {
   if (n_events == 0) return PAS_OK;
-  GasSnapshot& g = ctx->gas;
-  const size_t E = (size_t)n_events;
-  const int32_t N = g.n_nodes;
-  unsigned end_bit = 1;  // the bits of the largest key, N
-  while ((uint64_t(1) << end_bit) <= (uint64_t)N) ++end_bit;
-  size_t sort_bytes = 0;
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr,
-                                         (uint32_t*)nullptr, (int32_t*)nullptr,
-                                         (int32_t*)nullptr, E, 0u, end_bit, s));
-  sort_bytes = std::max<size_t>(sort_bytes, 16);
-  int rc = PAS_OK;
-  SlotScope scope(ctx, s, 0, &rc);
-  if (!scope.slot) return rc;
-  const size_t bytes = carve_size({4 * E, 4 * E, 4 * E, 4 * E, sort_bytes});
-  void* buf = slot_buf(ctx, scope.slot, kBufApply, bytes, s, &rc);
-  if (!buf) return rc;
-  Carve cv{static_cast<char*>(buf)};
-  uint32_t* d_key = cv.take<uint32_t>(E);
-  uint32_t* d_key_sorted = cv.take<uint32_t>(E);
-  int32_t* d_idx = cv.take<int32_t>(E);
-  int32_t* d_order = cv.take<int32_t>(E);
-  void* d_sort_tmp = cv.take<char>(sort_bytes);
-  gas_apply_key_kernel<<<(unsigned)((E + 255) / 256), 256, 0, s>>>(n_events, N, n_pods, d_kind,
-                                                                  d_pod, d_node, d_key, d_idx);
-  PAS_HIP(ctx, hipGetLastError());
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(d_sort_tmp, sort_bytes, d_key, d_key_sorted, d_idx,
-                                         d_order, E, 0u, end_bit, s));
-  BindArgs a{g.max_cards, g.n_res, max_containers, -1,      d_order, nullptr, d_pod,
-             d_node,      g.n_cards, g.cap,        g.used,  d_req,   d_mask,  d_ncont,
-             d_cpc,       d_cards, cards_ld,       nullptr, d_status, nullptr, nullptr,
-             nullptr,     nullptr};
-  const unsigned blocks = (unsigned)((E + kApplyTpb - 1) / kApplyTpb);
-  if (g.max_cards <= 8)
-    gas_apply_kernel<8><<<blocks, kApplyTpb, 0, s>>>(n_events, N, d_key_sorted, d_kind, a);
-  else if (g.max_cards <= 16)
-    gas_apply_kernel<16><<<blocks, kApplyTpb, 0, s>>>(n_events, N, d_key_sorted, d_kind, a);
-  else
-    gas_apply_kernel<PAS_GAS_MAX_CARDS><<<blocks, kApplyTpb, 0, s>>>(n_events, N, d_key_sorted,
-                                                                     d_kind, a);
-  PAS_HIP(ctx, hipGetLastError());
-  return PAS_OK;
+  NodeRuns runs(ctx, n_events, d_node, [=] __device__(int32_t e) {
+    const int32_t k = d_kind[e], p = d_pod[e];
+    return (k == PAS_GAS_EV_ADD || k == PAS_GAS_EV_REMOVE) && p >= 0 && p < n_pods;
+  }, s);
+  if (runs.rc) return runs.rc;
+  BindArgs a{};
+  a.C = max_containers, a.i915 = -1;
+  a.order = runs.order, a.op_pod = d_pod;
+  a.req = d_req, a.mask = d_mask, a.ncont = d_ncont;
+  a.cpc = d_cpc, a.cards = d_cards, a.cards_stride = cards_ld;
+  a.status = d_status;
+  return walk_launch<Op::kEvents>(ctx, n_events, runs.key, d_kind, a, s);
 }
 
-int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_seg, int32_t max_containers,
-                      int32_t i915_index, const int32_t* d_order, const int32_t* d_seg_off,
-                      const int32_t* d_pod, const int32_t* d_node, const int64_t* d_req,
-                      const uint32_t* d_mask, const int32_t* d_ncont, const int32_t* d_cpc,
-                      const int32_t* d_cards, int32_t cards_stride, uint32_t* d_res,
-                      int32_t* d_status, uint8_t* d_cards_out, int32_t* d_nsel_out,
-                      int64_t* d_counts_out, const int64_t* d_counts, hipStream_t s) {
-  if (n_seg == 0) return PAS_OK;
-  GasSnapshot& g = ctx->gas;
-  BindArgs a{g.max_cards, g.n_res,  max_containers, i915_index, d_order, d_seg_off,
-             d_pod,       d_node,   g.n_cards,      g.cap,      g.used,  d_req,
-             d_mask,      d_ncont,  d_cpc,          d_cards,    cards_stride,
-             d_res,       d_status, d_cards_out,    d_nsel_out, d_counts_out, d_counts};
-  const unsigned blocks = (unsigned)((n_seg + kTpb - 1) / kTpb);
-#define PAS_COMMIT(KM)                                       \
-  if (release)                                               \
-    gas_release_kernel<KM><<<blocks, kTpb, 0, s>>>(n_seg, a); \
-  else                                                       \
-    gas_bind_kernel<KM><<<blocks, kTpb, 0, s>>>(n_seg, a);
-  if (g.max_cards <= 8) {
-    PAS_COMMIT(8)
-  } else if (g.max_cards <= 16) {
-    PAS_COMMIT(16)
-  } else {
-    PAS_COMMIT(PAS_GAS_MAX_CARDS)
-  }
-#undef PAS_COMMIT
-  PAS_HIP(ctx, hipGetLastError());
-  return PAS_OK;
+int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_ops, int32_t max_containers,
+                      int32_t i915_index, const int32_t* d_order, const uint32_t* d_key,
+                      const int32_t* d_pod, const int64_t* d_req, const uint32_t* d_mask,
+                      const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
+                      int32_t cards_stride, uint32_t* d_res, int32_t* d_status,
+                      uint8_t* d_cards_out, int32_t* d_nsel_out, int64_t* d_counts_out,
+                      const int64_t* d_counts, hipStream_t s) {
+  if (n_ops == 0) return PAS_OK;
+  BindArgs a{};
+  a.C = max_containers, a.i915 = i915_index;
+  a.order = d_order, a.op_pod = d_pod;
+  a.req = d_req, a.mask = d_mask, a.ncont = d_ncont;
+  a.cpc = d_cpc, a.cards = d_cards, a.cards_stride = cards_stride;
+  a.res_out = d_res, a.status = d_status, a.cards_out = d_cards_out, a.nsel_out = d_nsel_out;
+  a.counts_out = d_counts_out, a.counts = d_counts;
+  return release ? walk_launch<Op::kRelease>(ctx, n_ops, d_key, nullptr, a, s)
+                 : walk_launch<Op::kBind>(ctx, n_ops, d_key, nullptr, a, s);
 }
 
 }  // namespace pas

@@ -11,22 +11,22 @@
 // row: new counts, new capacities, and the usage moved to the slots the new label gives its
 // cards (pas_gas_nodes_update[_device]).
 //
-// The grouping is the event path's (gas_commit.hip): a key per update (its node, or N for an
-// update out of range), a stable radix sort of (key, u) over the bits N needs, head detection,
-// one owner thread per node.  The owner folds its run's slot maps in call order into one map
-// (a later update's upd_src indexes the row the earlier one left, so the maps compose), reads
-// the old row once, and writes the row, n_cards[n] and cap[n][*] once: the whole old row is in
-// the thread's registers (scratch for 64-card snapshots) before its first store, so any
-// permutation is safe in place, and no other thread touches the row.  No atomics on the
-// snapshot.
+// The grouping is the shared one (gas_group.h): NodeRuns gives a key per update (its node, or N
+// for an update whose node or card count is out of range) and a stable radix sort of (key, u)
+// over the bits N needs; run_owner elects one owner thread per node.  The owner folds its run's
+// slot maps in call order into one map (a later update's upd_src indexes the row the earlier one
+// left, so the maps compose), reads the old row once, and writes the row, n_cards[n] and
+// cap[n][*] once: the whole old row is in the thread's registers (scratch for 64-card
+// snapshots) before its first store, so any permutation is safe in place, and no other thread
+// touches the row.  No atomics on the snapshot.  The row code is this kernel's own: fully
+// unrolled and register-resident at the 8- and 16-slot tiers (no scratch), where the walker of
+// gas_commit.hip indexes its row dynamically.
 //
 // pas_gas_snapshot_resize re-pitches [N][K][Q] -> [N'][K'][Q] into new storage with one
 // bandwidth-bound kernel (zero fill, -1 for the new nodes' counts).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "gas_group.h"
 #include "pas_internal.h"
 
 namespace pas {
@@ -34,21 +34,6 @@ namespace {
 
 constexpr int kMaxRes = PAS_GAS_MAX_RES;
 constexpr int kNodesTpb = 256;
-
-// Update u's sort key: its node, or N (sorts last) when the node or the card count is out of
-// range.
-__global__ __launch_bounds__(256) void gas_nodes_key_kernel(int32_t n_upd, int32_t N, int32_t K,
-                                                            const int32_t* __restrict__ node,
-                                                            const int32_t* __restrict__ ncards,
-                                                            uint32_t* __restrict__ key,
-                                                            int32_t* __restrict__ idx) {
-  const int32_t u = blockIdx.x * 256 + threadIdx.x;
-  if (u >= n_upd) return;
-  const int32_t n = node[u], c = ncards[u];
-  const bool ok = n >= 0 && n < N && c >= -1 && c <= K;
-  key[u] = ok ? (uint32_t)n : (uint32_t)N;
-  idx[u] = u;
-}
 
 // v[s] for a slot s the caller has checked, 0 <= s < K <= KMAX.  The 8- and 16-slot tiers
 // select over a fully unrolled chain, so v stays in registers; 64 slots index scratch.
@@ -64,9 +49,8 @@ __device__ __forceinline__ T pick(const T (&v)[KMAX], int32_t s) {
   }
 }
 
-// One thread per sorted position finds the heads and reports the statuses; the workgroup
-// compacts the heads and its first threads own one node each (gas_apply_kernel's shape).
-// upd_src is read defensively: a value outside [0, K) is "zero usage".
+// One thread per sorted position reports its update's status; the owners run_owner elects
+// rewrite one node each.  upd_src is read defensively: a value outside [0, K) is "zero usage".
 template <int KMAX>
 __global__ __launch_bounds__(kNodesTpb) void gas_nodes_kernel(
     int32_t n_upd, int32_t N, int32_t K, int32_t Q, const uint32_t* __restrict__ key,
@@ -74,20 +58,11 @@ __global__ __launch_bounds__(kNodesTpb) void gas_nodes_kernel(
     const int64_t* __restrict__ upd_cap, const int32_t* __restrict__ upd_src,
     int32_t* __restrict__ n_cards, int64_t* __restrict__ cap, int64_t* __restrict__ used,
     int32_t* __restrict__ status) {
-  __shared__ int32_t heads[kNodesTpb];
-  __shared__ int32_t n_heads;
-  if (threadIdx.x == 0) n_heads = 0;
-  __syncthreads();
   const int64_t pos = (int64_t)blockIdx.x * kNodesTpb + threadIdx.x;
-  if (pos < n_upd) {
-    const uint32_t kp = key[pos];
-    status[order[pos]] = kp >= (uint32_t)N ? PAS_GAS_ERR_INPUT : PAS_GAS_OK;
-    if (kp < (uint32_t)N && (pos == 0 || key[pos - 1] != kp))
-      heads[atomicAdd(&n_heads, 1)] = (int32_t)pos;
-  }
-  __syncthreads();
-  if ((int32_t)threadIdx.x >= n_heads) return;
-  const int32_t i = heads[threadIdx.x];
+  bool bad;
+  const int32_t i = run_owner<kNodesTpb>(pos, n_upd, N, key, &bad);
+  if (pos < n_upd) status[order[pos]] = bad ? PAS_GAS_ERR_INPUT : PAS_GAS_OK;
+  if (i < 0) return;
   const uint32_t n = key[i];
   int64_t* un = used + (int64_t)n * K * Q;
   // the old row, whole, before any store
@@ -159,44 +134,17 @@ int gas_nodes_update_launch(pas_ctx* ctx, int32_t n_updates, const int32_t* d_no
                             const int32_t* d_src, int32_t* d_status, hipStream_t s) {
   if (n_updates == 0) return PAS_OK;
   GasSnapshot& g = ctx->gas;
-  const size_t U = (size_t)n_updates;
   const int32_t N = g.n_nodes, K = g.max_cards, Q = g.n_res;
-  unsigned end_bit = 1;  // the bits of the largest key, N
-  while ((uint64_t(1) << end_bit) <= (uint64_t)N) ++end_bit;
-  size_t sort_bytes = 0;
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr,
-                                         (uint32_t*)nullptr, (int32_t*)nullptr,
-                                         (int32_t*)nullptr, U, 0u, end_bit, s));
-  sort_bytes = std::max<size_t>(sort_bytes, 16);
-  int rc = PAS_OK;
-  SlotScope scope(ctx, s, 0, &rc);
-  if (!scope.slot) return rc;
-  const size_t bytes = carve_size({4 * U, 4 * U, 4 * U, 4 * U, sort_bytes});
-  void* buf = slot_buf(ctx, scope.slot, kBufNodes, bytes, s, &rc);
-  if (!buf) return rc;
-  Carve cv{static_cast<char*>(buf)};
-  uint32_t* d_key = cv.take<uint32_t>(U);
-  uint32_t* d_key_sorted = cv.take<uint32_t>(U);
-  int32_t* d_idx = cv.take<int32_t>(U);
-  int32_t* d_order = cv.take<int32_t>(U);
-  void* d_sort_tmp = cv.take<char>(sort_bytes);
-  gas_nodes_key_kernel<<<(unsigned)((U + 255) / 256), 256, 0, s>>>(n_updates, N, K, d_node,
-                                                                  d_n_cards, d_key, d_idx);
-  PAS_HIP(ctx, hipGetLastError());
-  PAS_HIP(ctx, rocprim::radix_sort_pairs(d_sort_tmp, sort_bytes, d_key, d_key_sorted, d_idx,
-                                         d_order, U, 0u, end_bit, s));
-  const unsigned blocks = (unsigned)((U + kNodesTpb - 1) / kNodesTpb);
-#define PAS_NODES(KM)                                                                         \
-  gas_nodes_kernel<KM><<<blocks, kNodesTpb, 0, s>>>(n_updates, N, K, Q, d_key_sorted, d_order, \
-                                                    d_n_cards, d_cap, d_src, g.n_cards, g.cap, \
-                                                    g.used, d_status)
-  if (K <= 8)
-    PAS_NODES(8);
-  else if (K <= 16)
-    PAS_NODES(16);
-  else
-    PAS_NODES(PAS_GAS_MAX_CARDS);
-#undef PAS_NODES
+  NodeRuns runs(ctx, n_updates, d_node, [=] __device__(int32_t u) {
+    return d_n_cards[u] >= -1 && d_n_cards[u] <= K;
+  }, s);
+  if (runs.rc) return runs.rc;
+  const unsigned blocks = (unsigned)(((size_t)n_updates + kNodesTpb - 1) / kNodesTpb);
+  card_tier(K, [&](auto km) {
+    gas_nodes_kernel<decltype(km)::value><<<blocks, kNodesTpb, 0, s>>>(
+        n_updates, N, K, Q, runs.key, runs.order, d_n_cards, d_cap, d_src, g.n_cards, g.cap,
+        g.used, d_status);
+  });
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
 }

@@ -28,10 +28,8 @@
 // round moves a cursor: at most sum(row lengths) rounds, which the host loop enforces.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "gas_bind.h"
+#include "gas_group.h"
 #include "pas_internal.h"
 
 namespace pas {
@@ -213,13 +211,6 @@ __global__ __launch_bounds__(kTpb) void place_commit_kernel(PlaceArgs a, BindArg
   }
 }
 
-// bits that hold 0 .. n - 1 (at least 1)
-unsigned bits_for(int64_t n) {
-  unsigned b = 1;
-  while ((int64_t(1) << b) < n) ++b;
-  return b;
-}
-
 }  // namespace
 
 int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t i915_index,
@@ -235,7 +226,7 @@ int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32
   if (n_pods == 0) return PAS_OK;
   GasSnapshot& g = ctx->gas;
   const size_t P = (size_t)n_pods, N = (size_t)std::max(g.n_nodes, 1);
-  const unsigned pod_bits = bits_for(n_pods), end_bit = pod_bits + bits_for(g.n_nodes);
+  const unsigned pod_bits = key_bits(n_pods), end_bit = pod_bits + key_bits(g.n_nodes);
   if (!ctx->place_host)  // the round loop's read-back (pinned)
     PAS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->place_host), sizeof(PlaceCtr)));
   PlaceCtr* h = static_cast<PlaceCtr*>(ctx->place_host);
@@ -301,13 +292,10 @@ int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32
     PAS_HIP(ctx, rocprim::radix_sort_keys(d_sort_tmp, need, d_keys, d_sorted, (size_t)active,
                                           0u, end_bit, s));
     *began = true;
-    if (K <= 8)
-      place_commit_kernel<8><<<active, kTpb, 0, s>>>(a, b, (uint32_t)round, active);
-    else if (K <= 16)
-      place_commit_kernel<16><<<active, kTpb, 0, s>>>(a, b, (uint32_t)round, active);
-    else
-      place_commit_kernel<PAS_GAS_MAX_CARDS><<<active, kTpb, 0, s>>>(a, b, (uint32_t)round,
-                                                                    active);
+    card_tier(K, [&](auto km) {
+      place_commit_kernel<decltype(km)::value><<<active, kTpb, 0, s>>>(a, b, (uint32_t)round,
+                                                                       active);
+    });
     PAS_HIP(ctx, hipGetLastError());
     PAS_HIP(ctx, hipMemcpyAsync(h, d_ctr, sizeof(PlaceCtr), hipMemcpyDeviceToHost, s));
     PAS_HIP(ctx, hipStreamSynchronize(s));

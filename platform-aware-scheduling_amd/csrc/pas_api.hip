@@ -850,8 +850,52 @@ static int check_gas_gen(pas_ctx* ctx, uint64_t gen) {
   return PAS_OK;
 }
 
+// Pod p of a host batch: n_containers[p] within [0, max_containers] and no mask bit at or
+// above n_res.  Bind / release and apply check the pods their operations name, place and fit
+// check every pod.
+static int gas_pod_check(pas_ctx* ctx, int32_t p, int32_t max_containers,
+                         const uint32_t* req_mask, const int32_t* n_containers,
+                         const char* fn) {
+  if (n_containers[p] < 0 || n_containers[p] > max_containers)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": n_containers out of range");
+  for (int32_t c = 0; c < n_containers[p]; ++c)
+    if ((req_mask[(int64_t)p * max_containers + c] & ~PAS_REQ_UNKNOWN_KIND) >> ctx->gas.n_res)
+      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": mask bit >= n_res");
+  return PAS_OK;
+}
+
+// A call that wrote the resident snapshot has succeeded: the generation step.
+static int gas_stepped(pas_ctx* ctx, uint64_t gen_to) {
+  ctx->gas.gen = gen_to;
+  ++ctx->gas.epoch;
+  return PAS_OK;
+}
+
+// The tail of the host forms that write the resident usage (bind / release, apply, nodes
+// update).  enqueued = their kernel is on s: the results are copied back and s is synchronized,
+// and a failure of either leaves a snapshot of unknown content, which is invalidated.
+// Otherwise the generation steps.
+struct CopyBack {
+  void* dst;  // null or bytes == 0: skipped
+  const void* src;
+  size_t bytes;
+};
+static int gas_write_finish(pas_ctx* ctx, uint64_t gen_to, bool enqueued, hipStream_t s,
+                            const std::string& fn, std::initializer_list<CopyBack> back) {
+  hipError_t e = hipSuccess;
+  for (const CopyBack& b : back)
+    if (enqueued && e == hipSuccess && b.dst && b.bytes)
+      e = hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, s);
+  if (enqueued && e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    ctx->gas.valid = false;
+    return check_hip(ctx, e, (fn + ": copy of the results").c_str());
+  }
+  return gas_stepped(ctx, gen_to);
+}
+
 // Shared host path of pas_gas_bind / pas_gas_release: validates, groups the operations by
-// node (stable), uploads everything in one scratch carve and runs the commit kernel.
+// node (stable), uploads everything in one scratch carve and runs the walker kernel.
 static int gas_commit(pas_ctx* ctx, bool release, uint64_t gen_from, uint64_t gen_to,
                       int32_t n_ops, const int32_t* op_pod, const int32_t* op_node,
                       int32_t n_pods, int32_t max_containers, int32_t i915_index,
@@ -878,16 +922,12 @@ static int gas_commit(pas_ctx* ctx, bool release, uint64_t gen_from, uint64_t ge
     if (op_node[i] < 0 || op_node[i] >= N || op_pod[i] < 0 || op_pod[i] >= n_pods)
       return set_error(ctx, PAS_EINVAL, std::string(fn) + ": node or pod index out of range");
     const int32_t p = op_pod[i];
-    if (n_containers[p] < 0 || n_containers[p] > max_containers)
-      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": n_containers out of range");
+    if ((rc = gas_pod_check(ctx, p, max_containers, req_mask, n_containers, fn))) return rc;
     // annotation cards of a release: within the card list (cards[i][cards_stride]), or per
     // container a count sum that fits int64 (counts form).  Binds have no selection limit.
     const int64_t limit = cards_stride;
     int64_t sel = 0;
-    for (int32_t c = 0; c < n_containers[p]; ++c) {
-      const int64_t b = (int64_t)p * max_containers + c;
-      if ((req_mask[b] & ~PAS_REQ_UNKNOWN_KIND) >> Q) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": mask bit >= n_res");
-      if (!release) continue;
+    for (int32_t c = 0; release && c < n_containers[p]; ++c) {
       if (counts) {
         int64_t kc = 0;
         for (int32_t k = 0; k < K; ++k) {
@@ -909,34 +949,28 @@ static int gas_commit(pas_ctx* ctx, bool release, uint64_t gen_from, uint64_t ge
   }
   std::stable_sort(order.begin(), order.end(),
                    [&](int32_t a, int32_t b) { return op_node[a] < op_node[b]; });
-  std::vector<int32_t> seg_off;
-  for (int32_t i = 0; i < n_ops; ++i)
-    if (i == 0 || op_node[order[(size_t)i]] != op_node[order[(size_t)i - 1]])
-      seg_off.push_back(i);
-  const int32_t n_seg = (int32_t)seg_off.size();
-  seg_off.push_back(n_ops);
+  std::vector<uint32_t> key((size_t)n_ops);  // the sorted keys: one run per node
+  for (int32_t i = 0; i < n_ops; ++i) key[(size_t)i] = (uint32_t)op_node[order[(size_t)i]];
   if ((rc = activate(ctx))) return rc;
   const size_t C = (size_t)std::max(max_containers, 1);
   const size_t ops = (size_t)std::max(n_ops, 1);
   const size_t pods = (size_t)std::max(n_pods, 1);
   const size_t b_req = sizeof(int64_t) * pods * C * Q, b_mask = sizeof(uint32_t) * pods * C;
   const size_t b_nc = sizeof(int32_t) * pods, b_op = sizeof(int32_t) * ops;
-  const size_t b_seg = sizeof(int32_t) * (size_t)(n_seg + 1);
   const size_t b_cpc = sizeof(int32_t) * ops * C;
   const size_t b_cards = sizeof(int32_t) * ops * (size_t)cards_stride;
   const size_t b_sel = cards_out ? ops * PAS_GAS_MAX_SELECTIONS : 1;
   const size_t b_cnt = (counts || counts_out) ? sizeof(int64_t) * ops * C * (size_t)K : 8;
-  if ((rc = ensure_scratch(ctx, carve_size({b_req, b_mask, b_nc, b_op, b_op, b_op, b_seg, b_cpc,
-                                            b_cards, b_op, b_op, b_sel, b_op, b_cnt}))))
+  if ((rc = ensure_scratch(ctx, carve_size({b_req, b_mask, b_nc, b_op, b_op, b_op, b_cpc, b_cards,
+                                            b_op, b_op, b_sel, b_op, b_cnt}))))
     return rc;
   Carve cv{static_cast<char*>(ctx->scratch)};
   int64_t* d_req = cv.take<int64_t>(pods * C * Q);
   uint32_t* d_mask = cv.take<uint32_t>(pods * C);
   int32_t* d_nc = cv.take<int32_t>(pods);
   int32_t* d_pod = cv.take<int32_t>(ops);
-  int32_t* d_node = cv.take<int32_t>(ops);
   int32_t* d_order = cv.take<int32_t>(ops);
-  int32_t* d_seg = cv.take<int32_t>((size_t)n_seg + 1);
+  uint32_t* d_key = cv.take<uint32_t>(ops);
   int32_t* d_cpc = cv.take<int32_t>(ops * C);
   int32_t* d_cards = cv.take<int32_t>(ops * (size_t)cards_stride);
   uint32_t* d_res = cv.take<uint32_t>(ops);
@@ -955,9 +989,8 @@ static int gas_commit(pas_ctx* ctx, bool release, uint64_t gen_from, uint64_t ge
     PAS_HIP(ctx, hipMemcpyAsync(d_nc, n_containers, sizeof(int32_t) * n_pods,
                                 hipMemcpyHostToDevice, s));
     PAS_HIP(ctx, hipMemcpyAsync(d_pod, op_pod, b_op, hipMemcpyHostToDevice, s));
-    PAS_HIP(ctx, hipMemcpyAsync(d_node, op_node, b_op, hipMemcpyHostToDevice, s));
     PAS_HIP(ctx, hipMemcpyAsync(d_order, order.data(), b_op, hipMemcpyHostToDevice, s));
-    PAS_HIP(ctx, hipMemcpyAsync(d_seg, seg_off.data(), b_seg, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_key, key.data(), b_op, hipMemcpyHostToDevice, s));
     if (release && counts) {
       if (max_containers > 0 && K > 0)
         PAS_HIP(ctx, hipMemcpyAsync(d_cnt, counts, b_cnt, hipMemcpyHostToDevice, s));
@@ -967,26 +1000,20 @@ static int gas_commit(pas_ctx* ctx, bool release, uint64_t gen_from, uint64_t ge
                                     hipMemcpyHostToDevice, s));
       PAS_HIP(ctx, hipMemcpyAsync(d_cards, cards, b_cards, hipMemcpyHostToDevice, s));
     }
-    if ((rc = gas_commit_launch(ctx, release, n_seg, max_containers, i915_index, d_order, d_seg,
-                                d_pod, d_node, d_req, d_mask, d_nc, d_cpc, d_cards,
-                                cards_stride, d_res, d_status, cards_out ? d_sel : nullptr,
+    if ((rc = gas_commit_launch(ctx, release, n_ops, max_containers, i915_index, d_order, d_key,
+                                d_pod, d_req, d_mask, d_nc, d_cpc, d_cards, cards_stride, d_res,
+                                d_status, cards_out ? d_sel : nullptr,
                                 cards_out ? d_nsel : nullptr, counts_out ? d_cnt : nullptr,
                                 counts ? d_cnt : nullptr, s)))
       return rc;
-    if (!release)
-      PAS_HIP(ctx, hipMemcpyAsync(res_out, d_res, b_op, hipMemcpyDeviceToHost, s));
-    if (counts_out && max_containers > 0 && K > 0)
-      PAS_HIP(ctx, hipMemcpyAsync(counts_out, d_cnt, b_cnt, hipMemcpyDeviceToHost, s));
-    if (cards_out) {
-      PAS_HIP(ctx, hipMemcpyAsync(cards_out, d_sel, b_sel, hipMemcpyDeviceToHost, s));
-      PAS_HIP(ctx, hipMemcpyAsync(nsel_out, d_nsel, b_op, hipMemcpyDeviceToHost, s));
-    }
-    PAS_HIP(ctx, hipMemcpyAsync(status_out, d_status, b_op, hipMemcpyDeviceToHost, s));
   }
-  PAS_HIP(ctx, hipStreamSynchronize(s));
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
+  return gas_write_finish(
+      ctx, gen_to, n_ops > 0, s, fn,
+      {{release ? nullptr : res_out, d_res, b_op},
+       {max_containers > 0 && K > 0 ? counts_out : nullptr, d_cnt, b_cnt},
+       {cards_out, d_sel, b_sel},
+       {cards_out ? nsel_out : nullptr, d_nsel, b_op},
+       {status_out, d_status, b_op}});
 }
 
 int pas_gas_bind(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_binds,
@@ -1103,9 +1130,7 @@ int pas_gas_apply_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
                              d_cards_per_container, d_cards, cards_ld, d_status_out,
                              pick_stream(ctx, hip_stream))))
     return rc;
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
+  return gas_stepped(ctx, gen_to);
 }
 
 int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
@@ -1127,12 +1152,10 @@ int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_ev
     if (ev_node[e] < 0 || ev_node[e] >= N || ev_pod[e] < 0 || ev_pod[e] >= n_pods)
       return set_error(ctx, PAS_EINVAL, fn + ": node or pod index out of range");
     const int32_t p = ev_pod[e];
-    if (n_containers[p] < 0 || n_containers[p] > max_containers)
-      return set_error(ctx, PAS_EINVAL, fn + ": n_containers out of range");
+    if ((rc = gas_pod_check(ctx, p, max_containers, req_mask, n_containers, fn.c_str())))
+      return rc;
     int64_t sel = 0;
     for (int32_t c = 0; c < n_containers[p]; ++c) {
-      if ((req_mask[(int64_t)p * max_containers + c] & ~PAS_REQ_UNKNOWN_KIND) >> Q)
-        return set_error(ctx, PAS_EINVAL, fn + ": mask bit >= n_res");
       const int64_t v = cards_per_container[(int64_t)e * max_containers + c];
       if (v < 0) return set_error(ctx, PAS_EINVAL, fn + ": negative card count");
       sel += v;  // at most max_containers * INT32_MAX
@@ -1175,20 +1198,8 @@ int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_ev
     if ((rc = gas_apply_launch(ctx, n_events, d_kind, d_pod, d_node, n_pods, max_containers,
                                d_req, d_mask, d_nc, d_cpc, d_cards, cards_ld, d_status, s)))
       return rc;
-    // the kernel is enqueued: a failure from here on leaves a snapshot of unknown content
-    const hipError_t e = [&] {
-      hipError_t r = hipMemcpyAsync(status_out, d_status, b_ev, hipMemcpyDeviceToHost, s);
-      if (r == hipSuccess) r = hipStreamSynchronize(s);
-      return r;
-    }();
-    if (e != hipSuccess) {
-      ctx->gas.valid = false;
-      return check_hip(ctx, e, "pas_gas_apply: copy of the statuses");
-    }
   }
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
+  return gas_write_finish(ctx, gen_to, n_events > 0, s, fn, {{status_out, d_status, b_ev}});
 }
 
 // What pas_gas_place and pas_gas_place_device share: the checks a host can make on either
@@ -1222,9 +1233,7 @@ static int gas_place_finish(pas_ctx* ctx, int rc, bool began, uint64_t gen_to) {
     }
     return rc;
   }
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
+  return gas_stepped(ctx, gen_to);
 }
 
 int pas_gas_place_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_pods,
@@ -1263,13 +1272,8 @@ int pas_gas_place(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_po
                            cards_out, n_sel_out, fn);
   if (rc) return rc;
   const int32_t Q = ctx->gas.n_res, K = ctx->gas.max_cards;
-  for (int32_t p = 0; p < n_pods; ++p) {
-    if (n_containers[p] < 0 || n_containers[p] > max_containers)
-      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": n_containers out of range");
-    for (int32_t c = 0; c < n_containers[p]; ++c)
-      if ((req_mask[(int64_t)p * max_containers + c] & ~PAS_REQ_UNKNOWN_KIND) >> Q)
-        return set_error(ctx, PAS_EINVAL, std::string(fn) + ": mask bit >= n_res");
-  }
+  for (int32_t p = 0; p < n_pods; ++p)
+    if ((rc = gas_pod_check(ctx, p, max_containers, req_mask, n_containers, fn))) return rc;
   if ((rc = activate(ctx))) return rc;
   const size_t P = (size_t)n_pods, C = (size_t)max_containers;
   const bool counts = counts_out && C > 0;
@@ -1398,9 +1402,7 @@ int pas_gas_nodes_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to
   if ((rc = gas_nodes_update_launch(ctx, n_updates, d_upd_node, d_upd_n_cards, d_upd_cap,
                                     d_upd_src, d_status_out, pick_stream(ctx, hip_stream))))
     return rc;
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
+  return gas_stepped(ctx, gen_to);
 }
 
 int pas_gas_nodes_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_updates,
@@ -1446,20 +1448,8 @@ int pas_gas_nodes_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
     // the _device form's path: grouping and the rows' rewrite on the device
     if ((rc = gas_nodes_update_launch(ctx, n_updates, d_node, d_nc, d_cap, d_src, d_status, s)))
       return rc;
-    // the kernel is enqueued: a failure from here on leaves a snapshot of unknown content
-    const hipError_t e = [&] {
-      hipError_t r = hipMemcpyAsync(status_out, d_status, b_u, hipMemcpyDeviceToHost, s);
-      if (r == hipSuccess) r = hipStreamSynchronize(s);
-      return r;
-    }();
-    if (e != hipSuccess) {
-      ctx->gas.valid = false;
-      return check_hip(ctx, e, "pas_gas_nodes_update: copy of the statuses");
-    }
   }
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
+  return gas_write_finish(ctx, gen_to, n_updates > 0, s, fn, {{status_out, d_status, b_u}});
 }
 
 int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
@@ -1535,14 +1525,8 @@ static int gas_fit_host(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_t max_
       (side_cap > 0 && !side))
     return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
   // Validate the batch (no limit on card selections: see PAS_GAS_SEL_LIMIT)
-  for (int32_t p = 0; p < n_pods; ++p) {
-    if (n_containers[p] < 0 || n_containers[p] > max_containers)
-      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": n_containers out of range");
-    for (int32_t c = 0; c < n_containers[p]; ++c) {
-      const int64_t b = (int64_t)p * max_containers + c;
-      if ((req_mask[b] & ~PAS_REQ_UNKNOWN_KIND) >> Q) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": mask bit >= n_res");
-    }
-  }
+  for (int32_t p = 0; p < n_pods; ++p)
+    if ((rc = gas_pod_check(ctx, p, max_containers, req_mask, n_containers, fn))) return rc;
   if ((rc = activate(ctx))) return rc;
   const int64_t N = ctx->gas.n_nodes;
   const size_t C = (size_t)std::max(max_containers, 1);

@@ -190,9 +190,11 @@ enum SlotBuf {
   kBufMerge = 1,  // cut list and ping-pong rows of the full-list merge (tas_list_merge.hip)
   kBufLabel = 2,  // per-workgroup partial counts of the label plan (tas_labels.hip)
   kBufPlace = 3,  // cursors, keys, blockers and sort storage of a placement (gas_place.hip)
-  kBufApply = 4,  // sort keys, event order and sort storage of an event batch (gas_commit.hip)
-  kBufNodes = 5,  // the same of a batch of node updates (gas_nodes.hip)
-  kSlotBufs = 6
+  // sort keys, item order and sort storage of a batch grouped by node (gas_group.h): one
+  // buffer for pod events and node updates, since two calls on one slot are ordered (stream
+  // order, or the slot's event), so a batch never finds the other's storage still in use
+  kBufRuns = 4,
+  kSlotBufs = 5
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -392,26 +394,28 @@ int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t wi
 int topk_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t k, int32_t n_shards,
                       const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
                       int32_t* d_out_node, int32_t* d_out_len, hipStream_t s);
-// Bind (fit + commit, release = false) or release of operations grouped by node: order =
-// operation indices sorted by node (stable), seg_off [n_seg + 1] the node segments.
-int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_seg, int32_t max_containers,
-                      int32_t i915_index, const int32_t* d_order, const int32_t* d_seg_off,
-                      const int32_t* d_pod, const int32_t* d_node, const int64_t* d_req,
-                      const uint32_t* d_mask, const int32_t* d_ncont, const int32_t* d_cpc,
-                      const int32_t* d_cards, int32_t cards_stride, uint32_t* d_res,
-                      int32_t* d_status, uint8_t* d_cards_out, int32_t* d_nsel_out,
-                      int64_t* d_counts_out, const int64_t* d_counts, hipStream_t s);
-// Pod events (pas_gas_apply[_device]) on device arrays: grouped by node on the device (stable
-// radix sort, storage from the stream's slot) and applied in call order, all enqueued on s.
-// Nothing of the snapshot has changed when it returns an error.
+// Bind (fit + commit, release = false) or release of n_ops operations the host grouped by
+// node: order = the operation indices sorted by node (stable), key[i] = the node of operation
+// order[i] (all in range).  The walker kernel of the event path applies them (gas_commit.hip).
+int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_ops, int32_t max_containers,
+                      int32_t i915_index, const int32_t* d_order, const uint32_t* d_key,
+                      const int32_t* d_pod, const int64_t* d_req, const uint32_t* d_mask,
+                      const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
+                      int32_t cards_stride, uint32_t* d_res, int32_t* d_status,
+                      uint8_t* d_cards_out, int32_t* d_nsel_out, int64_t* d_counts_out,
+                      const int64_t* d_counts, hipStream_t s);
+// Pod events (pas_gas_apply[_device]) on device arrays: grouped by node on the device
+// (NodeRuns, gas_group.h: storage from the stream's slot) and applied in call order by the
+// walker kernel, all enqueued on s.  Nothing of the snapshot has changed when it returns an
+// error.
 int gas_apply_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
                      const int32_t* d_pod, const int32_t* d_node, int32_t n_pods,
                      int32_t max_containers, const int64_t* d_req, const uint32_t* d_mask,
                      const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
                      int32_t cards_ld, int32_t* d_status, hipStream_t s);
 // Node updates (pas_gas_nodes_update[_device], gas_nodes.hip) on device arrays: grouped by node
-// on the device and applied in call order, all enqueued on s.  Nothing of the snapshot has
-// changed when it returns an error.
+// on the device (NodeRuns, gas_group.h) and applied in call order, all enqueued on s.  Nothing
+// of the snapshot has changed when it returns an error.
 int gas_nodes_update_launch(pas_ctx* ctx, int32_t n_updates, const int32_t* d_node,
                             const int32_t* d_n_cards, const int64_t* d_cap,
                             const int32_t* d_src, int32_t* d_status, hipStream_t s);

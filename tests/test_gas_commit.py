@@ -263,3 +263,113 @@ def test_unknown_kind_bind_release(ctx, oracle):
     np.testing.assert_array_equal(st2, w_st2)
     _, back = ctx.gas_snapshot_get()
     np.testing.assert_array_equal(back, w_back)
+
+
+# The walker elects a node's owner among the sorted positions of a workgroup (gas_group.h): 64
+# positions for bind and release, 1 024 for events, so a run may straddle two workgroups and a
+# head may be a workgroup's first position.  Node counts (c0, c1, c2) put node 0's run at
+# positions [0, c0), node 1's behind it and node 2's last, whatever the call order (the host
+# sort is stable).  The positions named are boundaries at either width (1 024 = 16 x 64).
+_WALK_LAYOUTS = [
+    (1020, 8, 2),  # node 1's run covers 1 020-1 027 across the boundary, node 2's head is 1 028
+    (1024, 4, 2),  # node 1's head is position 1 024, a workgroup's first
+    (1020, 4, 0),  # n = 1 024: the grid's edge, full workgroups only
+    (1020, 4, 1),  # n = 1 025: the last workgroup holds one position, a head
+    (64, 3, 61),   # the same at the first 64-position boundary: a head at 64, n = 128
+]
+
+
+def _walk_case(counts, seed):
+    """3 nodes x 2 cards x 1 kind (i915), pods asking 1, 2 or 3 GPUs, and sum(counts)
+    operations in shuffled call order with counts[n] of them on node n."""
+    rng = np.random.default_rng(seed)
+    n_cards = np.full(3, 2, np.int32)
+    req = np.array([[[1]], [[2]], [[3]]], np.int64)
+    mask = np.ones((3, 1), np.uint32)
+    ncont = np.ones(3, np.int32)
+    nodes = rng.permutation(np.repeat(np.arange(3, dtype=np.int32), counts))
+    pods = rng.integers(0, 3, size=len(nodes)).astype(np.int32)
+    return n_cards, req, mask, ncont, pods, nodes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("counts", _WALK_LAYOUTS)
+def test_bind_runs_across_workgroups(ctx, oracle, counts):
+    n_cards, req, mask, ncont, pods, nodes = _walk_case(counts, 41)
+    # per-card capacities small enough that every node turns binds away (the outcome of a
+    # bind depends on the ones before it in call order: a 3-GPU pod fails where a later
+    # 1-GPU pod still fits)
+    cap = np.array([[300], [3], [1]], np.int64)
+    used = np.zeros((3, 2, 1), np.int64)
+    w_used, w_res, w_st = oracle.gas_bind(n_cards, cap, used, req, mask, ncont, 0, pods, nodes)
+    assert (w_st == pas_amd._lib.PAS_GAS_OK).any()
+    assert (w_st == pas_amd._lib.PAS_GAS_WONT_FIT).any()
+    gen = _upload(ctx, n_cards, cap, used)
+    res, st = ctx.gas_bind(gen, gen + 1, pods, nodes, req, mask, ncont, 0)
+    np.testing.assert_array_equal(st, w_st)
+    np.testing.assert_array_equal(res, w_res)
+    _, after = ctx.gas_snapshot_get()
+    np.testing.assert_array_equal(after, w_used)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("counts", _WALK_LAYOUTS)
+def test_release_runs_across_workgroups(ctx, oracle, counts):
+    n_cards, req, mask, ncont, pods, nodes = _walk_case(counts, 43)
+    # room for every bind; a usage of 5 before them, so a release applied twice or to the
+    # wrong node shows in the usage instead of clamping at zero
+    cap = np.full((3, 1), 4000, np.int64)
+    used = np.full((3, 2, 1), 5, np.int64)
+    gen = _upload(ctx, n_cards, cap, used)
+    res, st = ctx.gas_bind(gen, gen + 1, pods, nodes, req, mask, ncont, 0)
+    w_used, w_res, w_st = oracle.gas_bind(n_cards, cap, used, req, mask, ncont, 0, pods, nodes)
+    assert (w_st == pas_amd._lib.PAS_GAS_OK).all()
+    np.testing.assert_array_equal(res, w_res)
+    cpc = np.zeros((len(pods), 1), np.int32)
+    cards = np.zeros((len(pods), 8), np.int32)
+    for b in range(len(pods)):
+        cpc[b], cards[b] = annotation_cards(res[b], req[pods[b]], mask[pods[b]], 1, 0)
+    bad = int(np.nonzero(nodes == 1)[0][-1])  # the last operation of node 1's run
+    cards[bad, 0] = 5  # a card outside the label
+    st2 = ctx.gas_release(gen + 1, gen + 2, pods, nodes, req, mask, ncont, cpc, cards)
+    w_back, w_st2 = oracle.gas_release(n_cards, w_used, req, mask, ncont, pods, nodes, cpc, cards)
+    assert w_st2[bad] == pas_amd._lib.PAS_GAS_ERR_INPUT
+    assert (np.delete(w_st2, bad) == pas_amd._lib.PAS_GAS_OK).all()
+    np.testing.assert_array_equal(st2, w_st2)
+    _, back = ctx.gas_snapshot_get()
+    np.testing.assert_array_equal(back, w_back)
+
+
+@pytest.mark.gpu
+def test_host_sort_keys_and_order_agree(ctx, oracle):
+    # The host sorts the operations by node and uploads the sorted keys beside the order.  Call
+    # order with descending node ids, so the sort must reorder, and results that tell the nodes
+    # and the call order apart: node 1 holds 4 GPUs, so the 3-GPU pod fits and the 2-GPU pod
+    # behind it does not (it would if it ran first, or on its own); node 0 holds 2.
+    n_cards = np.array([1, 2], np.int32)
+    cap = np.array([[2], [2]], np.int64)
+    used = np.zeros((2, 2, 1), np.int64)
+    req = np.array([[[3]], [[2]]], np.int64)
+    mask = np.ones((2, 1), np.uint32)
+    ncont = np.ones(2, np.int32)
+    pods, nodes = [0, 1, 1], [1, 1, 0]
+    w_used, w_res, w_st = oracle.gas_bind(n_cards, cap, used, req, mask, ncont, 0, pods, nodes)
+    assert list(w_st) == [pas_amd._lib.PAS_GAS_OK, pas_amd._lib.PAS_GAS_WONT_FIT,
+                          pas_amd._lib.PAS_GAS_OK]
+    gen = _upload(ctx, n_cards, cap, used)
+    res, st = ctx.gas_bind(gen, gen + 1, pods, nodes, req, mask, ncont, 0)
+    np.testing.assert_array_equal(st, w_st)
+    np.testing.assert_array_equal(res, w_res)
+    _, after = ctx.gas_snapshot_get()
+    np.testing.assert_array_equal(after, w_used)
+    # releases naming card 1: a label card on node 1, outside the label on node 0
+    cpc = np.ones((3, 1), np.int32)
+    cards = np.zeros((3, 8), np.int32)
+    cards[:, 0] = 1
+    st2 = ctx.gas_release(gen + 1, gen + 2, pods, nodes, req, mask, ncont, cpc, cards)
+    w_back, w_st2 = oracle.gas_release(n_cards, w_used, req, mask, ncont, pods, nodes, cpc, cards)
+    assert list(w_st2) == [pas_amd._lib.PAS_GAS_OK, pas_amd._lib.PAS_GAS_OK,
+                           pas_amd._lib.PAS_GAS_ERR_INPUT]
+    np.testing.assert_array_equal(st2, w_st2)
+    _, back = ctx.gas_snapshot_get()
+    np.testing.assert_array_equal(back, w_back)
