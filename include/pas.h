@@ -282,6 +282,54 @@ int pas_tas_prioritize_request_device(pas_ctx* ctx, uint64_t gen, const pas_rule
                                       int32_t* d_pos_out, int32_t* d_len_out,
                                       void* hip_stream);
 
+/* The extender verbs for a BATCH of R requests, each with its own node list, in request
+ * terms (micro-batched concurrent requests).  Shared by the three
+ * families below (pas_tas_prioritize_requests, pas_tas_filter_requests,
+ * pas_gas_fit_requests):
+ *   req_off  [R + 1]  HOST array in both forms: request r lists req_off[r + 1] - req_off[r]
+ *                     nodes.  req_off[0] = 0, non-decreasing, T = req_off[R] <= INT32_MAX
+ *                     (else PAS_EINVAL).  R = 0 and empty requests are valid.
+ *   req_node [T]      the requests' snapshot node ids back to back, as pas_decode_args
+ *                     writes them; a value outside [0, n_nodes) = a node the snapshot does
+ *                     not hold.  No kernel reads outside its arrays, whatever it holds.
+ * Bitmap outputs have a row pitch: request r's row is out[r * ld_words ..), ld_words >=
+ * W64(longest request).  Bit j belongs to request position j; bits at and past the request's
+ * length are written 0 up to W64(n_req_r) words, words past that are left untouched.  A row
+ * is what pas_encode_tas_filter_result / pas_encode_gas_filter_result take with req_node =
+ * 0 .. n - 1.  The _device forms take device req_node / outputs, draw their workspace from
+ * the stream's slot and are asynchronous on hip_stream (apart from the copy of their host
+ * arrays).  Nothing resident is written and no generation moves.
+ *
+ * pas_tas_prioritize_requests: request r gets exactly the output of
+ * pas_tas_prioritize_request(gen, &prio[r], n_r, req_node + req_off[r], ..): request-local
+ * positions at pos_out[req_off[r] + i], -1 past len_out[r].  prio [R] is a host array in
+ * both forms; prio[r].metric < 0 = empty list, >= n_metrics PAS_EINVAL.  Two requests of one
+ * batch that list the same node do not see each other. */
+int pas_tas_prioritize_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                const int32_t* req_off, const pas_rule* prio,
+                                const int32_t* req_node, int32_t* pos_out, int32_t* len_out);
+int pas_tas_prioritize_requests_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                       const int32_t* req_off, const pas_rule* prio,
+                                       const int32_t* d_req_node, int32_t* d_pos_out,
+                                       int32_t* d_len_out, void* hip_stream);
+
+/* pas_tas_filter_requests: MetricsExtender.filterNodes per request.  Bit j of request r's
+ * row is set iff the node at position j is unknown to the snapshot or violates none of the
+ * request's dontschedule rules rules[rule_off[r] .. rule_off[r + 1]) (pas_tas_eval's rule
+ * semantics: a metric that is not cached or that the node lacks skips the rule).  A repeated
+ * node keeps its verdict at every position.  The host form validates the CSR and the
+ * operators as pas_tas_eval does; the _device form reads d_rule_off clamped into
+ * [0, n_rules] and skips unknown operators, as pas_tas_eval_device. */
+int pas_tas_filter_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                            const int32_t* req_off, const pas_rule* rules,
+                            const int32_t* rule_off, const int32_t* req_node,
+                            uint64_t* pass_out, int64_t ld_words);
+int pas_tas_filter_requests_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                   const int32_t* req_off, int32_t n_rules,
+                                   const pas_rule* d_rules, const int32_t* d_rule_off,
+                                   const int32_t* d_req_node, uint64_t* d_pass_out,
+                                   int64_t ld_words, void* hip_stream);
+
 /* Deschedule sweep: for each registered deschedule strategy s (rules
  * rules[rule_off[s] .. rule_off[s+1])), the node set of deschedule.Strategy.Violated
  * (deschedule/strategy.go:31-50), as the bitmap viol_out[s][W64].  The per-node
@@ -485,6 +533,23 @@ int pas_gas_fit_bitmap_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_
                               int32_t i915_index, const int64_t* d_req,
                               const uint32_t* d_req_mask, const int32_t* d_n_containers,
                               uint64_t* d_fit_out, void* hip_stream);
+
+/* GAS filter of a batch of requests in request terms (the conventions of
+ * pas_tas_prioritize_requests above): pod r (row r of req / req_mask / n_containers, as
+ * pas_gas_fit) is request r's pod.  Bit j of request r's row = bit 31 of the pas_gas_fit
+ * word of (pod r, node req_node[req_off[r] + j]), 0 for a node the snapshot does not hold
+ * (the FetchNode error).  Any number of selections, every card count and
+ * PAS_REQ_UNKNOWN_KIND mean what they mean to pas_gas_fit.  The host form validates as
+ * pas_gas_fit; the _device form clamps n_containers as pas_gas_fit_device. */
+int pas_gas_fit_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests, const int32_t* req_off,
+                         const int32_t* req_node, int32_t max_containers, int32_t i915_index,
+                         const int64_t* req, const uint32_t* req_mask,
+                         const int32_t* n_containers, uint64_t* fit_out, int64_t ld_words);
+int pas_gas_fit_requests_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                const int32_t* req_off, const int32_t* d_req_node,
+                                int32_t max_containers, int32_t i915_index, const int64_t* d_req,
+                                const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                uint64_t* d_fit_out, int64_t ld_words, void* hip_stream);
 
 /* Bind-time commit (GASExtender.bindNode, scheduler.go:385-445): for binds b in call order,
  * pod bind_pod[b] (an index into the req / req_mask / n_containers batch, as pas_gas_fit)

@@ -695,6 +695,183 @@ int pas_tas_prioritize_request_device(pas_ctx* ctx, uint64_t gen, const pas_rule
                              s);
 }
 
+// ------------------------------------------------------- batches of requests in request terms
+
+// The requests of a *_requests call: R >= 0, req_off [R + 1] a CSR from 0 (its total is an
+// int32, so at most INT32_MAX), req_node given when any request names a node.  *longest = the
+// longest request.
+static int check_requests(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
+                          const void* req_node, const char* fn, int32_t* longest) {
+  *longest = 0;
+  if (n_requests < 0) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": negative count");
+  if (n_requests == 0) return PAS_OK;
+  if (!req_off) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null req_off");
+  int rc = validate_csr(ctx, n_requests, req_off, "req_off");
+  if (rc) return rc;
+  if (req_off[n_requests] > 0 && !req_node)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null req_node");
+  for (int32_t r = 0; r < n_requests; ++r)
+    *longest = std::max(*longest, req_off[r + 1] - req_off[r]);
+  return PAS_OK;
+}
+
+// A bitmap output of a *_requests call: rows of ld_words >= W64(longest request).
+static int check_request_rows(pas_ctx* ctx, int32_t longest, const void* out, int64_t ld_words,
+                              const char* fn) {
+  if (ld_words < w64(longest))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": ld_words < W64(longest request)");
+  if (longest > 0 && !out) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null output");
+  return PAS_OK;
+}
+
+// The rows a *_requests kernel wrote at pitch ld_dev, copied into the caller's rows of pitch
+// ld_words: the W64(n_r) words of request r, nothing past them.
+static int fetch_request_rows(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
+                              const uint64_t* d_rows, int64_t ld_dev, uint64_t* out,
+                              int64_t ld_words, hipStream_t s) {
+  std::vector<uint64_t> rows((size_t)(n_requests * ld_dev));
+  if (!rows.empty())
+    PAS_HIP(ctx, hipMemcpyAsync(rows.data(), d_rows, sizeof(uint64_t) * rows.size(),
+                                hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  for (int32_t r = 0; r < n_requests; ++r)
+    std::copy_n(rows.data() + r * ld_dev, w64(req_off[r + 1] - req_off[r]), out + r * ld_words);
+  return PAS_OK;
+}
+
+static int check_prio_requests(pas_ctx* ctx, int32_t n_requests, const pas_rule* prio,
+                               int32_t total, const void* pos, const void* len) {
+  if (n_requests == 0) return PAS_OK;
+  if (!prio || !len || (total > 0 && !pos))
+    return set_error(ctx, PAS_EINVAL, "pas_tas_prioritize_requests: null argument");
+  for (int32_t r = 0; r < n_requests; ++r)
+    if (prio[r].metric >= ctx->tas.n_metrics)
+      return set_error(ctx, PAS_EINVAL, "pas_tas_prioritize_requests: request " +
+                                            std::to_string(r) + ": metric out of range");
+  return PAS_OK;
+}
+
+int pas_tas_prioritize_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                const int32_t* req_off, const pas_rule* prio,
+                                const int32_t* req_node, int32_t* pos_out, int32_t* len_out) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  int32_t longest = 0;
+  if ((rc = check_requests(ctx, n_requests, req_off, req_node, "pas_tas_prioritize_requests",
+                           &longest)))
+    return rc;
+  if (n_requests == 0) return PAS_OK;
+  const int32_t T = req_off[n_requests];
+  if ((rc = check_prio_requests(ctx, n_requests, prio, T, pos_out, len_out))) return rc;
+  if ((rc = activate(ctx))) return rc;
+  const size_t b_req = sizeof(int32_t) * (size_t)std::max(T, 1);
+  const size_t b_len = sizeof(int32_t) * (size_t)n_requests;
+  if ((rc = ensure_scratch(ctx, carve_size({b_req, b_req, b_len})))) return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int32_t* d_req = cv.take<int32_t>(std::max(T, 1));
+  int32_t* d_pos = cv.take<int32_t>(std::max(T, 1));
+  int32_t* d_len = cv.take<int32_t>(n_requests);
+  hipStream_t s = ctx->stream;
+  if (T) PAS_HIP(ctx, hipMemcpyAsync(d_req, req_node, b_req, hipMemcpyHostToDevice, s));
+  HostStage stage;  // until the synchronize below
+  if ((rc = prio_requests_launch(ctx, n_requests, req_off, prio, d_req, d_pos, d_len, &stage,
+                                 s))) {
+    (void)hipStreamSynchronize(s);  // a copy from the stage may be in flight
+    return rc;
+  }
+  PAS_HIP(ctx, hipMemcpyAsync(len_out, d_len, b_len, hipMemcpyDeviceToHost, s));
+  if (T) PAS_HIP(ctx, hipMemcpyAsync(pos_out, d_pos, b_req, hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  return PAS_OK;
+}
+
+int pas_tas_prioritize_requests_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                       const int32_t* req_off, const pas_rule* prio,
+                                       const int32_t* d_req_node, int32_t* d_pos_out,
+                                       int32_t* d_len_out, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  int32_t longest = 0;
+  if ((rc = check_requests(ctx, n_requests, req_off, d_req_node,
+                           "pas_tas_prioritize_requests_device", &longest)))
+    return rc;
+  if (n_requests == 0) return PAS_OK;
+  if ((rc = check_prio_requests(ctx, n_requests, prio, req_off[n_requests], d_pos_out,
+                                d_len_out)))
+    return rc;
+  if ((rc = activate(ctx))) return rc;
+  return prio_requests_launch(ctx, n_requests, req_off, prio, d_req_node, d_pos_out, d_len_out,
+                              nullptr, pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_filter_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                            const int32_t* req_off, const pas_rule* rules,
+                            const int32_t* rule_off, const int32_t* req_node,
+                            uint64_t* pass_out, int64_t ld_words) {
+  const char* fn = "pas_tas_filter_requests";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  int32_t longest = 0;
+  if ((rc = check_requests(ctx, n_requests, req_off, req_node, fn, &longest))) return rc;
+  if (n_requests == 0) return PAS_OK;
+  if ((rc = check_request_rows(ctx, longest, pass_out, ld_words, fn))) return rc;
+  if (!rule_off) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null rule_off");
+  if ((rc = validate_csr(ctx, n_requests, rule_off, "rule_off"))) return rc;
+  const int32_t n_rules = rule_off[n_requests];
+  if (n_rules > 0 && !rules) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null rules");
+  // (before the empty-list return: Violated runs before filterNodes looks at the node list)
+  if ((rc = validate_rules(ctx, n_rules, rules))) return rc;
+  if (longest == 0) return PAS_OK;
+  if ((rc = activate(ctx))) return rc;
+  const int32_t T = req_off[n_requests];
+  const int64_t ld_dev = w64(longest);
+  const size_t b_req = sizeof(int32_t) * (size_t)T;
+  const size_t b_rules = sizeof(pas_rule) * (size_t)std::max(n_rules, 1);
+  const size_t b_off = sizeof(int32_t) * ((size_t)n_requests + 1);
+  const size_t b_rows = sizeof(uint64_t) * (size_t)(n_requests * ld_dev);
+  if ((rc = ensure_scratch(ctx, carve_size({b_req, b_rules, b_off, b_rows})))) return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int32_t* d_req = cv.take<int32_t>(T);
+  pas_rule* d_rules = cv.take<pas_rule>(std::max(n_rules, 1));
+  int32_t* d_off = cv.take<int32_t>((size_t)n_requests + 1);
+  uint64_t* d_rows = cv.take<uint64_t>((size_t)(n_requests * ld_dev));
+  hipStream_t s = ctx->stream;
+  PAS_HIP(ctx, hipMemcpyAsync(d_req, req_node, b_req, hipMemcpyHostToDevice, s));
+  if (n_rules) PAS_HIP(ctx, hipMemcpyAsync(d_rules, rules, b_rules, hipMemcpyHostToDevice, s));
+  PAS_HIP(ctx, hipMemcpyAsync(d_off, rule_off, b_off, hipMemcpyHostToDevice, s));
+  HostStage stage;  // (req_off is the caller's until fetch_request_rows has synchronized)
+  if ((rc = filter_requests_launch(ctx, n_requests, req_off, n_rules, d_rules, d_off, d_req,
+                                   d_rows, ld_dev, &stage, s))) {
+    (void)hipStreamSynchronize(s);  // the copy of req_off may be in flight
+    return rc;
+  }
+  return fetch_request_rows(ctx, n_requests, req_off, d_rows, ld_dev, pass_out, ld_words, s);
+}
+
+int pas_tas_filter_requests_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                   const int32_t* req_off, int32_t n_rules,
+                                   const pas_rule* d_rules, const int32_t* d_rule_off,
+                                   const int32_t* d_req_node, uint64_t* d_pass_out,
+                                   int64_t ld_words, void* hip_stream) {
+  const char* fn = "pas_tas_filter_requests_device";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  int32_t longest = 0;
+  if ((rc = check_requests(ctx, n_requests, req_off, d_req_node, fn, &longest))) return rc;
+  if (n_requests == 0) return PAS_OK;
+  if ((rc = check_request_rows(ctx, longest, d_pass_out, ld_words, fn))) return rc;
+  if (n_rules < 0 || !d_rule_off || (n_rules > 0 && !d_rules))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad rules");
+  if ((rc = activate(ctx))) return rc;
+  return filter_requests_launch(ctx, n_requests, req_off, n_rules, d_rules, d_rule_off,
+                                d_req_node, d_pass_out, ld_words, nullptr,
+                                pick_stream(ctx, hip_stream));
+}
+
 int pas_tas_violations(pas_ctx* ctx, uint64_t gen, int32_t n_strategies, const pas_rule* rules,
                        const int32_t* rule_off, uint64_t* viol_out) {
   if (!ctx) return PAS_EINVAL;
@@ -1673,6 +1850,87 @@ int pas_gas_fit_bitmap_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_
   return gas_fit_device_common(ctx, gen, n_pods, max_containers, i915_index, d_req, d_req_mask,
                                d_n_containers, nullptr, -1, d_fit_out, nullptr, 0, nullptr,
                                hip_stream, "pas_gas_fit_bitmap_device");
+}
+
+// What the two forms of pas_gas_fit_requests check alike; *longest = the longest request.
+static int check_gas_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                              const int32_t* req_off, const void* req_node,
+                              int32_t max_containers, int32_t i915_index, const void* req,
+                              const void* req_mask, const void* n_containers, const void* fit,
+                              int64_t ld_words, const char* fn, int32_t* longest) {
+  int rc = check_gas_gen(ctx, gen);
+  if (rc) return rc;
+  if (max_containers < 0 || i915_index >= ctx->gas.n_res || i915_index < -1)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  if ((rc = check_requests(ctx, n_requests, req_off, req_node, fn, longest))) return rc;
+  if (n_requests == 0) return PAS_OK;
+  if ((rc = check_request_rows(ctx, *longest, fit, ld_words, fn))) return rc;
+  if (!n_containers || (max_containers > 0 && (!req || !req_mask)))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  return PAS_OK;
+}
+
+int pas_gas_fit_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests, const int32_t* req_off,
+                         const int32_t* req_node, int32_t max_containers, int32_t i915_index,
+                         const int64_t* req, const uint32_t* req_mask,
+                         const int32_t* n_containers, uint64_t* fit_out, int64_t ld_words) {
+  const char* fn = "pas_gas_fit_requests";
+  if (!ctx) return PAS_EINVAL;
+  int32_t longest = 0;
+  int rc = check_gas_requests(ctx, gen, n_requests, req_off, req_node, max_containers,
+                              i915_index, req, req_mask, n_containers, fit_out, ld_words, fn,
+                              &longest);
+  if (rc || n_requests == 0) return rc;
+  for (int32_t p = 0; p < n_requests; ++p)
+    if ((rc = gas_pod_check(ctx, p, max_containers, req_mask, n_containers, fn))) return rc;
+  if (longest == 0) return PAS_OK;
+  if ((rc = activate(ctx))) return rc;
+  const int32_t T = req_off[n_requests], Q = ctx->gas.n_res;
+  const int64_t ld_dev = w64(longest);
+  const size_t C = (size_t)std::max(max_containers, 1);
+  const size_t b_node = sizeof(int32_t) * (size_t)T;
+  const size_t b_req = sizeof(int64_t) * (size_t)n_requests * C * Q;
+  const size_t b_mask = sizeof(uint32_t) * (size_t)n_requests * C;
+  const size_t b_nc = sizeof(int32_t) * (size_t)n_requests;
+  const size_t b_rows = sizeof(uint64_t) * (size_t)(n_requests * ld_dev);
+  if ((rc = ensure_scratch(ctx, carve_size({b_node, b_req, b_mask, b_nc, b_rows})))) return rc;
+  Carve cv{static_cast<char*>(ctx->scratch)};
+  int32_t* d_node = cv.take<int32_t>(T);
+  int64_t* d_req = cv.take<int64_t>((size_t)n_requests * C * Q);
+  uint32_t* d_mask = cv.take<uint32_t>((size_t)n_requests * C);
+  int32_t* d_nc = cv.take<int32_t>(n_requests);
+  uint64_t* d_rows = cv.take<uint64_t>((size_t)(n_requests * ld_dev));
+  hipStream_t s = ctx->stream;
+  PAS_HIP(ctx, hipMemcpyAsync(d_node, req_node, b_node, hipMemcpyHostToDevice, s));
+  if (max_containers > 0) {
+    PAS_HIP(ctx, hipMemcpyAsync(d_req, req, b_req, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_mask, req_mask, b_mask, hipMemcpyHostToDevice, s));
+  }
+  PAS_HIP(ctx, hipMemcpyAsync(d_nc, n_containers, b_nc, hipMemcpyHostToDevice, s));
+  HostStage stage;  // (req_off is the caller's until fetch_request_rows has synchronized)
+  if ((rc = gas_fit_requests_launch(ctx, n_requests, req_off, d_node, max_containers,
+                                    i915_index, d_req, d_mask, d_nc, d_rows, ld_dev, &stage, s))) {
+    (void)hipStreamSynchronize(s);  // the copy of req_off may be in flight
+    return rc;
+  }
+  return fetch_request_rows(ctx, n_requests, req_off, d_rows, ld_dev, fit_out, ld_words, s);
+}
+
+int pas_gas_fit_requests_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                const int32_t* req_off, const int32_t* d_req_node,
+                                int32_t max_containers, int32_t i915_index, const int64_t* d_req,
+                                const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                uint64_t* d_fit_out, int64_t ld_words, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int32_t longest = 0;
+  int rc = check_gas_requests(ctx, gen, n_requests, req_off, d_req_node, max_containers,
+                              i915_index, d_req, d_req_mask, d_n_containers, d_fit_out, ld_words,
+                              "pas_gas_fit_requests_device", &longest);
+  if (rc || n_requests == 0) return rc;
+  if ((rc = activate(ctx))) return rc;
+  return gas_fit_requests_launch(ctx, n_requests, req_off, d_req_node, max_containers,
+                                 i915_index, d_req, d_req_mask, d_n_containers, d_fit_out,
+                                 ld_words, nullptr, pick_stream(ctx, hip_stream));
 }
 
 // --------------------------------------------------------------------------- deschedule labels

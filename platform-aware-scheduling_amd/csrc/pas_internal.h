@@ -354,6 +354,28 @@ int prio_request_workspace(pas_ctx* ctx, int32_t n_req, size_t* bytes);  // stat
 int prio_request_launch(pas_ctx* ctx, const pas_rule& rule, int32_t n_req, const int32_t* d_req,
                         int32_t* d_pos, int32_t* d_len, void* ws, size_t ws_bytes,
                         hipStream_t s);
+// The verbs for a batch of requests in request terms (tas_request_batch.hip,
+// gas_fit_requests.hip): req_off [R + 1] and prio [R] are host arrays (a valid CSR, the
+// metrics below n_metrics), everything else is on the device; the workspace is the slot of s.
+// Enqueued on s.  stage == nullptr (the _device forms): the launch waits for the copy of the
+// host arrays, which are the caller's again on return.  Otherwise (the host forms, which
+// synchronize s before they return) nothing waits: the caller keeps req_off and *stage, where
+// the launch puts what it derives from the host arrays, until it has synchronized.
+struct HostStage {
+  std::vector<char> bytes;
+};
+int prio_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
+                         const pas_rule* prio, const int32_t* d_req, int32_t* d_pos,
+                         int32_t* d_len, HostStage* stage, hipStream_t s);
+int filter_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
+                           int32_t n_rules, const pas_rule* d_rules, const int32_t* d_rule_off,
+                           const int32_t* d_req, uint64_t* d_pass, int64_t ld_words,
+                           HostStage* stage, hipStream_t s);
+int gas_fit_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
+                            const int32_t* d_req_node, int32_t max_containers,
+                            int32_t i915_index, const int64_t* d_req, const uint32_t* d_mask,
+                            const int32_t* d_ncont, uint64_t* d_fit, int64_t ld_words,
+                            HostStage* stage, hipStream_t s);
 // (n_rules bounds the device rule_off: offsets are clamped into [0, n_rules], rule_span)
 int tas_violations_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,
                           const pas_rule* d_rules, const int32_t* d_rule_off, uint64_t* d_viol,

@@ -139,6 +139,16 @@ SIGNATURES = {
     "pas_tas_eval": (c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, c_uint32, _P, _P, _P]),
     "pas_tas_prioritize_request": (c_int, [_P, c_uint64, _P, c_int32, _P, _P, _P]),
     "pas_tas_prioritize_request_device": (c_int, [_P, c_uint64, _P, c_int32, _P, _P, _P, _P]),
+    "pas_tas_prioritize_requests": (c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, _P]),
+    "pas_tas_prioritize_requests_device": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, _P, _P]),
+    "pas_tas_filter_requests": (c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, _P, c_int64]),
+    "pas_tas_filter_requests_device": (
+        c_int, [_P, c_uint64, c_int32, _P, c_int32, _P, _P, _P, _P, c_int64, _P]),
+    "pas_gas_fit_requests": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P, _P, c_int64]),
+    "pas_gas_fit_requests_device": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P, _P, c_int64, _P]),
     "pas_tas_eval_device": (
         c_int,
         [_P, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_uint32, _P, _P, _P, _P],

@@ -345,6 +345,98 @@ class Context:
                                                        _stream(stream))
         self._check(rc, "pas_tas_prioritize_request_device")
 
+    # -- batches of requests in request terms (pas_tas_prioritize_requests and its kin):
+    # req_off [R + 1] is the CSR of the requests' node lists, req_node their snapshot ids
+    @staticmethod
+    def _requests(req_off, req_node):
+        req_off = np.ascontiguousarray(req_off, dtype=np.int32)
+        req_node = np.ascontiguousarray(req_node, dtype=np.int32)
+        lens = np.diff(req_off)
+        return req_off, req_node, len(req_off) - 1, int(lens.max(initial=0))
+
+    def tas_prioritize_requests(self, gen: int, req_off, prio, req_node):
+        """(pos [T] int32, len [R] int32): request r's positions best-first at
+        pos[req_off[r] : req_off[r] + len[r]], -1 after, each exactly
+        tas_prioritize_request's list for that request."""
+        req_off = np.ascontiguousarray(req_off, dtype=np.int32)
+        req_node = np.ascontiguousarray(req_node, dtype=np.int32)
+        prio = np.ascontiguousarray(prio, dtype=RULE_DTYPE)
+        r = len(req_off) - 1
+        assert prio.shape == (r,)
+        pos = np.empty(max(len(req_node), 1), np.int32)  # (the call writes every position)
+        lens = np.empty(max(r, 1), np.int32)
+        rc = self._l.pas_tas_prioritize_requests(self._h, gen, r, _ptr(req_off), _ptr(prio),
+                                                 _ptr(req_node), _ptr(pos), _ptr(lens))
+        self._check(rc, "pas_tas_prioritize_requests")
+        return pos[: len(req_node)], lens[:r]
+
+    def tas_prioritize_requests_device(self, gen: int, req_off, prio, req_t, pos_t, len_t,
+                                       stream=None):
+        req_off = np.ascontiguousarray(req_off, dtype=np.int32)
+        prio = np.ascontiguousarray(prio, dtype=RULE_DTYPE)
+        rc = self._l.pas_tas_prioritize_requests_device(
+            self._h, gen, len(req_off) - 1, _ptr(req_off), _ptr(prio), _dptr(req_t),
+            _dptr(pos_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_prioritize_requests_device")
+
+    def tas_filter_requests(self, gen: int, req_off, rules, rule_off, req_node,
+                            out: Optional[np.ndarray] = None) -> np.ndarray:
+        """pass [R][ld] uint64: bit j of row r = request r's node at position j is unknown to
+        the snapshot or violates none of rules[rule_off[r] : rule_off[r + 1]].  out: rows to
+        write into (pitch out.shape[1]); words past a request's own are left as they are."""
+        req_off, req_node, r, longest = self._requests(req_off, req_node)
+        rules = np.ascontiguousarray(rules, dtype=RULE_DTYPE)
+        rule_off = np.ascontiguousarray(rule_off, dtype=np.int32)
+        assert rule_off.shape == (r + 1,)
+        if out is None:
+            out = np.zeros((r, max(w64(longest), 1)), np.uint64)
+        assert out.dtype == np.uint64 and out.ndim == 2 and out.shape[0] == r
+        rc = self._l.pas_tas_filter_requests(self._h, gen, r, _ptr(req_off),
+                                             _ptr(rules) if rules.size else None,
+                                             _ptr(rule_off), _ptr(req_node), _ptr(out),
+                                             out.shape[1])
+        self._check(rc, "pas_tas_filter_requests")
+        return out
+
+    def tas_filter_requests_device(self, gen: int, req_off, n_rules: int, rules_t, rule_off_t,
+                                   req_t, pass_t, ld_words: int, stream=None):
+        req_off = np.ascontiguousarray(req_off, dtype=np.int32)
+        rc = self._l.pas_tas_filter_requests_device(
+            self._h, gen, len(req_off) - 1, _ptr(req_off), n_rules, _dptr(rules_t),
+            _dptr(rule_off_t), _dptr(req_t), _dptr(pass_t), ld_words, _stream(stream))
+        self._check(rc, "pas_tas_filter_requests_device")
+
+    def gas_fit_requests(self, gen: int, req_off, req_node, req: np.ndarray,
+                         req_mask: np.ndarray, n_containers: np.ndarray, i915_index: int,
+                         out: Optional[np.ndarray] = None) -> np.ndarray:
+        """fit [R][ld] uint64: bit j of row r = pod r fits request r's node at position j (bit
+        31 of the gas_fit word; 0 for a node the snapshot does not hold).  out as in
+        tas_filter_requests."""
+        req_off, req_node, r, longest = self._requests(req_off, req_node)
+        req = np.ascontiguousarray(req, dtype=np.int64)
+        p, c, q = req.shape
+        req_mask = np.ascontiguousarray(req_mask, dtype=np.uint32)
+        n_containers = np.ascontiguousarray(n_containers, dtype=np.int32)
+        assert p == r and req_mask.shape == (p, c) and n_containers.shape == (p,)
+        if out is None:
+            out = np.zeros((r, max(w64(longest), 1)), np.uint64)
+        assert out.dtype == np.uint64 and out.ndim == 2 and out.shape[0] == r
+        rc = self._l.pas_gas_fit_requests(self._h, gen, r, _ptr(req_off), _ptr(req_node), c,
+                                          i915_index, _ptr(req), _ptr(req_mask),
+                                          _ptr(n_containers), _ptr(out), out.shape[1])
+        self._check(rc, "pas_gas_fit_requests")
+        return out
+
+    def gas_fit_requests_device(self, gen: int, req_off, req_node_t, max_containers: int,
+                                i915_index: int, req_t, mask_t, ncont_t, fit_t, ld_words: int,
+                                stream=None):
+        req_off = np.ascontiguousarray(req_off, dtype=np.int32)
+        rc = self._l.pas_gas_fit_requests_device(
+            self._h, gen, len(req_off) - 1, _ptr(req_off), _dptr(req_node_t), max_containers,
+            i915_index, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), _dptr(fit_t), ld_words,
+            _stream(stream))
+        self._check(rc, "pas_gas_fit_requests_device")
+
     def tas_violations(self, gen: int, rules: np.ndarray, rule_off: np.ndarray) -> np.ndarray:
         rule_off = np.ascontiguousarray(rule_off, dtype=np.int32)
         s = rule_off.shape[0] - 1

@@ -78,6 +78,11 @@ def _op_code(op: str) -> int:
     return code if code >= 0 else 3
 
 
+def _offsets(lengths) -> np.ndarray:
+    """CSR offsets [R + 1] of R lists of the given lengths."""
+    return np.concatenate([[0], np.cumsum(list(lengths), dtype=np.int64)]).astype(np.int32)
+
+
 class MetricsExtender:
     """TAS extender: Filter / Prioritize / Bind (telemetryscheduler.go:36-244).
 
@@ -204,6 +209,82 @@ class MetricsExtender:
     def bind(self, body: bytes) -> Tuple[int, bytes]:
         return 404, b""  # not implemented by TAS (:178-181)
 
+    # -- a micro-batch of concurrent requests (INTEGRATION.md §3) -------------------
+    # Decoding and every early return stay per request, the rest of the batch is one library
+    # call in request terms, and each body is rendered from its row: byte for byte what the
+    # single verb answers, ties included.
+    def filter_batch(self, bodies: Sequence[bytes]) -> List[Tuple[int, bytes]]:
+        """[self.filter(b) for b in bodies] through one pas_tas_filter_requests call."""
+        out: List[Optional[Tuple[int, bytes]]] = [None] * len(bodies)
+        pend = []
+        for b, body in enumerate(bodies):
+            try:
+                info, idx, _, spans, policy_ref = self._decode(body)
+            except ValueError:
+                out[b] = (200, b"")
+                continue
+            policy = self._policy(policy_ref)
+            rules = (policy or {}).get("dontschedule") or []
+            if policy is None or not rules:
+                out[b] = (404, b"null\n")
+                continue
+            pend.append((b, info, idx, spans, self._rules(rules)))
+        if pend:
+            req_off = _offsets(len(p[2]) for p in pend)
+            rule_off = _offsets(len(p[4]) for p in pend)
+            try:
+                rows = self.ctx.tas_filter_requests(
+                    self.gen, req_off, np.concatenate([p[4] for p in pend]), rule_off,
+                    np.concatenate([p[2] for p in pend]))
+            except _lib.PasError as e:
+                if e.code == _lib.PAS_EINVAL and "unknown operator" in str(e):
+                    for p in pend:  # the first request whose own verb panics raises it
+                        self.filter(bodies[p[0]])
+                raise
+            for k, (b, info, idx, spans, _) in enumerate(pend):
+                if info.n_req == 0:
+                    out[b] = (404, b"null\n")
+                    continue
+                body = bodies[b]
+                blobs = [_compact(body[o:o + n]) for o, n in spans]
+                table = wire.NodeTable(self._names(body, info, idx), blobs)
+                out[b] = (200, wire.tas_filter_result(np.arange(info.n_req, dtype=np.int32),
+                                                      rows[k], table))
+        return out
+
+    def prioritize_batch(self, bodies: Sequence[bytes]) -> List[Tuple[int, bytes]]:
+        """[self.prioritize(b) for b in bodies] through one pas_tas_prioritize_requests call."""
+        out: List[Optional[Tuple[int, bytes]]] = [None] * len(bodies)
+        pend = []
+        for b, body in enumerate(bodies):
+            try:
+                info, idx, _, _, policy_ref = self._decode(body)
+            except ValueError:
+                out[b] = (200, b"")
+                continue
+            if info.n_req == 0:
+                out[b] = (200, b"")
+                continue
+            status = 400 if policy_ref[1] is None else 200
+            policy = self._policy(policy_ref)
+            prio = (policy or {}).get("scheduleonmetric") or []
+            if (policy is None or not prio or not prio[0][0]
+                    or prio[0][0] not in self.metric_index):
+                out[b] = (status, b"[]\n")
+                continue
+            pend.append((b, info, idx, status,
+                         (self.metric_index[prio[0][0]], _op_code(prio[0][1]), int(prio[0][2]))))
+        if pend:
+            req_off = _offsets(len(p[2]) for p in pend)
+            pos, lens = self.ctx.tas_prioritize_requests(
+                self.gen, req_off, make_rules(*zip(*(p[4] for p in pend))),
+                np.concatenate([p[2] for p in pend]))
+            for k, (b, info, idx, status, _) in enumerate(pend):
+                table = wire.NodeTable(self._names(bodies[b], info, idx))
+                out[b] = (status, wire.host_priority_list(
+                    pos[req_off[k]: req_off[k] + lens[k]], table))
+        return out
+
 
 class GASExtender:
     """GAS extender: Filter / Bind / Prioritize (gpuscheduler/scheduler.go:385-573).
@@ -269,6 +350,44 @@ class GASExtender:
                 fit[j >> 6] |= np.uint64(1 << (j & 63))
         return 200, wire.gas_filter_result(np.arange(info.n_req, dtype=np.int32), fit,
                                            wire.NodeTable(names))
+
+    def filter_batch(self, bodies: Sequence[bytes]) -> List[Tuple[int, bytes]]:
+        """[self.filter(b) for b in bodies] through one pas_gas_fit_requests call: each pod is
+        fitted against the nodes its own request names, not against the snapshot."""
+        out: List[Optional[Tuple[int, bytes]]] = [None] * len(bodies)
+        pend = []
+        for b, body in enumerate(bodies):
+            try:
+                info, idx, _, _ = wire.decode_args(self.name_table, body,
+                                                   _lib.PAS_ARGS_NODE_NAMES)
+                req, mask, ncont, _ = self._requests(
+                    body[info.pod_off: info.pod_off + info.pod_len])
+            except _lib.PasError as e:
+                if e.code != _lib.PAS_EDECODE:
+                    raise
+                out[b] = (404, b"")
+                continue
+            if info.n_req == 0:
+                out[b] = (404, wire.gas_filter_result([], np.zeros(1, np.uint64),
+                                                      wire.NodeTable([])))
+                continue
+            pend.append((b, info, idx, req, mask, ncont))
+        if pend:
+            c = max(p[3].shape[1] for p in pend)  # pods with fewer containers: zero rows
+            req = np.zeros((len(pend), c, len(self.kinds)), np.int64)
+            mask = np.zeros((len(pend), c), np.uint32)
+            for k, p in enumerate(pend):
+                req[k, : p[3].shape[1]] = p[3][0]
+                mask[k, : p[4].shape[1]] = p[4][0]
+            rows = self.ctx.gas_fit_requests(
+                self.gen, _offsets(len(p[2]) for p in pend), np.concatenate([p[2] for p in pend]),
+                req, mask, np.concatenate([p[5] for p in pend]), self.i915)
+            for k, (b, info, idx, _, _, _) in enumerate(pend):
+                names = (wire.decode_request_names(bodies[b], _lib.PAS_ARGS_NODE_NAMES)
+                         if info.n_unknown else [self.node_names[i] for i in idx])
+                out[b] = (200, wire.gas_filter_result(np.arange(info.n_req, dtype=np.int32),
+                                                      rows[k], wire.NodeTable(names)))
+        return out
 
     def bind(self, body: bytes) -> Tuple[int, bytes]:
         """Bind + bindNode (:385-445, 546-566): fit on the current usage, commit, annotate."""
