@@ -907,6 +907,51 @@ int pas_tas_gas_topk_wide_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_ge
                                  uint32_t* d_top_sub, int32_t* d_top_node, int32_t* d_top_len,
                                  void* hip_stream);
 
+/* Resuming a top-k list.  d_after_key / [d_after_sub /] d_after_node are [n_pods] contiguous
+ * device arrays holding one cursor per pod in the record form the call writes (64-bit records
+ * for pas_tas_gas_topk_after_device, the canonical (key, sub, node) unit for the wide form;
+ * node ids are global).
+ * Definition: the result for pod p is what the entry point without _after would give on the
+ * same snapshots and arguments with k unbounded, minus every record that is not strictly after
+ * the pod's cursor, cut at k.  "After" is in the ascending (key[, sub], node) order above, the
+ * list order.  Nothing else about the cursor matters: it need not be a record of the list, its
+ * node need not be in this shard (every shard resumes after the same global cursor, and the
+ * merge of the shards' pages is the cluster's page), and the snapshots may have changed since
+ * it was produced.  The device cannot validate the cursor arrays and does not need to: every
+ * bit pattern has a defined result.  On a pod whose prioritize operator is neither LessThan
+ * nor GreaterThan every record has key 0 (sub 0), so a cursor key below that gives the whole
+ * list and one above it the empty list.
+ *   begin   (INT64_MIN, [0,] -1) gives the whole list: equal to the call without _after.
+ *   end     the padding record (INT64_MAX, [UINT32_MAX,] INT32_MAX) gives the empty list
+ *           (top_len 0, padding only).  So top_key[p][k-1], [top_sub[p][k-1],] top_node[p][k-1]
+ *           of one call is the cursor of the next, and a pod whose list was shorter than k is
+ *           finished by construction.
+ * The position after the cursor is found by binary search in the pod's order row (the value's
+ * tie run, then the node within it), so a page costs what its own records cost, whatever came
+ * before it.  The checks are those of the entry points without _after, and null cursor arrays
+ * are PAS_EINVAL; the 64-bit form returns PAS_ENOTEXACT on a snapshot with wide columns. */
+int pas_tas_gas_topk_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                  int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+                                  const int32_t* d_rule_off, const pas_rule* d_prio,
+                                  const uint64_t* d_cand, int32_t max_containers,
+                                  int32_t i915_index, const int64_t* d_req,
+                                  const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                  int32_t k, int32_t node_base, const int64_t* d_after_key,
+                                  const int32_t* d_after_node, int64_t* d_top_key,
+                                  int32_t* d_top_node, int32_t* d_top_len, void* hip_stream);
+int pas_tas_gas_topk_wide_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                       int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+                                       const int32_t* d_rule_off, const pas_rule* d_prio,
+                                       const uint64_t* d_cand, int32_t max_containers,
+                                       int32_t i915_index, const int64_t* d_req,
+                                       const uint32_t* d_req_mask,
+                                       const int32_t* d_n_containers, int32_t k,
+                                       int32_t node_base, const int64_t* d_after_key,
+                                       const uint32_t* d_after_sub, const int32_t* d_after_node,
+                                       int64_t* d_top_key, uint32_t* d_top_sub,
+                                       int32_t* d_top_node, int32_t* d_top_len,
+                                       void* hip_stream);
+
 /* pas_topk_merge_device over wide records: keys / subs / nodes [n_shards][n_pods][k], the k
  * smallest (key, sub, node) records' nodes in order.  PAS_ECAPACITY when n_shards * k > 4096
  * (16 bytes of LDS per record). */

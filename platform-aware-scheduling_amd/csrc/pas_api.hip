@@ -2070,6 +2070,8 @@ static int tas_gas_topk_api(pas_ctx* ctx, const char* fn, bool wide, uint64_t ta
                             const uint32_t* d_req_mask, const int32_t* d_n_containers,
                             int32_t k, int32_t node_base, int64_t* d_top_key,
                             uint32_t* d_top_sub, int32_t* d_top_node, int32_t* d_top_len,
+                            bool after, const int64_t* d_after_key,
+                            const uint32_t* d_after_sub, const int32_t* d_after_node,
                             void* hip_stream) {
   if (!ctx) return PAS_EINVAL;
   int rc = check_tas_gen(ctx, tas_gen);
@@ -2086,13 +2088,16 @@ static int tas_gas_topk_api(pas_ctx* ctx, const char* fn, bool wide, uint64_t ta
   if (n_pods == 0) return PAS_OK;
   if (!d_rule_off || !d_prio || (n_rules > 0 && !d_rules) || !d_top_key || !d_top_node ||
       !d_top_len || !d_n_containers || (max_containers > 0 && (!d_req || !d_req_mask)) ||
-      (wide && !d_top_sub))
+      (wide && !d_top_sub) ||
+      (after && (!d_after_key || !d_after_node || (wide && !d_after_sub))))
     return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
   if ((rc = activate(ctx))) return rc;
   return tas_gas_topk_launch(ctx, n_pods, n_rules, d_rules, d_rule_off, d_prio, d_cand,
                              max_containers, i915_index, d_req, d_req_mask, d_n_containers, k,
                              node_base, d_top_key, wide ? d_top_sub : nullptr, d_top_node,
-                             d_top_len, pick_stream(ctx, hip_stream));
+                             d_top_len, after ? d_after_key : nullptr,
+                             wide ? d_after_sub : nullptr, d_after_node,
+                             pick_stream(ctx, hip_stream));
 }
 
 int pas_tas_gas_topk_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, int32_t n_pods,
@@ -2105,7 +2110,8 @@ int pas_tas_gas_topk_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, in
   return tas_gas_topk_api(ctx, "pas_tas_gas_topk_device", false, tas_gen, gas_gen, n_pods,
                           n_rules, d_rules, d_rule_off, d_prio, d_cand, max_containers,
                           i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
-                          d_top_key, nullptr, d_top_node, d_top_len, hip_stream);
+                          d_top_key, nullptr, d_top_node, d_top_len, false, nullptr, nullptr,
+                          nullptr, hip_stream);
 }
 
 int pas_tas_gas_topk_wide_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
@@ -2120,7 +2126,43 @@ int pas_tas_gas_topk_wide_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_ge
   return tas_gas_topk_api(ctx, "pas_tas_gas_topk_wide_device", true, tas_gen, gas_gen, n_pods,
                           n_rules, d_rules, d_rule_off, d_prio, d_cand, max_containers,
                           i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
-                          d_top_key, d_top_sub, d_top_node, d_top_len, hip_stream);
+                          d_top_key, d_top_sub, d_top_node, d_top_len, false, nullptr, nullptr,
+                          nullptr, hip_stream);
+}
+
+int pas_tas_gas_topk_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                  int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+                                  const int32_t* d_rule_off, const pas_rule* d_prio,
+                                  const uint64_t* d_cand, int32_t max_containers,
+                                  int32_t i915_index, const int64_t* d_req,
+                                  const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                  int32_t k, int32_t node_base, const int64_t* d_after_key,
+                                  const int32_t* d_after_node, int64_t* d_top_key,
+                                  int32_t* d_top_node, int32_t* d_top_len, void* hip_stream) {
+  return tas_gas_topk_api(ctx, "pas_tas_gas_topk_after_device", false, tas_gen, gas_gen, n_pods,
+                          n_rules, d_rules, d_rule_off, d_prio, d_cand, max_containers,
+                          i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
+                          d_top_key, nullptr, d_top_node, d_top_len, true, d_after_key, nullptr,
+                          d_after_node, hip_stream);
+}
+
+int pas_tas_gas_topk_wide_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                       int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+                                       const int32_t* d_rule_off, const pas_rule* d_prio,
+                                       const uint64_t* d_cand, int32_t max_containers,
+                                       int32_t i915_index, const int64_t* d_req,
+                                       const uint32_t* d_req_mask,
+                                       const int32_t* d_n_containers, int32_t k,
+                                       int32_t node_base, const int64_t* d_after_key,
+                                       const uint32_t* d_after_sub, const int32_t* d_after_node,
+                                       int64_t* d_top_key, uint32_t* d_top_sub,
+                                       int32_t* d_top_node, int32_t* d_top_len,
+                                       void* hip_stream) {
+  return tas_gas_topk_api(ctx, "pas_tas_gas_topk_wide_after_device", true, tas_gen, gas_gen,
+                          n_pods, n_rules, d_rules, d_rule_off, d_prio, d_cand, max_containers,
+                          i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
+                          d_top_key, d_top_sub, d_top_node, d_top_len, true, d_after_key,
+                          d_after_sub, d_after_node, hip_stream);
 }
 
 static int topk_merge_api(pas_ctx* ctx, const char* fn, bool wide, int32_t n_pods, int32_t k,

@@ -403,13 +403,16 @@ int tas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
 int tas_group_launch(pas_ctx* ctx, int32_t n_pods, const pas_rule* d_prio,
                      const int32_t* d_rule_off, int4* d_desc, int2* d_keys, int32_t n_rules,
                      const pas_rule* d_rules, int2* d_ranges, hipStream_t s);
+// d_after_key / d_after_sub (wide records) / d_after_node: the pods' cursors, the lists resume
+// strictly after them (pas.h); null d_after_key = the lists from their beginning.
 int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
                         const int32_t* d_rule_off, const pas_rule* d_prio,
                         const uint64_t* d_cand, int32_t max_containers, int32_t i915_index,
                         const int64_t* d_req, const uint32_t* d_req_mask,
                         const int32_t* d_n_containers, int32_t k, int32_t node_base,
                         int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
-                        hipStream_t s);
+                        const int64_t* d_after_key, const uint32_t* d_after_sub,
+                        const int32_t* d_after_node, hipStream_t s);
 int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
                       const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
                       int32_t* d_out_node, int64_t out_ld, int32_t* d_out_len, hipStream_t s);

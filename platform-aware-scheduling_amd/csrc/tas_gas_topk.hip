@@ -28,12 +28,19 @@
 // node = global id (local + node_base); past len: key INT64_MAX, node INT32_MAX.  The kWide
 // instantiations (pas_tas_gas_topk_wide_device) write the wide records (key, sub, node) of
 // pas.h instead and evaluate rules and jumps on wide columns exactly.
+//
+// Resuming (pas_tas_gas_topk[_wide]_after_device): the pod's list continues strictly after a
+// cursor record.  Ascending (key[, sub], node) is the order of the row, so the records not
+// after the cursor are a prefix of the row whose length topk_start_kernel finds by binary
+// search (the value's tie run, then the node id within the run); the kAfter instantiations of
+// the walk begin at that position instead of 0 and are otherwise the same kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "gas_runs.h"
 #include "pas_internal.h"
+#include "tas_rank.h"
 
 namespace pas {
 namespace {
@@ -337,7 +344,9 @@ template <int KMAX, int QW, bool kWide>
 constexpr int topk_waves() { return KMAX <= 8 && QW <= 3 ? (kWide ? 3 : 4) : 1; }
 // kWide: the wide records (key, sub, node) in the canonical unit (pas.h), rules and jumps on
 // wide columns; the narrow instantiations (kWide = false) hold none of that code.
-template <int KMAX, int QW, bool kWide>
+// kAfter: the walk begins at the pod's start position, which topk_start_kernel left in
+// len_out[p] (the walk writes the list's length there at its end); nothing else differs.
+template <int KMAX, int QW, bool kWide, bool kAfter>
 __global__ __launch_bounds__(kTpb)
 __attribute__((amdgpu_waves_per_eu(topk_waves<KMAX, QW, kWide>())))
 void tas_gas_topk_kernel(LazyTopkParams a) {
@@ -478,7 +487,9 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
   int64_t* keys = a.key_out + (int64_t)p * k;
   int32_t* nodes = a.node_out + (int64_t)p * k;
   int32_t kept = 0;
-  for (int32_t j0 = 0;; j0 += kPodLanes) {
+  int32_t j0 = 0;
+  if constexpr (kAfter) j0 = have ? min(max(a.len_out[p], 0), c0) : 0;
+  for (;; j0 += kPodLanes) {
 #pragma unroll
     for (int it = 0; it < kSkip; ++it)
 #pragma unroll
@@ -636,19 +647,115 @@ __global__ __launch_bounds__(kTpb) void transpose_present_kernel(
   }
 }
 
+// The resumed walk's start positions (pas.h, "Resuming a top-k list").
+struct TopkStartParams {
+  int32_t n_pods, N, M, R, node_base;
+  const pas_rule* prio;
+  const int32_t* perm;          // [3][M][R]
+  const int32_t* cnt;           // [M]
+  const int64_t* sorted;        // [M][R]
+  const uint32_t* sorted_nano;  // [M][R] (wide columns)
+  const int64_t* scale_tab;
+  const uint8_t* wide_flag;     // null while the snapshot holds no wide column
+  const int64_t* after_key;     // [P] the cursors
+  const uint32_t* after_sub;    // [P] (kWide)
+  const int32_t* after_node;    // [P] global ids
+  int32_t* start;               // [P]
+};
+
+// First position of [lo, hi) at which before(position) does not hold (hi if none); before
+// must hold on a prefix of the range.
+template <typename F>
+__device__ __forceinline__ int32_t first_not(int32_t lo, int32_t hi, F before) {
+  while (lo < hi) {
+    const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
+    if (before(mid)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// start[p] = the number of entries of pod p's order row whose record is <= the pod's cursor
+// in ascending (key[, sub], node), a lane per pod.  Sorted rows: the cursor's key decodes to a
+// value (v = key for LessThan, ~key for GreaterThan; kWide: the pair (W, F) from key and sub
+// the same way); [lb, ub) is that value's tie run in the ascending column, mirrored to
+// [c0 - ub, c0 - lb) in the descending row; everything before the run is before the cursor,
+// and within the run (ascending node index in both rows) the nodes up to the cursor's.  Index
+// rows: every record has key 0 (sub 0), so a cursor key below that starts at 0, one above it
+// at c0, and key 0 at the number of nodes up to the cursor's.  kWide on a narrow column
+// compares each probed stored value's canonical pair with (W, F): the cursor is never
+// converted into the column's unit, which the sentinels would overflow.  Every bit pattern of
+// a cursor has a start in [0, c0]; c0 = 0 (no rule, metric not cached) stays the empty list.
 template <bool kWide>
+__global__ __launch_bounds__(kTpb) void topk_start_kernel(TopkStartParams a) {
+  const int32_t p = blockIdx.x * kTpb + threadIdx.x;
+  if (p >= a.n_pods) return;
+  const pas_rule q = a.prio[p];
+  const int32_t m = q.metric;
+  const int32_t c0 = (m >= 0 && m < a.M) ? a.cnt[m] : 0;
+  int32_t start = 0;
+  if (c0 > 0) {
+    const int64_t ck = a.after_key[p];
+    uint32_t cs = 0;
+    if constexpr (kWide) cs = a.after_sub[p];
+    // the cursor's node as a local id, clamped to [-1, N]: a node below the shard counts none
+    // of a run, one at or past the shard's end all of it
+    const int64_t loc = (int64_t)a.after_node[p] - (int64_t)a.node_base;
+    const int32_t cn = (int32_t)(loc < -1 ? -1 : loc > a.N ? a.N : loc);
+    const int ord = q.op == PAS_OP_GREATER_THAN ? kOrderDesc
+                    : q.op == PAS_OP_LESS_THAN  ? kOrderAsc
+                                                : kOrderIndex;
+    const int32_t* row = a.perm + ((int64_t)ord * a.M + m) * a.R;
+    auto node_not_above = [&](int32_t j) { return row[j] <= cn; };
+    if (ord == kOrderIndex) {
+      const bool above = ck > 0 || (kWide && ck == 0 && cs > 0u);
+      start = ck < 0 ? 0 : above ? c0 : first_not(0, c0, node_not_above);
+    } else {
+      const bool desc = ord == kOrderDesc;
+      const int64_t v = desc ? ~ck : ck;
+      const int64_t* sv = a.sorted + (int64_t)m * a.R;
+      int32_t lb, ub;
+      if constexpr (kWide) {
+        const uint32_t f = desc ? ~cs : cs;
+        if (a.wide_flag && a.wide_flag[m]) {
+          const uint32_t* sn = a.sorted_nano + (int64_t)m * a.R;
+          lb = bound<true>(sv, sn, c0, v, f, false);
+          ub = lb + bound<true>(sv + lb, sn + lb, c0 - lb, v, f, true);
+        } else {
+          const int64_t mult = a.scale_tab[2 * m];
+          auto before = [&](int32_t j, bool upper) {
+            int64_t W;
+            uint32_t F;
+            canonical_pair(sv[j], mult, &W, &F);
+            return upper ? pair_not_above(W, F, v, f) : pair_below(W, F, v, f);
+          };
+          lb = first_not(0, c0, [&](int32_t j) { return before(j, false); });
+          ub = first_not(lb, c0, [&](int32_t j) { return before(j, true); });
+        }
+      } else {
+        lb = bound<false>(sv, nullptr, c0, v, 0u, false);
+        ub = lb + bound<false>(sv + lb, nullptr, c0 - lb, v, 0u, true);
+      }
+      const int32_t t0 = desc ? c0 - ub : lb, t1 = desc ? c0 - lb : ub;
+      start = first_not(t0, t1, node_not_above);
+    }
+  }
+  a.start[p] = start;
+}
+
+template <bool kWide, bool kAfter>
 void topk_dispatch(const LazyTopkParams& a, unsigned grid, hipStream_t s) {
   if (a.K <= 8) {
     switch (a.Q) {
-      case 1: tas_gas_topk_kernel<8, 1, kWide><<<grid, kTpb, 0, s>>>(a); break;
-      case 2: tas_gas_topk_kernel<8, 2, kWide><<<grid, kTpb, 0, s>>>(a); break;
-      case 3: tas_gas_topk_kernel<8, 3, kWide><<<grid, kTpb, 0, s>>>(a); break;
-      default: tas_gas_topk_kernel<8, kMaxRes, kWide><<<grid, kTpb, 0, s>>>(a); break;
+      case 1: tas_gas_topk_kernel<8, 1, kWide, kAfter><<<grid, kTpb, 0, s>>>(a); break;
+      case 2: tas_gas_topk_kernel<8, 2, kWide, kAfter><<<grid, kTpb, 0, s>>>(a); break;
+      case 3: tas_gas_topk_kernel<8, 3, kWide, kAfter><<<grid, kTpb, 0, s>>>(a); break;
+      default: tas_gas_topk_kernel<8, kMaxRes, kWide, kAfter><<<grid, kTpb, 0, s>>>(a); break;
     }
   } else if (a.K <= 16) {
-    tas_gas_topk_kernel<16, kMaxRes, kWide><<<grid, kTpb, 0, s>>>(a);
+    tas_gas_topk_kernel<16, kMaxRes, kWide, kAfter><<<grid, kTpb, 0, s>>>(a);
   } else {
-    tas_gas_topk_kernel<PAS_GAS_MAX_CARDS, kMaxRes, kWide><<<grid, kTpb, 0, s>>>(a);
+    tas_gas_topk_kernel<PAS_GAS_MAX_CARDS, kMaxRes, kWide, kAfter><<<grid, kTpb, 0, s>>>(a);
   }
 }
 
@@ -660,7 +767,8 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
                         const int64_t* d_req, const uint32_t* d_req_mask,
                         const int32_t* d_n_containers, int32_t k, int32_t node_base,
                         int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
-                        hipStream_t s) {
+                        const int64_t* d_after_key, const uint32_t* d_after_sub,
+                        const int32_t* d_after_node, hipStream_t s) {
   if (n_pods == 0) return PAS_OK;
   TasSnapshot& t = ctx->tas;
   const GasSnapshot& g = ctx->gas;
@@ -737,8 +845,38 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
   a.f1k_nano = t.f1k_nano;
   a.f32_nano = t.f32_nano;
   const unsigned grid = (unsigned)((n_pods + kPodsPerBlock - 1) / kPodsPerBlock);
-  if (d_sub) topk_dispatch<true>(a, grid, s);
-  else topk_dispatch<false>(a, grid, s);
+  if (d_after_key) {
+    // the start positions into d_len, where the walk reads them
+    TopkStartParams b;
+    b.n_pods = n_pods;
+    b.N = N;
+    b.M = M;
+    b.R = t.row;
+    b.node_base = node_base;
+    b.prio = d_prio;
+    b.perm = t.perm;
+    b.cnt = t.cnt;
+    b.sorted = t.sorted;
+    b.sorted_nano = t.sorted_nano;
+    b.scale_tab = t.scale_tab;
+    b.wide_flag = a.wide_flag;
+    b.after_key = d_after_key;
+    b.after_sub = d_after_sub;
+    b.after_node = d_after_node;
+    b.start = d_len;
+    const unsigned sgrid = (unsigned)((n_pods + kTpb - 1) / kTpb);
+    if (d_sub) {
+      topk_start_kernel<true><<<sgrid, kTpb, 0, s>>>(b);
+      topk_dispatch<true, true>(a, grid, s);
+    } else {
+      topk_start_kernel<false><<<sgrid, kTpb, 0, s>>>(b);
+      topk_dispatch<false, true>(a, grid, s);
+    }
+  } else if (d_sub) {
+    topk_dispatch<true, false>(a, grid, s);
+  } else {
+    topk_dispatch<false, false>(a, grid, s);
+  }
   timing_end(ctx, s, &tl);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;

@@ -1,5 +1,6 @@
 // tas_rank.h — a value's rank in a column's sorted row: what the request-order prioritize
-// paths (tas_request.hip: one request; tas_request_batch.hip: a batch) build their keys from.
+// paths (tas_request.hip: one request; tas_request_batch.hip: a batch) build their keys from,
+// and where a resumed top-k list finds its cursor's tie run (tas_gas_topk.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

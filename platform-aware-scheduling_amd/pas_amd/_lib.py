@@ -265,6 +265,16 @@ SIGNATURES = {
         [_P, c_uint64, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P,
          c_int32, c_int32, _P, _P, _P, _P, _P],
     ),
+    "pas_tas_gas_topk_after_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int32, c_int32, _P, _P, _P, _P, _P, _P],
+    ),
+    "pas_tas_gas_topk_wide_after_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P],
+    ),
     "pas_topk_merge_wide_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
                                            _P]),
     "pas_list_merge_wide_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P,

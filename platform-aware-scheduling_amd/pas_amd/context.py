@@ -904,6 +904,38 @@ class Context:
             _dptr(node_t), _dptr(len_t), _stream(stream))
         self._check(rc, "pas_tas_gas_topk_wide_device")
 
+    # ------------------------------------------------------------------ resumed lists
+    def tas_gas_topk_after_device(self, tas_gen: int, gas_gen: int, n_pods: int, n_rules: int,
+                                  rules_t, rule_off_t, prio_t, cand_t, max_containers: int,
+                                  i915_index: int, req_t, mask_t, ncont_t, k: int,
+                                  node_base: int, after_key_t, after_node_t, key_t, node_t,
+                                  len_t, stream=None):
+        """tas_gas_topk_device resumed strictly after each pod's cursor record
+        (pas_tas_gas_topk_after_device): after_key_t int64 [P], after_node_t int32 [P], global
+        node ids; (INT64_MIN, -1) is the whole list, the padding record the empty list."""
+        rc = self._l.pas_tas_gas_topk_after_device(
+            self._h, tas_gen, gas_gen, n_pods, n_rules, _dptr(rules_t), _dptr(rule_off_t),
+            _dptr(prio_t), _dptr(cand_t), max_containers, i915_index, _dptr(req_t),
+            _dptr(mask_t), _dptr(ncont_t), k, node_base, _dptr(after_key_t),
+            _dptr(after_node_t), _dptr(key_t), _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_gas_topk_after_device")
+
+    def tas_gas_topk_wide_after_device(self, tas_gen: int, gas_gen: int, n_pods: int,
+                                       n_rules: int, rules_t, rule_off_t, prio_t, cand_t,
+                                       max_containers: int, i915_index: int, req_t, mask_t,
+                                       ncont_t, k: int, node_base: int, after_key_t, after_sub_t,
+                                       after_node_t, key_t, sub_t, node_t, len_t, stream=None):
+        """tas_gas_topk_wide_device resumed strictly after each pod's cursor record
+        (pas_tas_gas_topk_wide_after_device): after_sub_t uint32-sized [P] (torch.int32
+        storage) beside the two arrays of tas_gas_topk_after_device."""
+        rc = self._l.pas_tas_gas_topk_wide_after_device(
+            self._h, tas_gen, gas_gen, n_pods, n_rules, _dptr(rules_t), _dptr(rule_off_t),
+            _dptr(prio_t), _dptr(cand_t), max_containers, i915_index, _dptr(req_t),
+            _dptr(mask_t), _dptr(ncont_t), k, node_base, _dptr(after_key_t), _dptr(after_sub_t),
+            _dptr(after_node_t), _dptr(key_t), _dptr(sub_t), _dptr(node_t), _dptr(len_t),
+            _stream(stream))
+        self._check(rc, "pas_tas_gas_topk_wide_after_device")
+
     def topk_merge_wide_device(self, n_pods: int, k: int, n_shards: int, keys_t, subs_t, nodes_t,
                                out_node_t, out_len_t, stream=None):
         """Merge of [n_shards][P][k] wide records into the global first-k lists

@@ -1,0 +1,108 @@
+"""Batch placement to completion: top-k rows and placement, round after round, until every
+pod is placed or has tried every node of its list.
+
+One pas_tas_gas_topk_device -> pas_gas_place_device pass leaves a pod unplaced as soon as its
+k candidates were taken by the pods before it.  Here such a pod continues: its next row
+resumes the list strictly after the last record it tried (pas_tas_gas_topk[_wide]_after_device,
+include/pas.h "Resuming a top-k list") on the usage the round before left behind.
+
+Equivalence.  During the call the usage only grows, so a node that did not fit a pod at a
+round's start never fits it later in the call: a row holds the next k nodes of the pod's list
+that can still take it.  Each round is therefore the sequential pod-after-pod loop of
+pas_gas_place over the queued pods, each walking its full list from its cursor for at most k
+still-feasible nodes, and a pod that used up its k goes to the back of the queue, as a pod that
+failed to bind does in kube-scheduler (the extender is called again and answers from its
+current cache).  A pod ends unplaced only when a row came back shorter than k, i.e. when every
+node of its list had been tried or no longer fits.  The caller must not interleave releases or
+node / pod events with the call: they would let a node the cursor has passed fit again.
+
+Torch allocates the buffers and does the elementwise plumbing between the two device calls;
+there is no per-pod work on the host."""
+from collections import namedtuple
+
+import torch
+
+INT32_MAX = 2**31 - 1
+INT64_MIN, INT64_MAX = -2**63, 2**63 - 1
+
+PlacementResult = namedtuple("PlacementResult", "node round res n_placed rounds gas_gen")
+PlacementResult.__doc__ = """place_to_completion's result: node int32 [P] (global id, -1 =
+unplaced), round int32 [P] (0-based round the pod was placed in, -1 = unplaced), res int32 [P]
+(pas_gas_place_device's result word, 0 for an unplaced pod), all on the device; n_placed,
+rounds (top-k + place passes run) and gas_gen (the GAS generation after the last pass)."""
+
+
+def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: int, rules_t,
+                        rule_off_t, prio_t, cand_t, max_containers: int, i915_index: int, req_t,
+                        mask_t, ncont_t, k: int, node_base: int = 0, wide: bool = False,
+                        max_rounds=None, stream=None) -> PlacementResult:
+    """Place a batch until every pod is placed or has provably run out of nodes (the module's
+    docstring has the equivalence).  The pod batch tensors are those of
+    Context.tas_gas_topk[_wide]_device and Context.gas_place_device; wide selects the wide
+    records (required on a snapshot with wide columns).  Every pass moves the GAS snapshot one
+    generation on, from gas_gen; the result names the last one.
+
+    max_rounds defaults to ceil(N / k) + 1, which the loop cannot exceed: every unfinished
+    cursor advances by k records per round.  Passing it raises RuntimeError (the passes run so
+    far stay committed, the snapshot is at gas_gen + max_rounds).  Errors of the two device
+    calls propagate as PasError: a stale generation before anything changed, PAS_EDEVICE from
+    the place call as pas_gas_place_device reports it."""
+    stream = torch.cuda.current_stream() if stream is None else stream
+    if max_rounds is None:
+        max_rounds = -(-ctx.gas_shape[0] // k) + 1
+    with torch.cuda.stream(stream):
+        dev = req_t.device if req_t is not None else "cuda"
+
+        def full(shape, value, dtype):
+            return torch.full(shape, value, dtype=dtype, device=dev)
+        p = n_pods
+        # the cursors: begin for every pod
+        after_key, after_node = full((p,), INT64_MIN, torch.int64), full((p,), -1, torch.int32)
+        after_sub = full((p,), 0, torch.int32) if wide else None
+        node, rnd = full((p,), -1, torch.int32), full((p,), -1, torch.int32)
+        res = full((p,), 0, torch.int32)
+        key = torch.empty((p, k), dtype=torch.int64, device=dev)
+        sub = torch.empty((p, k), dtype=torch.int32, device=dev) if wide else None
+        top_node = torch.empty((p, k), dtype=torch.int32, device=dev)
+        top_len = torch.empty(p, dtype=torch.int32, device=dev)
+        r_node = torch.empty(p, dtype=torch.int32, device=dev)
+        r_rank = torch.empty(p, dtype=torch.int32, device=dev)
+        r_res = torch.empty(p, dtype=torch.int32, device=dev)
+        gen, rounds, n_placed = gas_gen, 0, 0
+        while True:
+            if rounds >= max_rounds:
+                raise RuntimeError(f"place_to_completion: pods still queued after {rounds} "
+                                   f"rounds (max_rounds)")
+            head = (tas_gen, gen, p, n_rules, rules_t, rule_off_t, prio_t, cand_t,
+                    max_containers, i915_index, req_t, mask_t, ncont_t, k, node_base)
+            if wide:
+                ctx.tas_gas_topk_wide_after_device(*head, after_key, after_sub, after_node, key,
+                                                   sub, top_node, top_len, stream=stream)
+            else:
+                ctx.tas_gas_topk_after_device(*head, after_key, after_node, key, top_node,
+                                              top_len, stream=stream)
+            placed_now, _ = ctx.gas_place_device(gen, gen + 1, p, max_containers, i915_index,
+                                                 req_t, mask_t, ncont_t, k, k, node_base,
+                                                 top_node, top_len, r_node, r_rank, r_res,
+                                                 stream=stream)
+            gen += 1
+            n_placed += placed_now
+            if p == 0:
+                rounds += 1
+                break
+            placed = r_node >= 0
+            node = torch.where(placed, r_node, node)
+            res = torch.where(placed, r_res, res)
+            rnd = torch.where(placed, torch.full_like(rnd, rounds), rnd)
+            rounds += 1
+            # the next cursors: the end for a placed pod, the row's last record otherwise (the
+            # padding record, i.e. the end, when the row was shorter than k)
+            after_key = torch.where(placed, torch.full_like(after_key, INT64_MAX), key[:, k - 1])
+            after_node = torch.where(placed, torch.full_like(after_node, INT32_MAX),
+                                     top_node[:, k - 1])
+            if wide:
+                after_sub = torch.where(placed, torch.full_like(after_sub, -1), sub[:, k - 1])
+            # queued: unplaced with a full row (finished pods come back with an empty row)
+            if not bool((~placed & (top_len == k)).any()):
+                break
+        return PlacementResult(node, rnd, res, n_placed, rounds, gen)
