@@ -232,6 +232,9 @@ constexpr int kAuxSlots = 4;
 
 // Sub-buffers of one scratch allocation, each rounded up to 256 bytes: carve_size() of the
 // sub-buffers' byte sizes is what take() of their element counts, in the same order, uses.
+// For the _launch functions' AuxSlot and slot_buf storage (gas_fit.hip, gas_place.hip,
+// gas_group.h, the *_requests launches); the host forms' arrays in ctx->scratch are stated
+// once each to a Staging (host_staging.h), which sizes and lays them out itself.
 struct Carve {
   char* base;
   size_t off = 0;
