@@ -175,7 +175,8 @@ int pas_tas_snapshot_set_scale(pas_ctx* ctx, uint64_t gen, int32_t n_metrics,
  * columns cols[0 .. n_cols) (distinct metric indices, host array) with
  * v_milli[n_cols][n_nodes] / present[n_cols][W64] and rebuilds only their orders; the
  * snapshot moves from generation gen_from (PAS_ESTALE otherwise) to gen_to.  Node count and
- * metric count are unchanged (a new node or metric column needs pas_tas_snapshot_set).
+ * metric count are unchanged (pas_tas_snapshot_reshape adds node slots and adds, drops or
+ * moves metric columns on the device).
  * The _device form is asynchronous on hip_stream except for the copy of cols. */
 int pas_tas_snapshot_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_cols,
                             const int32_t* cols, const int64_t* v_milli,
@@ -212,6 +213,45 @@ int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_
                                         int32_t n_cols, const int32_t* cols,
                                         const int64_t* d_whole, const uint32_t* d_nano,
                                         const uint64_t* d_present, void* hip_stream);
+/* Change the shape of the resident snapshot on the device: node slots are appended and metric
+ * columns added, dropped or moved, without a host copy and without a sort (the orders of a
+ * kept column do not change; its rows are gathered into the new pitch and their pads
+ * rewritten).  The reference's cache does this all the time: WriteMetric(name, nil) for the
+ * rules of a new policy (controller.go:83-87,142-146), DeleteMetric with the last user
+ * (autoupdating.go:127-137), and a refresh whose node map lists a node first seen (:62-72).
+ *   n_nodes_new    >= the resident n_nodes (PAS_EINVAL otherwise: nodes only grow, as in
+ *                  pas_gas_snapshot_resize); slots [n_nodes, n_nodes_new) carry no present
+ *                  bit in any column
+ *   n_metrics_new  >= 0
+ *   src_col        host [n_metrics_new]: new column m is old column src_col[m] with its
+ *                  values, presence, recorded scale and narrow / wide kind, or, for -1, an
+ *                  empty column (no node present, scale milli, narrow).  Any other value and
+ *                  an old column named twice are PAS_EINVAL.  NULL: old column m for m <
+ *                  n_metrics, -1 from there on (PAS_EINVAL when n_metrics_new < n_metrics).
+ * gen_from is checked (PAS_ESTALE, PAS_ENOSNAP without a snapshot; nothing changed) and the
+ * snapshot moves to gen_to.  The limits are pas_tas_snapshot_set's (PAS_ECAPACITY: 3 *
+ * n_metrics_new * padded n_nodes_new < 2^31; checked before anything is allocated).  The same
+ * shape with every column in place moves the generation only.  Synchronous on hip_stream (NULL:
+ * the context's stream): new storage is allocated and filled by one gather kernel, hip_stream
+ * and the context's stream are synchronized, then the old storage is freed; the caller orders
+ * the call after readers on other streams, as for every snapshot change.  When the new
+ * storage cannot be allocated the old snapshot stays valid and untouched (PAS_ENOMEM); a HIP
+ * failure after that leaves the context without a TAS snapshot (PAS_ENOSNAP until the next
+ * pas_tas_snapshot_set).  Afterwards every evaluation answers what it would on a snapshot
+ * built from the same content by pas_tas_snapshot_set + pas_tas_snapshot_set_scale +
+ * pas_tas_snapshot_update_wide.  The wide parts' storage is carried over when a kept column is
+ * wide and otherwise allocated again by the next wide update. */
+int pas_tas_snapshot_reshape(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                             int32_t n_nodes_new, int32_t n_metrics_new,
+                             const int32_t* src_col /* host [n_metrics_new], or NULL */,
+                             void* hip_stream);
+/* Read back the resident snapshot and its generation; any output may be NULL.  present_out
+ * has the bits at and past n_nodes cleared; values and nanos are meaningful only where the
+ * bit is set.  scale_out is each column's recorded decimal scale, wide_out 1 for a wide
+ * column; nano_out is zero for every narrow column. */
+int pas_tas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* vals_out /*[M][N]*/,
+                         uint64_t* present_out /*[M][W64]*/, int32_t* scale_out /*[M]*/,
+                         uint8_t* wide_out /*[M]*/, uint32_t* nano_out /*[M][N]*/);
 /* Forget the resident TAS snapshot (its storage is kept): every call that checks a
  * generation answers PAS_ENOSNAP until the next pas_tas_snapshot_set[_device].  For a
  * binding that installs a snapshot in two steps (set, then the wide columns) and must not
@@ -800,8 +840,8 @@ int pas_gas_nodes_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to
  * to gen_to.  Synchronous on hip_stream: the old storage is freed after the copy kernel has
  * finished.  When the new storage cannot be allocated the old snapshot stays valid and
  * untouched (PAS_ENOMEM).  pas_tas_gas_topk*_device still needs both snapshots to hold the
- * same number of nodes: a caller that grows the GAS snapshot sets its next TAS snapshot with
- * the same number of slots (spare slots: no present bit). */
+ * same number of nodes: a caller that grows the GAS snapshot grows its TAS snapshot to the
+ * same number of slots with pas_tas_snapshot_reshape (spare slots: no present bit). */
 int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
                             int32_t n_nodes_new, int32_t max_cards_new, void* hip_stream);
 

@@ -179,8 +179,7 @@ static void free_ptr(void*& p) {
   p = nullptr;
 }
 
-void free_tas(pas_ctx* ctx) {
-  TasSnapshot& t = ctx->tas;
+void tas_free_storage(TasSnapshot& t) {
   free_ptr(reinterpret_cast<void*&>(t.vals));
   free_ptr(reinterpret_cast<void*&>(t.present));
   free_ptr(reinterpret_cast<void*&>(t.vals_t));
@@ -208,6 +207,11 @@ void free_tas(pas_ctx* ctx) {
   free_ptr(reinterpret_cast<void*&>(t.rows));
   free_ptr(t.sort_tmp);
   free_ptr(t.scan_tmp);
+}
+
+void free_tas(pas_ctx* ctx) {
+  TasSnapshot& t = ctx->tas;
+  tas_free_storage(t);
   const hipEvent_t ev = t.t_sync.ev;  // kept for the context's life (pas_destroy)
   t = TasSnapshot{};
   t.t_sync.ev = ev;
@@ -527,6 +531,81 @@ int pas_tas_snapshot_set_scale(pas_ctx* ctx, uint64_t gen, int32_t n_metrics,
   PAS_HIP(ctx, hipMemcpyAsync(ctx->tas.scale_tab, tab.data(), sizeof(int64_t) * tab.size(),
                               hipMemcpyHostToDevice, s));
   PAS_HIP(ctx, hipStreamSynchronize(s));  // tab is this call's
+  return PAS_OK;
+}
+
+int pas_tas_snapshot_reshape(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                             int32_t n_nodes_new, int32_t n_metrics_new, const int32_t* src_col,
+                             void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_reshape";
+  int rc = check_tas_gen(ctx, gen_from);
+  if (rc) return rc;
+  TasSnapshot& t = ctx->tas;
+  const int32_t M = t.n_metrics;
+  if (n_nodes_new < t.n_nodes)
+    return set_error(ctx, PAS_EINVAL, fn + ": the node count only grows");
+  if (n_metrics_new < 0 || (!src_col && n_metrics_new < M))
+    return set_error(ctx, PAS_EINVAL, fn + ": fewer metric columns need a src_col");
+  // pas_tas_snapshot_set's limit, before anything of that size is allocated, here or there
+  if ((int64_t)n_metrics_new * order_row(n_nodes_new) * kNumOrders > 0x7fffffffLL)
+    return set_error(ctx, PAS_ECAPACITY,
+                     "TAS snapshot: 3 * n_metrics * padded n_nodes must be < 2^31");
+  // the column map, checked: an old column at most once, or -1
+  std::vector<int32_t> src((size_t)n_metrics_new);
+  std::vector<char> seen((size_t)M, 0);
+  bool identity = n_metrics_new == M;
+  for (int32_t m = 0; m < n_metrics_new; ++m) {
+    const int32_t c = src_col ? src_col[m] : m < M ? m : -1;
+    if (c < -1 || c >= M || (c >= 0 && seen[(size_t)c]++))
+      return set_error(ctx, PAS_EINVAL,
+                       fn + ": src_col entries must be distinct columns < n_metrics, or -1");
+    src[(size_t)m] = c;
+    identity &= c == m;
+  }
+  if (identity && n_nodes_new == t.n_nodes) {  // the same shape and columns
+    t.gen = gen_to;
+    return PAS_OK;
+  }
+  if ((rc = activate(ctx))) return rc;
+  return tas_snapshot_reshape(ctx, gen_to, n_nodes_new, n_metrics_new, src.data(),
+                              pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* vals_out, uint64_t* present_out,
+                         int32_t* scale_out, uint8_t* wide_out, uint32_t* nano_out) {
+  if (!ctx) return PAS_EINVAL;
+  if (!ctx->tas.valid) return set_error(ctx, PAS_ENOSNAP, "no TAS snapshot uploaded");
+  const TasSnapshot& t = ctx->tas;
+  const size_t M = (size_t)t.n_metrics, N = (size_t)t.n_nodes, W = (size_t)w64(t.n_nodes);
+  int rc = activate(ctx);
+  if (rc) return rc;
+  // (out of the resident arrays, not scratch: no Staging)
+  hipStream_t s = ctx->stream;
+  const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
+  if (vals_out && M * N)
+    PAS_HIP(ctx, hipMemcpyAsync(vals_out, t.vals, sizeof(int64_t) * M * N, d2h, s));
+  if (present_out && M * W)
+    PAS_HIP(ctx, hipMemcpyAsync(present_out, t.present, sizeof(uint64_t) * M * W, d2h, s));
+  if (nano_out && M * N && t.nano)
+    PAS_HIP(ctx, hipMemcpyAsync(nano_out, t.nano, sizeof(uint32_t) * M * N, d2h, s));
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  for (size_t m = 0; m < M; ++m) {
+    // the resident last word keeps what its upload carried past n_nodes
+    if (present_out && W) {
+      uint64_t& last = present_out[m * W + W - 1];
+      last = word_mask(last, (int64_t)W - 1, t.n_nodes);
+    }
+    const bool wide = t.n_wide > 0 && t.wide_host[m];
+    if (nano_out && !wide) std::memset(nano_out + m * N, 0, sizeof(uint32_t) * N);  // unset rows
+    if (wide_out) wide_out[m] = wide ? 1 : 0;
+    if (scale_out) {
+      int32_t sc = 0;
+      for (int64_t mult = t.scale_host[2 * m]; mult > 1; mult /= 10) ++sc;
+      scale_out[m] = sc;
+    }
+  }
+  if (gen) *gen = t.gen;
   return PAS_OK;
 }
 

@@ -100,6 +100,13 @@ struct TasSnapshot {
   DerivedSync t_sync;  // the copies' build
 };
 
+// Word w of a presence row of N nodes without the bits at and past N (an upload may carry
+// them in the last word).
+__host__ __device__ __forceinline__ uint64_t word_mask(uint64_t bits, int64_t w, int32_t N) {
+  const int64_t lo = w * 64;
+  return lo + 64 > N ? bits & ((N - lo) >= 64 ? ~0ull : ((1ull << (N - lo)) - 1)) : bits;
+}
+
 // Device-resident GAS snapshot (node-major):
 //   n_cards int32 [N], cap int64 [N][Q], used int64 [N][K][Q]
 // core.EvaluateRule's CmpInt64 (operator.go:16-22) against column m's fixed point: the
@@ -334,6 +341,13 @@ void timing_end(pas_ctx* ctx, hipStream_t s, TimedLaunch* tl);
 
 void free_tas(pas_ctx* ctx);
 void free_gas(pas_ctx* ctx);
+// The device storage of a TAS snapshot shape into t (tas_snapshot.hip): every array and the
+// build scratch of n_nodes x n_metrics, content unset, t.n_nodes / n_metrics / row set; then
+// the wide parts of that shape (wide_flag zeroed on s).  A failure leaves what it had
+// allocated in t for tas_free_storage, which frees every array of t and nulls the pointers.
+int tas_alloc(pas_ctx* ctx, TasSnapshot& t, int32_t n_nodes, int32_t n_metrics, hipStream_t s);
+int tas_alloc_wide(pas_ctx* ctx, TasSnapshot& t, hipStream_t s);
+void tas_free_storage(TasSnapshot& t);
 
 // Per-translation-unit entry points used by the C-ABI layer.
 int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t n_nodes, int32_t n_metrics,
@@ -347,6 +361,13 @@ int tas_snapshot_update(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_
 int tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
                              const int64_t* d_whole, const uint32_t* d_nano,
                              const uint64_t* d_present, hipStream_t s);
+// The resident snapshot gathered into storage of n_nodes_new (>= the resident count) x
+// n_metrics_new (tas_reshape.hip): new column m is old column src_col[m] or, for -1, empty
+// (src_col: host [n_metrics_new], distinct old columns or -1; the caller has checked it and
+// the new shape against the snapshot's size limit).  No sort runs.  Synchronous on s; the old storage is freed once s and the context's stream are
+// idle.  An allocation failure leaves the resident snapshot as it was.
+int tas_snapshot_reshape(pas_ctx* ctx, uint64_t gen, int32_t n_nodes_new, int32_t n_metrics_new,
+                         const int32_t* src_col, hipStream_t s);
 int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
                     const int32_t* d_rule_off, const pas_rule* d_prio, const uint64_t* d_cand,
                     uint32_t flags, uint64_t* d_pass, int32_t* d_order, int32_t* d_len,

@@ -71,11 +71,6 @@ __device__ __forceinline__ int32_t row_of(const int32_t* rows, int32_t c) {
   return rows ? rows[c] : c;
 }
 
-__device__ __forceinline__ uint64_t word_mask(uint64_t bits, int64_t w, int32_t N) {
-  const int64_t lo = w * 64;
-  return lo + 64 > N ? bits & ((N - lo) >= 64 ? ~0ull : ((1ull << (N - lo)) - 1)) : bits;
-}
-
 // popc[c*W + w] = present nodes in word w of column c; the last entry (c*W == C*W) is 0 so
 // the exclusive scan yields every column's end.
 __global__ void popc_words(const uint64_t* __restrict__ present, int64_t total_words,
@@ -187,8 +182,7 @@ inline unsigned bits_for(int32_t c) {  // bits of the column index in the sort k
 
 // Temp storage of the largest (whole-snapshot, M columns of row R) sort of either key width.
 template <bool kWide>
-int alloc_sort_tmp(pas_ctx* ctx, size_t mr, int32_t M, hipStream_t s) {
-  TasSnapshot& t = ctx->tas;
+int alloc_sort_tmp(pas_ctx* ctx, TasSnapshot& t, size_t mr, int32_t M, hipStream_t s) {
   size_t sort_bytes = 0;
   SortKey* ka = static_cast<SortKey*>(t.keys_a);
   SortKey* kb = static_cast<SortKey*>(t.keys_b);
@@ -243,19 +237,7 @@ int build_columns(pas_ctx* ctx, int32_t C, const int32_t* d_rows, const int64_t*
 
 // Storage of the wide parts, on the first wide column of a snapshot shape.
 int ensure_wide(pas_ctx* ctx, hipStream_t s) {
-  TasSnapshot& t = ctx->tas;
-  if (t.wide_flag) return PAS_OK;
-  const size_t mn = (size_t)std::max<int64_t>((int64_t)t.n_metrics * t.n_nodes, 1);
-  const size_t mr = (size_t)std::max<int64_t>((int64_t)t.n_metrics * t.row, 1);
-  const size_t mm = (size_t)std::max(t.n_metrics, 1);
-  PAS_HIP(ctx, hipMalloc(&t.nano, sizeof(uint32_t) * mn));
-  PAS_HIP(ctx, hipMalloc(&t.sorted_nano, sizeof(uint32_t) * mr));
-  PAS_HIP(ctx, hipMalloc(&t.f1k_nano, sizeof(uint32_t) * (mr / 1024 + 1)));
-  PAS_HIP(ctx, hipMalloc(&t.f32_nano, sizeof(uint32_t) * (mr / 32 + 1)));
-  if (int rc = alloc_sort_tmp<true>(ctx, mr, t.n_metrics, s)) return rc;
-  PAS_HIP(ctx, hipMalloc(&t.wide_flag, mm));
-  PAS_HIP(ctx, hipMemsetAsync(t.wide_flag, 0, mm, s));
-  return PAS_OK;
+  return ctx->tas.wide_flag ? PAS_OK : tas_alloc_wide(ctx, ctx->tas, s);
 }
 
 // Columns cols[0 .. n_cols) become wide (1) or narrow (0): host marks, count, device flags.
@@ -332,6 +314,56 @@ __global__ void scale_fill_kernel(int64_t* tab, int32_t M) {
   }
 }
 
+// Storage of a snapshot shape (pas_internal.h): shared by the build and the reshape.
+int tas_alloc(pas_ctx* ctx, TasSnapshot& t, int32_t N, int32_t M, hipStream_t s) {
+  const int64_t W = w64(N);
+  const int32_t R = (int32_t)order_row(N);
+  const size_t mn = (size_t)std::max<int64_t>((int64_t)M * N, 1);
+  const size_t mr = (size_t)std::max<int64_t>((int64_t)M * R, 1);
+  const size_t mw = (size_t)std::max<int64_t>((int64_t)M * W, 1);
+  const size_t mm = (size_t)std::max(M, 1);
+  PAS_HIP(ctx, hipMalloc(&t.vals, sizeof(int64_t) * mn));
+  PAS_HIP(ctx, hipMalloc(&t.present, sizeof(uint64_t) * mw));
+  PAS_HIP(ctx, hipMalloc(&t.cnt, sizeof(int32_t) * mm));
+  PAS_HIP(ctx, hipMalloc(&t.sorted, sizeof(int64_t) * mr));
+  PAS_HIP(ctx, hipMalloc(&t.perm, sizeof(int32_t) * mr * kNumOrders));
+  PAS_HIP(ctx, hipMalloc(&t.f1k, sizeof(int64_t) * (mr / 1024 + 1)));
+  PAS_HIP(ctx, hipMalloc(&t.f32, sizeof(int64_t) * (mr / 32 + 1)));
+  PAS_HIP(ctx, hipMalloc(&t.keys_a, sizeof(SortKey) * mr));
+  PAS_HIP(ctx, hipMalloc(&t.keys_b, sizeof(SortKey) * mr));
+  PAS_HIP(ctx, hipMalloc(&t.ids_a, sizeof(int32_t) * mr));
+  PAS_HIP(ctx, hipMalloc(&t.ids_b, sizeof(int32_t) * mr));
+  PAS_HIP(ctx, hipMalloc(&t.popc, sizeof(uint32_t) * (mw + 1)));
+  PAS_HIP(ctx, hipMalloc(&t.word_scan, sizeof(uint32_t) * (mw + 1)));
+  PAS_HIP(ctx, hipMalloc(&t.rows, sizeof(int32_t) * mm));
+  PAS_HIP(ctx, hipMalloc(&t.scale_tab, sizeof(int64_t) * 2 * mm));
+  // temp storage for the largest (whole-snapshot) sort and scan
+  if (int rc = alloc_sort_tmp<false>(ctx, t, mr, M, s)) return rc;
+  size_t scan_bytes = 0;
+  PAS_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, t.popc, t.word_scan, 0u,
+                                       (size_t)(mw + 1), rocprim::plus<uint32_t>(), s));
+  t.scan_tmp_bytes = std::max<size_t>(scan_bytes, 16);
+  PAS_HIP(ctx, hipMalloc(&t.scan_tmp, t.scan_tmp_bytes));
+  t.n_nodes = N;
+  t.n_metrics = M;
+  t.row = R;
+  return PAS_OK;
+}
+
+int tas_alloc_wide(pas_ctx* ctx, TasSnapshot& t, hipStream_t s) {
+  const size_t mn = (size_t)std::max<int64_t>((int64_t)t.n_metrics * t.n_nodes, 1);
+  const size_t mr = (size_t)std::max<int64_t>((int64_t)t.n_metrics * t.row, 1);
+  const size_t mm = (size_t)std::max(t.n_metrics, 1);
+  PAS_HIP(ctx, hipMalloc(&t.nano, sizeof(uint32_t) * mn));
+  PAS_HIP(ctx, hipMalloc(&t.sorted_nano, sizeof(uint32_t) * mr));
+  PAS_HIP(ctx, hipMalloc(&t.f1k_nano, sizeof(uint32_t) * (mr / 1024 + 1)));
+  PAS_HIP(ctx, hipMalloc(&t.f32_nano, sizeof(uint32_t) * (mr / 32 + 1)));
+  if (int rc = alloc_sort_tmp<true>(ctx, t, mr, t.n_metrics, s)) return rc;
+  PAS_HIP(ctx, hipMalloc(&t.wide_flag, mm));
+  PAS_HIP(ctx, hipMemsetAsync(t.wide_flag, 0, mm, s));
+  return PAS_OK;
+}
+
 int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t N, int32_t M,
                        const int64_t* d_vals, const uint64_t* d_present, hipStream_t s) {
   TasSnapshot& t = ctx->tas;
@@ -346,35 +378,7 @@ int tas_snapshot_build(pas_ctx* ctx, uint64_t gen, int32_t N, int32_t M,
   if (t.n_nodes != N || t.n_metrics != M || !t.cnt) {
     PAS_HIP(ctx, hipStreamSynchronize(s));
     free_tas(ctx);
-    const size_t mn = (size_t)std::max<int64_t>(MN, 1);
-    const size_t mr = (size_t)std::max<int64_t>(MR, 1);
-    const size_t mw = (size_t)std::max<int64_t>((int64_t)M * W, 1);
-    const size_t mm = (size_t)std::max(M, 1);
-    PAS_HIP(ctx, hipMalloc(&t.vals, sizeof(int64_t) * mn));
-    PAS_HIP(ctx, hipMalloc(&t.present, sizeof(uint64_t) * mw));
-    PAS_HIP(ctx, hipMalloc(&t.cnt, sizeof(int32_t) * mm));
-    PAS_HIP(ctx, hipMalloc(&t.sorted, sizeof(int64_t) * mr));
-    PAS_HIP(ctx, hipMalloc(&t.perm, sizeof(int32_t) * mr * kNumOrders));
-    PAS_HIP(ctx, hipMalloc(&t.f1k, sizeof(int64_t) * (mr / 1024 + 1)));
-    PAS_HIP(ctx, hipMalloc(&t.f32, sizeof(int64_t) * (mr / 32 + 1)));
-    PAS_HIP(ctx, hipMalloc(&t.keys_a, sizeof(SortKey) * mr));
-    PAS_HIP(ctx, hipMalloc(&t.keys_b, sizeof(SortKey) * mr));
-    PAS_HIP(ctx, hipMalloc(&t.ids_a, sizeof(int32_t) * mr));
-    PAS_HIP(ctx, hipMalloc(&t.ids_b, sizeof(int32_t) * mr));
-    PAS_HIP(ctx, hipMalloc(&t.popc, sizeof(uint32_t) * (mw + 1)));
-    PAS_HIP(ctx, hipMalloc(&t.word_scan, sizeof(uint32_t) * (mw + 1)));
-    PAS_HIP(ctx, hipMalloc(&t.rows, sizeof(int32_t) * mm));
-    PAS_HIP(ctx, hipMalloc(&t.scale_tab, sizeof(int64_t) * 2 * mm));
-    // temp storage for the largest (whole-snapshot) sort and scan
-    if (int rc = alloc_sort_tmp<false>(ctx, mr, M, s)) return rc;
-    size_t scan_bytes = 0;
-    PAS_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, t.popc, t.word_scan, 0u,
-                                         (size_t)(mw + 1), rocprim::plus<uint32_t>(), s));
-    t.scan_tmp_bytes = std::max<size_t>(scan_bytes, 16);
-    PAS_HIP(ctx, hipMalloc(&t.scan_tmp, t.scan_tmp_bytes));
-    t.n_nodes = N;
-    t.n_metrics = M;
-    t.row = R;
+    if (int rc = tas_alloc(ctx, t, N, M, s)) return rc;
   }
   t.scale_host.assign(2 * (size_t)M, 0);
   for (int32_t m = 0; m < M; ++m) {

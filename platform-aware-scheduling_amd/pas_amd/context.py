@@ -287,6 +287,38 @@ class Context:
             self._l.pas_tas_snapshot_drop(self._h)
             raise
 
+    def tas_snapshot_reshape(self, gen_from: int, gen_to: int, n_nodes: int, n_metrics: int,
+                             src_col=None, stream=None):
+        """Grow the node count and add, drop or move metric columns of the resident snapshot on
+        the device (pas_tas_snapshot_reshape): new column m is old column src_col[m], or empty
+        for -1; None keeps the old columns in place and appends empty ones."""
+        src = None
+        if src_col is not None:
+            src = np.ascontiguousarray(src_col, dtype=np.int32)
+            assert src.shape == (n_metrics,), (src.shape, n_metrics)
+            if not src.size:  # an empty map (every column dropped) is still a map, not NULL
+                src = np.zeros(1, np.int32)
+        self._check(self._l.pas_tas_snapshot_reshape(
+            self._h, gen_from, gen_to, n_nodes, n_metrics, _ptr(src), _stream(stream)),
+            "pas_tas_snapshot_reshape")
+        self.n_nodes, self.n_metrics = n_nodes, n_metrics
+
+    def tas_snapshot_get(self):
+        """(gen, vals [M][N] int64, present [M][W64] uint64, scale [M] int32, wide [M] uint8,
+        nano [M][N] uint32) of the resident snapshot (pas_tas_snapshot_get): present without
+        bits past n_nodes, values and nanos meaningful only where the bit is set."""
+        _, n, m = self.tas_snapshot_info()
+        g = c_uint64()
+        vals = np.zeros((m, n), np.int64)
+        present = np.zeros((m, w64(n)), np.uint64)
+        scale = np.zeros(m, np.int32)
+        wide = np.zeros(m, np.uint8)
+        nano = np.zeros((m, n), np.uint32)
+        self._check(self._l.pas_tas_snapshot_get(self._h, byref(g), _ptr(vals), _ptr(present),
+                                                 _ptr(scale), _ptr(wide), _ptr(nano)),
+                    "pas_tas_snapshot_get")
+        return g.value, vals, present, scale, wide, nano
+
     def tas_snapshot_info(self):
         g = c_uint64()
         n = c_int32()

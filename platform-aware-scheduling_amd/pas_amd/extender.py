@@ -101,6 +101,20 @@ class MetricsExtender:
         self.table = wire.NodeTable(node_names)
         self.name_table = wire.NameTable(node_names)
 
+    def snapshot_changed(self, gen: int, node_names: Sequence[Optional[str]],
+                         metric_names: Sequence[Optional[str]]):
+        """The snapshot's generation, slots and columns after the cache changed them
+        (TasCache.gen / node_names / metric_names): None in node_names is a spare slot, listed
+        as "" in the name table and left out of node_index (it has no present bit, so a request
+        naming "" meets a node without metrics); None in metric_names is a free column, left
+        out of metric_index."""
+        self.gen = gen
+        self.node_names = [n if n is not None else "" for n in node_names]
+        self.node_index = {n: i for i, n in enumerate(node_names) if n is not None}
+        self.metric_index = {m: i for i, m in enumerate(metric_names) if m is not None}
+        self.table = wire.NodeTable(self.node_names)
+        self.name_table = wire.NameTable(self.node_names)
+
     # -- helpers ------------------------------------------------------------------
     def _decode(self, body: bytes):
         """DecodeExtenderRequest (:63-78) through pas_decode_args: (info, request node ids,
