@@ -245,6 +245,31 @@ int pas_tas_snapshot_reshape(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
                              int32_t n_nodes_new, int32_t n_metrics_new,
                              const int32_t* src_col /* host [n_metrics_new], or NULL */,
                              void* hip_stream);
+/* Renumber the node slots of the resident snapshot on the device: dead slots are dropped, the
+ * others move down, without a host copy and without a sort.  Every refresh of the reference's
+ * cache replaces a metric's whole node map (autoupdating.go:62-72), so a node that left the
+ * cluster is in no map after one sync period; here its slot stays until a compaction drops it.
+ *   n_nodes_new    >= 0; smaller than, equal to or larger than the resident n_nodes
+ *   src_node       host [n_nodes_new]: new slot j holds old slot src_node[j] with its value,
+ *                  nano and presence in every column, or, for -1, nothing (a spare slot: no
+ *                  present bit in any column).  The entries >= 0 are strictly increasing and <
+ *                  n_nodes, -1 may stand anywhere; anything else is PAS_EINVAL.  An old slot that
+ *                  no entry names is dropped from every column and from its three orders.
+ * Removing ids from a sorted list leaves it sorted and the monotone map keeps ties in ascending
+ * node index, so the orders are compacted in place of being sorted again: a stable stream
+ * compaction of the order rows (counts per 1024-position segment, their scan, a ranked
+ * scatter; no atomics, so the result is reproducible) and a gather of the value rows.  Metric
+ * columns, recorded scales and the narrow / wide kinds stay as they are.  Generation, errors,
+ * limits and storage are pas_tas_snapshot_reshape's: gen_from is checked (PAS_ESTALE,
+ * PAS_ENOSNAP; nothing changed), PAS_ECAPACITY before anything is allocated, PAS_ENOMEM leaves
+ * the old snapshot valid, synchronous on hip_stream with the old storage freed after both
+ * streams are synchronized, a HIP failure after the launch leaves PAS_ENOSNAP; the identity map
+ * moves the generation only.  Afterwards every evaluation answers what it would on a snapshot
+ * built from the same content by pas_tas_snapshot_set + pas_tas_snapshot_set_scale +
+ * pas_tas_snapshot_update_wide. */
+int pas_tas_snapshot_compact(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                             int32_t n_nodes_new, const int32_t* src_node /* host [n_nodes_new] */,
+                             void* hip_stream);
 /* Read back the resident snapshot and its generation; any output may be NULL.  present_out
  * has the bits at and past n_nodes cleared; values and nanos are meaningful only where the
  * bit is set.  scale_out is each column's recorded decimal scale, wide_out 1 for a wide
@@ -844,6 +869,19 @@ int pas_gas_nodes_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to
  * same number of slots with pas_tas_snapshot_reshape (spare slots: no present bit). */
 int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
                             int32_t n_nodes_new, int32_t max_cards_new, void* hip_stream);
+/* Renumber the node slots of the resident snapshot on the device, with the arguments and the
+ * src_node contract of pas_tas_snapshot_compact: new row j takes n_cards, cap [n_res] and used
+ * [max_cards][n_res] of old row src_node[j], or, for -1, n_cards -1, cap 0 and usage 0; a row no
+ * entry names is gone with its usage.  The reference keeps usage by node and card name and
+ * never deletes it (nodeStatuses, node_resource_cache.go:64,259-272): a caller that wants that
+ * keeps the rows that still hold usage.  max_cards is unchanged.  One gather kernel into new
+ * storage; generation, errors and the freeing of the old storage as in
+ * pas_gas_snapshot_resize, and the fit's derived values are computed again by the next fit.
+ * pas_tas_gas_topk*_device still needs equal node counts: a caller compacts both snapshots with
+ * the same src_node. */
+int pas_gas_snapshot_compact(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                             int32_t n_nodes_new, const int32_t* src_node /* host [n_nodes_new] */,
+                             void* hip_stream);
 
 /* ------------------------------------------------------------------------- */
 /* Node-sharded snapshots                                  */

@@ -23,7 +23,10 @@
 // gas_commit.hip indexes its row dynamically.
 //
 // pas_gas_snapshot_resize re-pitches [N][K][Q] -> [N'][K'][Q] into new storage with one
-// bandwidth-bound kernel (zero fill, -1 for the new nodes' counts).
+// bandwidth-bound kernel (zero fill, -1 for the new nodes' counts).  pas_gas_snapshot_compact
+// renumbers the node slots the same way: new row j is old row src_node[j], whole (a slot is
+// all a deleted node's usage is keyed by here, where the reference keys it by name), or a spare
+// row for -1; the rows no entry names are gone.
 #include <hip/hip_runtime.h>
 
 #include "gas_group.h"
@@ -127,6 +130,30 @@ __global__ __launch_bounds__(256) void gas_repitch_kernel(
   if (t < (int64_t)N2 * Q) cap2[t] = t < (int64_t)N * Q ? cap[t] : 0;
 }
 
+// [N][K][Q] -> [N2][K][Q] through src [N2] (an old row or -1): thread t writes element t of the
+// new usage, and the new count and capacities of its index while t is inside those arrays
+// (spare rows: -1, 0, 0).
+__global__ __launch_bounds__(256) void gas_compact_kernel(
+    int32_t K, int32_t Q, int32_t N2, const int32_t* __restrict__ src,
+    const int32_t* __restrict__ n_cards, const int64_t* __restrict__ cap,
+    const int64_t* __restrict__ used, int32_t* __restrict__ n_cards2, int64_t* __restrict__ cap2,
+    int64_t* __restrict__ used2) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t kq = (int64_t)K * Q;
+  if (t < N2 * kq) {
+    const int64_t s = src[t / kq];
+    used2[t] = s >= 0 ? used[s * kq + t % kq] : 0;
+  }
+  if (t < N2) {
+    const int32_t s = src[t];
+    n_cards2[t] = s >= 0 ? n_cards[s] : -1;
+  }
+  if (t < (int64_t)N2 * Q) {
+    const int64_t s = src[t / Q];
+    cap2[t] = s >= 0 ? cap[s * Q + t % Q] : 0;
+  }
+}
+
 }  // namespace
 
 int gas_nodes_update_launch(pas_ctx* ctx, int32_t n_updates, const int32_t* d_node,
@@ -158,6 +185,19 @@ int gas_repitch_launch(pas_ctx* ctx, int32_t n_nodes_new, int32_t max_cards_new,
   gas_repitch_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
       g.n_nodes, g.max_cards, g.n_res, n_nodes_new, max_cards_new, g.n_cards, g.cap, g.used,
       d_n_cards_new, d_cap_new, d_used_new);
+  PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
+}
+
+int gas_compact_launch(pas_ctx* ctx, int32_t n_nodes_new, const int32_t* d_src_node,
+                       int32_t* d_n_cards_new, int64_t* d_cap_new, int64_t* d_used_new,
+                       hipStream_t s) {
+  const GasSnapshot& g = ctx->gas;
+  const int64_t total = (int64_t)n_nodes_new * g.max_cards * g.n_res;  // (K, Q >= 1)
+  if (total == 0) return PAS_OK;
+  gas_compact_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
+      g.max_cards, g.n_res, n_nodes_new, d_src_node, g.n_cards, g.cap, g.used, d_n_cards_new,
+      d_cap_new, d_used_new);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
 }

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -570,6 +571,48 @@ int pas_tas_snapshot_reshape(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
   if ((rc = activate(ctx))) return rc;
   return tas_snapshot_reshape(ctx, gen_to, n_nodes_new, n_metrics_new, src.data(),
                               pick_stream(ctx, hip_stream));
+}
+
+// The node map of the compactions: n_new >= 0 entries (a host array), each -1 or an old slot
+// below n_old, the old slots strictly increasing.  *identity: n_new == n_old and entry j is j.
+static int check_node_map(pas_ctx* ctx, int32_t n_old, int32_t n_new, const int32_t* src_node,
+                          const std::string& fn, bool* identity) {
+  if (n_new < 0 || (n_new > 0 && !src_node))
+    return set_error(ctx, PAS_EINVAL, fn + ": n_nodes_new < 0, or no src_node");
+  int32_t last = -1;
+  *identity = n_new == n_old;
+  for (int32_t j = 0; j < n_new; ++j) {
+    const int32_t s = src_node[j];
+    *identity &= s == j;
+    if (s == -1) continue;
+    if (s < -1 || s >= n_old || s <= last)
+      return set_error(ctx, PAS_EINVAL,
+                       fn + ": src_node entries must be -1 or strictly increasing slots < n_nodes");
+    last = s;
+  }
+  return PAS_OK;
+}
+
+int pas_tas_snapshot_compact(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                             int32_t n_nodes_new, const int32_t* src_node, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen_from);
+  if (rc) return rc;
+  TasSnapshot& t = ctx->tas;
+  bool identity;
+  if ((rc = check_node_map(ctx, t.n_nodes, n_nodes_new, src_node, "pas_tas_snapshot_compact",
+                           &identity)))
+    return rc;
+  // pas_tas_snapshot_set's limit, before anything of that size is allocated, here or there
+  if ((int64_t)t.n_metrics * order_row(n_nodes_new) * kNumOrders > 0x7fffffffLL)
+    return set_error(ctx, PAS_ECAPACITY,
+                     "TAS snapshot: 3 * n_metrics * padded n_nodes must be < 2^31");
+  if (identity) {  // every slot in place
+    t.gen = gen_to;
+    return PAS_OK;
+  }
+  if ((rc = activate(ctx))) return rc;
+  return tas_snapshot_compact(ctx, gen_to, n_nodes_new, src_node, pick_stream(ctx, hip_stream));
 }
 
 int pas_tas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* vals_out, uint64_t* present_out,
@@ -1601,33 +1644,26 @@ int pas_gas_nodes_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
   return gas_write_finish(ctx, gen_to, n_updates > 0, st, fn);
 }
 
-int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
-                            int32_t n_nodes_new, int32_t max_cards_new, void* hip_stream) {
-  if (!ctx) return PAS_EINVAL;
-  int rc = check_gas_gen(ctx, gen_from);
-  if (rc) return rc;
+// The resident snapshot moved into new storage of n_nodes_new x max_cards_new, for the calls
+// that change its shape: fill(n_cards, cap, used, derived) launches the copy on s (derived: the
+// new storage for the fit's derived values, unset until the next fit, free as staging).  The
+// old storage is freed after s and the context's stream are idle.
+using GasFill = std::function<int(int32_t*, int64_t*, int64_t*, void*)>;
+static int gas_restore(pas_ctx* ctx, uint64_t gen_to, int32_t n_nodes_new, int32_t max_cards_new,
+                       hipStream_t s, const char* fn, const GasFill& fill) {
   GasSnapshot& g = ctx->gas;
-  if (n_nodes_new < g.n_nodes || max_cards_new < g.max_cards)
-    return set_error(ctx, PAS_EINVAL, "pas_gas_snapshot_resize: the snapshot only grows");
-  if (max_cards_new > PAS_GAS_MAX_CARDS)
-    return set_error(ctx, PAS_ECAPACITY, "pas_gas_snapshot_resize: max_cards <= 64 supported");
-  if (n_nodes_new == g.n_nodes && max_cards_new == g.max_cards) {
-    g.gen = gen_to;
-    return PAS_OK;
-  }
-  if ((rc = activate(ctx))) return rc;
-  hipStream_t s = pick_stream(ctx, hip_stream);
   const size_t nn = (size_t)std::max(n_nodes_new, 1), Q = (size_t)g.n_res;
   int32_t* n_cards = nullptr;
   int64_t *cap = nullptr, *used = nullptr;
   void *derived = nullptr, *free_t = nullptr;
+  int rc = PAS_OK;
   hipError_t e = hipMalloc(&n_cards, sizeof(int32_t) * nn);
   if (e == hipSuccess) e = hipMalloc(&cap, sizeof(int64_t) * nn * Q);
   if (e == hipSuccess) e = hipMalloc(&used, sizeof(int64_t) * nn * (size_t)max_cards_new * Q);
   if (e == hipSuccess) e = hipMalloc(&derived, 64 + sizeof(int32_t) * nn);
   if (e == hipSuccess) e = hipMalloc(&free_t, sizeof(int64_t) * PAS_GAS_PACKED * Q * nn);
   if (e == hipSuccess) {
-    rc = gas_repitch_launch(ctx, n_nodes_new, max_cards_new, n_cards, cap, used, s);
+    rc = fill(n_cards, cap, used, derived);
     // the old storage is freed below: its readers (the copy, and earlier calls of the host
     // forms on the context's stream) have finished by then
     if (!rc) e = hipStreamSynchronize(s);
@@ -1636,7 +1672,7 @@ int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
   if (rc || e != hipSuccess) {  // the resident snapshot was only read: it stays as it is
     for (void* p : {(void*)n_cards, (void*)cap, (void*)used, derived, free_t})
       if (p) (void)hipFree(p);
-    return rc ? rc : check_hip(ctx, e, "pas_gas_snapshot_resize");
+    return rc ? rc : check_hip(ctx, e, fn);
   }
   free_ptr(reinterpret_cast<void*&>(g.n_cards));
   free_ptr(reinterpret_cast<void*&>(g.cap));
@@ -1653,6 +1689,57 @@ int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
   g.gen = gen_to;
   ++g.epoch;  // the next fit derives its values again, into the new storage
   return PAS_OK;
+}
+
+int pas_gas_snapshot_resize(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                            int32_t n_nodes_new, int32_t max_cards_new, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_gas_gen(ctx, gen_from);
+  if (rc) return rc;
+  GasSnapshot& g = ctx->gas;
+  if (n_nodes_new < g.n_nodes || max_cards_new < g.max_cards)
+    return set_error(ctx, PAS_EINVAL, "pas_gas_snapshot_resize: the snapshot only grows");
+  if (max_cards_new > PAS_GAS_MAX_CARDS)
+    return set_error(ctx, PAS_ECAPACITY, "pas_gas_snapshot_resize: max_cards <= 64 supported");
+  if (n_nodes_new == g.n_nodes && max_cards_new == g.max_cards) {
+    g.gen = gen_to;
+    return PAS_OK;
+  }
+  if ((rc = activate(ctx))) return rc;
+  hipStream_t s = pick_stream(ctx, hip_stream);
+  return gas_restore(ctx, gen_to, n_nodes_new, max_cards_new, s, "pas_gas_snapshot_resize",
+                     [&](int32_t* n_cards, int64_t* cap, int64_t* used, void*) {
+                       return gas_repitch_launch(ctx, n_nodes_new, max_cards_new, n_cards, cap,
+                                                 used, s);
+                     });
+}
+
+int pas_gas_snapshot_compact(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                             int32_t n_nodes_new, const int32_t* src_node, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const char* fn = "pas_gas_snapshot_compact";
+  int rc = check_gas_gen(ctx, gen_from);
+  if (rc) return rc;
+  GasSnapshot& g = ctx->gas;
+  bool identity;
+  if ((rc = check_node_map(ctx, g.n_nodes, n_nodes_new, src_node, fn, &identity))) return rc;
+  if (identity) {  // every row in place
+    g.gen = gen_to;
+    return PAS_OK;
+  }
+  if ((rc = activate(ctx))) return rc;
+  hipStream_t s = pick_stream(ctx, hip_stream);
+  return gas_restore(ctx, gen_to, n_nodes_new, g.max_cards, s, fn,
+                     [&](int32_t* n_cards, int64_t* cap, int64_t* used, void* derived) {
+                       if (n_nodes_new == 0) return (int)PAS_OK;
+                       // the map rides in the new derived storage; src_node is the caller's
+                       // again once s has been synchronized
+                       int32_t* d_src = static_cast<int32_t*>(derived);
+                       PAS_HIP(ctx, hipMemcpyAsync(d_src, src_node,
+                                                   sizeof(int32_t) * (size_t)n_nodes_new,
+                                                   hipMemcpyHostToDevice, s));
+                       return gas_compact_launch(ctx, n_nodes_new, d_src, n_cards, cap, used, s);
+                     });
 }
 
 // Host path of pas_gas_fit / pas_gas_fit_ex: validates, uploads the batch, runs the fit and

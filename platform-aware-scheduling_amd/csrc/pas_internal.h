@@ -36,7 +36,7 @@ struct DerivedSync {
 
 // Device-resident TAS snapshot.  Layout in HBM (M metrics, N nodes, R = order_row(N)):
 //   vals     int64 [M][N]      raw v_milli (deschedule sweep reads it directly)
-//   present  uint64 [M][W64]
+//   present  uint64 [M][W64]   (vals and present have room for one column when M = 0)
 //   cnt      int32 [M]         nodes that have metric m
 //   sorted   int64 [M][R]      ascending values of the present nodes (first cnt[m])
 //   perm     int32 [3][M][R]   node ids in asc / desc / index order (first cnt[m]); the
@@ -368,6 +368,13 @@ int tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const i
 // idle.  An allocation failure leaves the resident snapshot as it was.
 int tas_snapshot_reshape(pas_ctx* ctx, uint64_t gen, int32_t n_nodes_new, int32_t n_metrics_new,
                          const int32_t* src_col, hipStream_t s);
+// The resident snapshot with its node slots renumbered into storage of n_nodes_new slots
+// (tas_compact.hip): new slot j is old slot src_node[j] or, for -1, spare; an old slot no
+// entry names is dropped from every column (src_node: host [n_nodes_new], its non-negative
+// entries strictly increasing and below the resident count; the caller has checked it and the
+// new shape against the size limit).  No sort runs.  Synchronous and failing as the reshape.
+int tas_snapshot_compact(pas_ctx* ctx, uint64_t gen, int32_t n_nodes_new,
+                         const int32_t* src_node, hipStream_t s);
 int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
                     const int32_t* d_rule_off, const pas_rule* d_prio, const uint64_t* d_cand,
                     uint32_t flags, uint64_t* d_pass, int32_t* d_order, int32_t* d_len,
@@ -471,6 +478,12 @@ int gas_nodes_update_launch(pas_ctx* ctx, int32_t n_updates, const int32_t* d_no
 // The resident n_cards / cap / used copied into storage of n_nodes_new x max_cards_new (both
 // >= the resident shape), new nodes -1 / 0 / 0 and new card slots 0; reads the snapshot only.
 int gas_repitch_launch(pas_ctx* ctx, int32_t n_nodes_new, int32_t max_cards_new,
+                       int32_t* d_n_cards_new, int64_t* d_cap_new, int64_t* d_used_new,
+                       hipStream_t s);
+// The resident rows gathered into storage of n_nodes_new x max_cards: new row j is old row
+// d_src_node[j] (device [n_nodes_new], every entry -1 or below the resident count), or -1 / 0 /
+// 0 for -1; reads the snapshot only.
+int gas_compact_launch(pas_ctx* ctx, int32_t n_nodes_new, const int32_t* d_src_node,
                        int32_t* d_n_cards_new, int64_t* d_cap_new, int64_t* d_used_new,
                        hipStream_t s);
 // Batch placement (gas_place.hip): the rounds of pas_gas_place_device on s, returning when the

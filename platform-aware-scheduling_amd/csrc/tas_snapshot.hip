@@ -318,9 +318,11 @@ __global__ void scale_fill_kernel(int64_t* tab, int32_t M) {
 int tas_alloc(pas_ctx* ctx, TasSnapshot& t, int32_t N, int32_t M, hipStream_t s) {
   const int64_t W = w64(N);
   const int32_t R = (int32_t)order_row(N);
-  const size_t mn = (size_t)std::max<int64_t>((int64_t)M * N, 1);
+  // vals / present hold one column even with no metric: the deschedule sweep reads column 0
+  // over all N nodes for a rule whose metric is out of range (and drops what it read)
+  const size_t mn = (size_t)std::max<int64_t>((int64_t)std::max(M, 1) * N, 1);
   const size_t mr = (size_t)std::max<int64_t>((int64_t)M * R, 1);
-  const size_t mw = (size_t)std::max<int64_t>((int64_t)M * W, 1);
+  const size_t mw = (size_t)std::max<int64_t>((int64_t)std::max(M, 1) * W, 1);
   const size_t mm = (size_t)std::max(M, 1);
   PAS_HIP(ctx, hipMalloc(&t.vals, sizeof(int64_t) * mn));
   PAS_HIP(ctx, hipMalloc(&t.present, sizeof(uint64_t) * mw));

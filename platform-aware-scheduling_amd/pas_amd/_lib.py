@@ -134,6 +134,7 @@ SIGNATURES = {
         c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P]),
     "pas_tas_snapshot_wide_count": (c_int, [_P, POINTER(c_int32)]),
     "pas_tas_snapshot_reshape": (c_int, [_P, c_uint64, c_uint64, c_int32, c_int32, _P, _P]),
+    "pas_tas_snapshot_compact": (c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P]),
     "pas_tas_snapshot_get": (c_int, [_P, POINTER(c_uint64), _P, _P, _P, _P, _P]),
     "pas_tas_snapshot_drop": (c_int, [_P]),
     "pas_tas_snapshot_info":(c_int, [_P, POINTER(c_uint64), POINTER(c_int32), POINTER(c_int32)]),
@@ -246,6 +247,7 @@ SIGNATURES = {
     "pas_gas_nodes_update_device": (
         c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P, _P]),
     "pas_gas_snapshot_resize": (c_int, [_P, c_uint64, c_uint64, c_int32, c_int32, _P]),
+    "pas_gas_snapshot_compact": (c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P]),
     "pas_tas_topk_device": (
         c_int,
         [_P, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P],

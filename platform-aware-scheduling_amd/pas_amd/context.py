@@ -303,6 +303,17 @@ class Context:
             "pas_tas_snapshot_reshape")
         self.n_nodes, self.n_metrics = n_nodes, n_metrics
 
+    def tas_snapshot_compact(self, gen_from: int, gen_to: int, src_node, stream=None):
+        """Renumber the node slots of the resident snapshot on the device
+        (pas_tas_snapshot_compact): new slot j holds old slot src_node[j], or nothing for -1; the
+        old slots that src_node does not name are dropped.  The entries >= 0 are strictly
+        increasing."""
+        src = np.ascontiguousarray(src_node, dtype=np.int32).reshape(-1)
+        self._check(self._l.pas_tas_snapshot_compact(
+            self._h, gen_from, gen_to, len(src), _ptr(src) if src.size else None,
+            _stream(stream)), "pas_tas_snapshot_compact")
+        self.n_nodes = len(src)
+
     def tas_snapshot_get(self):
         """(gen, vals [M][N] int64, present [M][W64] uint64, scale [M] int32, wide [M] uint8,
         nano [M][N] uint32) of the resident snapshot (pas_tas_snapshot_get): present without
@@ -840,6 +851,16 @@ class Context:
                                                     max_cards, _stream(stream)),
                     "pas_gas_snapshot_resize")
         self.gas_shape = (n_nodes, max_cards, self.gas_shape[2])
+
+    def gas_snapshot_compact(self, gen_from: int, gen_to: int, src_node, stream=None):
+        """Renumber the node rows of the resident GAS snapshot on the device
+        (pas_gas_snapshot_compact): new row j is old row src_node[j], or a spare row for -1;
+        gas_shape follows."""
+        src = np.ascontiguousarray(src_node, dtype=np.int32).reshape(-1)
+        self._check(self._l.pas_gas_snapshot_compact(
+            self._h, gen_from, gen_to, len(src), _ptr(src) if src.size else None,
+            _stream(stream)), "pas_gas_snapshot_compact")
+        self.gas_shape = (len(src),) + tuple(self.gas_shape[1:])
 
     def gas_fit_device(self, gen: int, n_pods: int, max_containers: int, i915_index: int, req_t,
                        mask_t, ncont_t, res_t, stream=None):

@@ -107,7 +107,8 @@ class MetricsExtender:
         (TasCache.gen / node_names / metric_names): None in node_names is a spare slot, listed
         as "" in the name table and left out of node_index (it has no present bit, so a request
         naming "" meets a node without metrics); None in metric_names is a free column, left
-        out of metric_index."""
+        out of metric_index.  A compaction (TasCache.compact) renumbers the slots: call this
+        after it as after a reshape."""
         self.gen = gen
         self.node_names = [n if n is not None else "" for n in node_names]
         self.node_index = {n: i for i, n in enumerate(node_names) if n is not None}

@@ -117,7 +117,8 @@ class GasCache:
     usage in a parked slot and has it again when the label lists it again, as the reference's
     nodeStatuses keeps it by card name.  A deleted node keeps its slot and name with n_cards
     -1 and every card parked, so its usage is there when the name returns; a new name takes a
-    spare slot.  The snapshot grows on the device (pas_gas_snapshot_resize) when no spare slot
+    spare slot.  compact() drops the spare slots and the deleted nodes without usage; nothing
+    calls it implicitly.  The snapshot grows on the device (pas_gas_snapshot_resize) when no spare slot
     is left, by max(64, N / 8) slots rounded up to 64, and when a label lists more cards than
     max_cards, to the next of 8 / 16 / 64; parking never grows it.  card_names is changed in
     place (a GASExtender sharing the list sees the changes; GASExtender.nodes_changed takes
@@ -381,6 +382,40 @@ class GasCache:
         close()
         close_nodes()
         return results  # type: ignore[return-value]
+
+    def compact(self, spare_nodes: int = 0) -> List[int]:
+        """Drop the dead node slots with one pas_gas_snapshot_compact call and return the map
+        applied: new slot j is old slot map[j], or a spare slot for -1.
+
+        The queue is flushed first (a caller that wants the items' outcomes calls flush()
+        itself before).  Dead are the spare slots and the slots of deleted nodes (n_cards -1)
+        whose usage, read back from the device, is zero in every card slot, label and parked.
+        A deleted node that still holds usage keeps its slot and name, as the reference keeps
+        its nodeStatuses entry by name (node_resource_cache.go:64,259-272).  The live slots
+        keep their order and spare_nodes spare slots follow them; node_names, card_names (in
+        place), parked and the n_cards / cap rows move with them.  A TasCache over the same
+        slots applies the same map: src = gas.compact(); tas.compact(src); its metric entries
+        of names that lost their slot are skipped_nodes from then on.
+        GASExtender.nodes_changed takes the new node_names."""
+        self.flush()
+        _, n_cards, cap = self.ctx.gas_snapshot_get_nodes()
+        _, used = self.ctx.gas_snapshot_get()
+        idle = ~used.reshape(len(used), -1).any(axis=1)
+        src = [i for i, name in enumerate(self.node_names)
+               if name is not None and not (n_cards[i] == -1 and idle[i])]
+        src += [-1] * int(spare_nodes)
+        self.ctx.gas_snapshot_compact(self.gen, self.gen + 1, src)
+        self.gen += 1
+        self.node_names = [self.node_names[s] if s >= 0 else None for s in src]
+        self.node_index = {n: i for i, n in enumerate(self.node_names) if n is not None}
+        self.card_names[:] = [self.card_names[s] if s >= 0 else [] for s in src]
+        self.parked = [self.parked[s] if s >= 0 else [] for s in src]
+        if self.n_cards is not None and self.cap is not None:
+            at = np.asarray(src, np.int64)
+            self.n_cards = np.where(at >= 0, n_cards[at], -1).astype(np.int32)
+            self.cap = np.where((at >= 0)[:, None], cap[at], 0).astype(np.int64)
+            self._rows_owned = True
+        return src
 
     def rebuild(self, pods: Sequence[dict]) -> List[Tuple[str, str, str]]:
         """The cold start: zero usage, then every annotated pod as the informer's initial

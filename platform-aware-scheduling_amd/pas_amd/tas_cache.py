@@ -55,7 +55,8 @@ class TasCache:
     snapshot grows by max(64, N / 8) slots rounded up to 64 (GasCache's rule).  A name with
     first data takes a free column; when none is left the snapshot grows by 8 columns.  A
     column freed by delete_metric is emptied (no present bit, milli, narrow) and reused.  A
-    node that no metric lists any more keeps its slot.  One refresh issues at most one
+    node that no metric lists any more keeps its slot until compact() drops it; nothing calls
+    compact() implicitly.  One refresh issues at most one
     pas_tas_snapshot_reshape for all its new nodes and columns, then at most one
     pas_tas_snapshot_update for its narrow columns, one pas_tas_snapshot_update_wide for its
     wide ones, and one pas_tas_snapshot_set_scale when a narrow column's scale changed (a
@@ -165,6 +166,39 @@ class TasCache:
                 continue
             self._write(name, result, pending)
         self._flush(pending)
+
+    def compact(self, src_node: Optional[Sequence[int]] = None,
+                spare_nodes: int = 0) -> List[int]:
+        """Drop the dead node slots with one pas_tas_snapshot_compact call and return the map
+        applied: new slot j holds old slot map[j], or nothing for -1.
+
+        Without a map (a cache that owns its slots): a slot is dead when it is spare or no held
+        map in `data` lists its name, as the reference's maps forget a node one refresh after
+        it left (autoupdating.go:62-72); the live slots keep their order and spare_nodes spare
+        slots follow them.  With a map (the combined case: src = gas.compact();
+        tas.compact(src)) exactly that map is applied.  A cache that follows `slots` does not
+        choose: without a map it raises ValueError.  A name that lost its slot and comes back
+        takes a fresh slot (or, with `slots`, is a skipped node until the slot owner has it
+        again).  A MetricsExtender over this cache takes the new slots through
+        snapshot_changed, as after a reshape."""
+        if src_node is None:
+            if self.slots is not None:
+                raise ValueError("compact: the slot owner decides (pass its map)")
+            listed = {n for mp in self.data.values() if mp for n in mp}
+            src = [i for i, n in enumerate(self.node_names) if n is not None and n in listed]
+            src += [-1] * int(spare_nodes)
+        else:
+            # (a slot the owner added since this cache's last flush holds no metric yet)
+            n_old = len(self.node_names)
+            src = [int(s) if s < n_old else -1 for s in src_node]
+        self.ctx.tas_snapshot_compact(self.gen, self.gen + 1, src)
+        self.gen += 1
+        self.node_names = [self.node_names[s] if s >= 0 else None for s in src]
+        self.node_index = {n: i for i, n in enumerate(self.node_names) if n is not None}
+        if self.slots is not None:
+            for mp in self.data.values():
+                self._note_skipped(mp or {})
+        return src
 
     # ------------------------------------------------------------ host side
     def _register(self, name: str):
