@@ -409,6 +409,80 @@ int pas_tas_violations_device(pas_ctx* ctx, uint64_t gen, int32_t n_strategies,
                               const int32_t* d_rule_off, uint64_t* d_viol_out,
                               void* hip_stream);
 
+/* The resident policy table: the TASPolicy objects the reference keeps in its cache
+ * (WritePolicy / ReadPolicy / DeletePolicy, cache/types.go:11-22) and keeps current through
+ * the controller's onAdd / onUpdate / onDelete (controller/controller.go:61-176).  Its verbs
+ * read a pod's policy on every request (getPolicyFromPod, telemetryscheduler.go:103-112); here
+ * a pod or a request names a row of the table, its policy id.
+ *   rules, rule_off   CSR of the policies' dontschedule rules: policy i owns
+ *                     rules[rule_off[i] .. rule_off[i + 1])
+ *   prio              [n_policies] scheduleonmetric Rules[0]; metric < 0 = none, as in
+ *                     pas_tas_eval
+ * All host arrays (the table is a few KB).  The call replaces any earlier table; n_policies = 0
+ * is a valid table.  Metric indices are columns of the resident TAS snapshot: PAS_ENOSNAP
+ * without one.  An unknown operator is accepted here: the reference panics only where the rule
+ * is evaluated (operator.go:25), and so do the verbs below.  Synchronous on the context's
+ * stream; order it after policy verbs that still run on other streams, as a snapshot change.
+ *
+ * The table against the snapshot.  Column numbering: pas_tas_snapshot_set[_device],
+ * pas_tas_snapshot_reshape (unless it moves the generation only) and pas_tas_snapshot_drop can
+ * renumber or re-create columns; a policy verb called with a table set before such a call
+ * returns PAS_ESTALE (its message names the policy table; a generation mismatch names the
+ * generation): resolve the metric names again and set the table again.  Values:
+ * pas_tas_snapshot_update[_wide][_device], pas_tas_snapshot_set_scale and
+ * pas_tas_snapshot_compact keep the table valid.
+ *
+ * Derived: the policies' violating sets, viol [n_policies][W64] (dontschedule.Violated,
+ * dontschedule/strategy.go:25-44, depends only on the rules and the metric cache).  The first
+ * policy verb after the snapshot's content or the table changed builds them with the
+ * deschedule sweep on its own stream; later verbs read them, verbs on other streams ordered
+ * after the build by an event, never by the host.  pas_tas_policies_info: PAS_EINVAL without a
+ * table.  pas_tas_policies_drop forgets the table (its storage is kept): the policy verbs
+ * answer PAS_EINVAL until the next set. */
+int pas_tas_policies_set(pas_ctx* ctx, int32_t n_policies, const pas_rule* rules,
+                         const int32_t* rule_off, const pas_rule* prio);
+int pas_tas_policies_info(const pas_ctx* ctx, int32_t* n_policies, int32_t* n_rules);
+int pas_tas_policies_drop(pas_ctx* ctx);
+
+/* The cached violating sets viol_out [n_policies][W64] (built if needed): what
+ * pas_tas_violations answers for the table's rules.  A binding can answer single filter
+ * requests from them in host memory between two refreshes.  The operators are not validated
+ * (an unknown one is skipped, as in pas_tas_violations_device). */
+int pas_tas_policies_violated(pas_ctx* ctx, uint64_t gen, uint64_t* viol_out);
+int pas_tas_policies_violated_device(pas_ctx* ctx, uint64_t gen, uint64_t* d_viol_out,
+                                     void* hip_stream);
+
+/* pas_tas_eval[_device] by policy id: exactly its outputs (pass_out, order_out, order_len; the
+ * flags, cand and the candidate rule as there) with pod p's rules and prio being table row
+ * pod_policy[p].  -1 = no dontschedule rules and no prio rule: pass = cand, empty list.  With
+ * PAS_TAS_FILTER alone the call is one pass over the bitmaps (pass = cand AND NOT viol[id]);
+ * with PAS_TAS_PRIORITIZE alone the bitmaps are not consulted.  The host form returns
+ * PAS_EINVAL for an id outside [-1, n_policies) and, as pas_tas_eval, for an unknown operator
+ * on a cached non-empty column in a policy the batch references (a policy no pod names does not
+ * fail the call); the device form reads an id outside the range as -1 and skips unknown
+ * operators. */
+int pas_tas_eval_policies(pas_ctx* ctx, uint64_t gen, int32_t n_pods, const int32_t* pod_policy,
+                          const uint64_t* cand, uint32_t flags, uint64_t* pass_out,
+                          int32_t* order_out, int32_t* order_len);
+int pas_tas_eval_policies_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods,
+                                 const int32_t* d_pod_policy, const uint64_t* d_cand,
+                                 uint32_t flags, uint64_t* d_pass_out, int32_t* d_order_out,
+                                 int32_t* d_order_len, void* hip_stream);
+
+/* pas_tas_filter_requests[_device] by policy id: its contract (row pitch, tail bits, unknown
+ * nodes pass, a repeated node keeps its verdict) with request r's rules being table row
+ * req_policy[r].  req_policy [R] is a host array in both forms, as req_off; ids are handled as
+ * in pas_tas_eval_policies (host form PAS_EINVAL, device form -1).  Prioritize in request terms
+ * needs no verb of its own: pas_tas_prioritize_requests takes a host prio [R]. */
+int pas_tas_filter_requests_policies(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                     const int32_t* req_off, const int32_t* req_policy,
+                                     const int32_t* req_node, uint64_t* pass_out,
+                                     int64_t ld_words);
+int pas_tas_filter_requests_policies_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                            const int32_t* req_off, const int32_t* req_policy,
+                                            const int32_t* d_req_node, uint64_t* d_pass_out,
+                                            int64_t ld_words, void* hip_stream);
+
 /* Deschedule label plan (Deschedule.updateNodeLabels, deschedule/enforce.go:99-151) for
  * n_strategies <= 64 strategies from a sweep's viol[s][W64(n_nodes)] and the nodes' labels.
  * The reference keys its non-violated set by policy NAME (allPolicies, :89-95), and two

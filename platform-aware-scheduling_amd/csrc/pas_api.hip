@@ -275,6 +275,9 @@ void pas_destroy(pas_ctx* ctx) {
   free_gas(ctx);
   if (ctx->tas.t_sync.ev) (void)hipEventDestroy(ctx->tas.t_sync.ev);
   if (ctx->gas.derived_sync.ev) (void)hipEventDestroy(ctx->gas.derived_sync.ev);
+  if (ctx->policies.dev) (void)hipFree(ctx->policies.dev);
+  if (ctx->policies.viol) (void)hipFree(ctx->policies.viol);
+  if (ctx->policies.viol_sync.ev) (void)hipEventDestroy(ctx->policies.viol_sync.ev);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->gas_sync_fault) (void)hipHostFree(ctx->gas_sync_fault);
   if (ctx->place_host) (void)hipHostFree(ctx->place_host);
@@ -345,6 +348,7 @@ int pas_tas_snapshot_set(pas_ctx* ctx, uint64_t gen, int32_t n_nodes, int32_t n_
   st.in(d_v, v_milli, (size_t)n_nodes * (size_t)n_metrics);
   st.in(d_p, present, (size_t)w64(n_nodes) * (size_t)n_metrics);
   if ((rc = st.upload())) return rc;
+  ++ctx->tas_col_epoch;
   rc = tas_snapshot_build(ctx, gen, n_nodes, n_metrics, d_v, d_p, ctx->stream);
   if (rc) return rc;
   PAS_HIP(ctx, st.fetch());
@@ -358,6 +362,7 @@ int pas_tas_snapshot_set_device(pas_ctx* ctx, uint64_t gen, int32_t n_nodes, int
   if (n_nodes < 0 || n_metrics < 0) return set_error(ctx, PAS_EINVAL, "bad snapshot shape");
   int rc = activate(ctx);
   if (rc) return rc;
+  ++ctx->tas_col_epoch;
   return tas_snapshot_build(ctx, gen, n_nodes, n_metrics, d_v_milli, d_present,
                             pick_stream(ctx, hip_stream));
 }
@@ -463,6 +468,7 @@ int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_
 int pas_tas_snapshot_drop(pas_ctx* ctx) {
   if (!ctx) return PAS_EINVAL;
   ctx->tas.valid = false;
+  ++ctx->tas_col_epoch;
   return PAS_OK;
 }
 
@@ -526,6 +532,7 @@ int pas_tas_snapshot_set_scale(pas_ctx* ctx, uint64_t gen, int32_t n_metrics,
         tab[2 * (size_t)m + 1] = ctx->tas.scale_host[2 * (size_t)m + 1];
       }
   ctx->tas.scale_host = tab;
+  ctx->policies.viol_built = false;  // the generation stays: the policy bitmaps go by hand
   if ((rc = activate(ctx))) return rc;
   hipStream_t s = pick_stream(ctx, hip_stream);
   // (into the resident table, not scratch: no Staging)
@@ -569,6 +576,7 @@ int pas_tas_snapshot_reshape(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
     return PAS_OK;
   }
   if ((rc = activate(ctx))) return rc;
+  ++ctx->tas_col_epoch;
   return tas_snapshot_reshape(ctx, gen_to, n_nodes_new, n_metrics_new, src.data(),
                               pick_stream(ctx, hip_stream));
 }
@@ -1005,6 +1013,272 @@ int pas_tas_violations_device(pas_ctx* ctx, uint64_t gen, int32_t n_strategies,
   if ((rc = activate(ctx))) return rc;
   return tas_violations_launch(ctx, n_strategies, n_rules, d_rules, d_rule_off, d_viol_out,
                                pick_stream(ctx, hip_stream));
+}
+
+// ------------------------------------------------------------ the resident policy table
+
+int pas_tas_policies_set(pas_ctx* ctx, int32_t n_policies, const pas_rule* rules,
+                         const int32_t* rule_off, const pas_rule* prio) {
+  const std::string fn = "pas_tas_policies_set";
+  if (!ctx) return PAS_EINVAL;
+  if (!ctx->tas.valid)  // the metric indices are the resident snapshot's columns
+    return set_error(ctx, PAS_ENOSNAP, fn + ": no TAS snapshot");
+  if (n_policies < 0 || (n_policies > 0 && (!rule_off || !prio)))
+    return set_error(ctx, PAS_EINVAL, fn + ": negative count or null rule_off/prio");
+  static const int32_t no_off[1] = {0};
+  if (n_policies == 0) rule_off = no_off;
+  int rc = validate_csr(ctx, n_policies, rule_off, "rule_off");
+  if (rc) return rc;
+  const int32_t n_rules = rule_off[n_policies];
+  if (n_rules > 0 && !rules) return set_error(ctx, PAS_EINVAL, fn + ": null rules");
+  if ((rc = activate(ctx))) return rc;
+  TasPolicies& pt = ctx->policies;
+  const size_t P = (size_t)n_policies, R = (size_t)n_rules;
+  const size_t b_rules = sizeof(pas_rule) * R, b_off = sizeof(int32_t) * (P + 1),
+               b_prio = sizeof(pas_rule) * P;
+  const size_t need = carve_size({b_rules, b_off, b_prio});
+  pt.valid = false;
+  // (the caller orders a table change after the verbs that read the table on other streams,
+  // as a snapshot change)
+  PAS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (need > pt.dev_bytes) {
+    if (pt.dev) {
+      PAS_HIP(ctx, hipDeviceSynchronize());
+      PAS_HIP(ctx, hipFree(pt.dev));
+      pt.dev = nullptr;
+      pt.dev_bytes = 0;
+    }
+    PAS_HIP(ctx, hipMalloc(&pt.dev, need));
+    pt.dev_bytes = need;
+  }
+  pt.rules.assign(rules, rules + R);
+  pt.rule_off.assign(rule_off, rule_off + P + 1);
+  pt.prio.assign(prio, prio + P);
+  Carve cv{static_cast<char*>(pt.dev)};
+  pt.d_rules = cv.take<pas_rule>(R);
+  pt.d_rule_off = cv.take<int32_t>(P + 1);
+  pt.d_prio = cv.take<pas_rule>(P);
+  hipStream_t s = ctx->stream;
+  if (b_rules)
+    PAS_HIP(ctx, hipMemcpyAsync(pt.d_rules, pt.rules.data(), b_rules, hipMemcpyHostToDevice, s));
+  PAS_HIP(ctx, hipMemcpyAsync(pt.d_rule_off, pt.rule_off.data(), b_off, hipMemcpyHostToDevice, s));
+  if (b_prio)
+    PAS_HIP(ctx, hipMemcpyAsync(pt.d_prio, pt.prio.data(), b_prio, hipMemcpyHostToDevice, s));
+  PAS_HIP(ctx, hipStreamSynchronize(s));  // verbs on any stream may read the table from here on
+  pt.n_policies = n_policies;
+  pt.n_rules = n_rules;
+  pt.col_epoch = ctx->tas_col_epoch;
+  ++pt.serial;
+  pt.valid = true;
+  return PAS_OK;
+}
+
+int pas_tas_policies_info(const pas_ctx* ctx, int32_t* n_policies, int32_t* n_rules) {
+  if (!ctx) return PAS_EINVAL;
+  if (!ctx->policies.valid) return PAS_EINVAL;
+  if (n_policies) *n_policies = ctx->policies.n_policies;
+  if (n_rules) *n_rules = ctx->policies.n_rules;
+  return PAS_OK;
+}
+
+int pas_tas_policies_drop(pas_ctx* ctx) {
+  if (!ctx) return PAS_EINVAL;
+  ctx->policies.valid = false;  // (the storage is kept for the next table)
+  ctx->policies.viol_built = false;
+  return PAS_OK;
+}
+
+// A policy verb's preconditions: the snapshot at gen, a table, and the table not older than
+// the snapshot's column numbering.
+static int check_policies(pas_ctx* ctx, uint64_t gen, const char* fn) {
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  if (!ctx->policies.valid)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": no policy table (pas_tas_policies_set)");
+  if (ctx->policies.col_epoch != ctx->tas_col_epoch)
+    return set_error(ctx, PAS_ESTALE,
+                     std::string(fn) + ": the policy table predates a column change of the TAS "
+                                       "snapshot (set, reshape or drop): set the table again");
+  return PAS_OK;
+}
+
+// ids [n] within [-1, n_policies); seen (when given): the policies the ids reference.
+static int check_policy_ids(pas_ctx* ctx, int32_t n, const int32_t* ids, const char* fn,
+                            std::vector<char>* seen) {
+  const int32_t np = ctx->policies.n_policies;
+  if (seen) seen->assign((size_t)np, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    if (ids[i] < -1 || ids[i] >= np)
+      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": policy id " +
+                                            std::to_string(ids[i]) + " at " + std::to_string(i) +
+                                            " outside [-1, n_policies)");
+    if (seen && ids[i] >= 0) (*seen)[(size_t)ids[i]] = 1;
+  }
+  return PAS_OK;
+}
+
+// validate_rules' test (the reference panics where EvaluateRule meets an unknown operator) on
+// the rules of the referenced policies only: a policy no pod names is never read.
+static int validate_policies(pas_ctx* ctx, const std::vector<char>& seen) {
+  const TasPolicies& pt = ctx->policies;
+  for (int32_t i = 0; i < pt.n_policies; ++i) {
+    if (!seen[(size_t)i]) continue;
+    const int32_t a = pt.rule_off[(size_t)i], b = pt.rule_off[(size_t)i + 1];
+    if (int rc = validate_rules(ctx, b - a, pt.rules.data() + a)) {
+      ctx->err = "policy " + std::to_string(i) + ", " + ctx->err;
+      return rc;
+    }
+  }
+  return PAS_OK;
+}
+
+int pas_tas_policies_violated(pas_ctx* ctx, uint64_t gen, uint64_t* viol_out) {
+  const char* fn = "pas_tas_policies_violated";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_policies(ctx, gen, fn);
+  if (rc) return rc;
+  const size_t words = (size_t)ctx->policies.n_policies * (size_t)w64(ctx->tas.n_nodes);
+  if (words == 0) return PAS_OK;
+  if (!viol_out) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null viol_out");
+  if ((rc = activate(ctx))) return rc;
+  hipStream_t s = ctx->stream;
+  const uint64_t* viol = nullptr;
+  if ((rc = policies_viol(ctx, s, &viol))) return rc;
+  // (out of the resident bitmaps, not scratch: no Staging)
+  PAS_HIP(ctx, hipMemcpyAsync(viol_out, viol, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  return PAS_OK;
+}
+
+int pas_tas_policies_violated_device(pas_ctx* ctx, uint64_t gen, uint64_t* d_viol_out,
+                                     void* hip_stream) {
+  const char* fn = "pas_tas_policies_violated_device";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_policies(ctx, gen, fn);
+  if (rc) return rc;
+  const size_t words = (size_t)ctx->policies.n_policies * (size_t)w64(ctx->tas.n_nodes);
+  if (words == 0) return PAS_OK;
+  if (!d_viol_out) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null viol_out");
+  if ((rc = activate(ctx))) return rc;
+  hipStream_t s = pick_stream(ctx, hip_stream);
+  const uint64_t* viol = nullptr;
+  if ((rc = policies_viol(ctx, s, &viol))) return rc;
+  PAS_HIP(ctx, hipMemcpyAsync(d_viol_out, viol, sizeof(uint64_t) * words,
+                              hipMemcpyDeviceToDevice, s));
+  return PAS_OK;
+}
+
+int pas_tas_eval_policies(pas_ctx* ctx, uint64_t gen, int32_t n_pods, const int32_t* pod_policy,
+                          const uint64_t* cand, uint32_t flags, uint64_t* pass_out,
+                          int32_t* order_out, int32_t* order_len) {
+  const std::string fn = "pas_tas_eval_policies";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_policies(ctx, gen, fn.c_str());
+  if (rc) return rc;
+  if (n_pods < 0 || (n_pods > 0 && !pod_policy))
+    return set_error(ctx, PAS_EINVAL, fn + ": negative count or null pod_policy");
+  if ((flags & PAS_TAS_FILTER) && n_pods > 0 && !pass_out)
+    return set_error(ctx, PAS_EINVAL, fn + ": FILTER without pass_out");
+  if ((flags & PAS_TAS_PRIORITIZE) && n_pods > 0 && (!order_out || !order_len))
+    return set_error(ctx, PAS_EINVAL, fn + ": PRIORITIZE without order outputs");
+  if (n_pods == 0) return PAS_OK;
+  std::vector<char> seen;
+  if ((rc = check_policy_ids(ctx, n_pods, pod_policy, fn.c_str(), &seen))) return rc;
+  if ((rc = validate_policies(ctx, seen))) return rc;
+  if ((rc = activate(ctx))) return rc;
+  const size_t P = (size_t)n_pods, N = (size_t)ctx->tas.n_nodes, W = (size_t)w64(N);
+  const bool filter = flags & PAS_TAS_FILTER, order = flags & PAS_TAS_PRIORITIZE;
+  Staging st(ctx);
+  int32_t *d_pol, *d_order, *d_len;
+  uint64_t *d_cand, *d_pass;
+  st.in(d_pol, pod_policy, P);
+  st.in_opt(d_cand, cand, W * P);
+  st.out_opt(d_pass, filter ? pass_out : nullptr, W * P);
+  st.out(d_len, order ? order_len : nullptr, P);
+  st.out_opt(d_order, order ? order_out : nullptr, N * P);
+  if ((rc = st.upload())) return rc;
+  rc = policy_eval_launch(ctx, n_pods, d_pol, d_cand, flags, d_pass, d_order, d_len,
+                          ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+int pas_tas_eval_policies_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods,
+                                 const int32_t* d_pod_policy, const uint64_t* d_cand,
+                                 uint32_t flags, uint64_t* d_pass_out, int32_t* d_order_out,
+                                 int32_t* d_order_len, void* hip_stream) {
+  const std::string fn = "pas_tas_eval_policies_device";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_policies(ctx, gen, fn.c_str());
+  if (rc) return rc;
+  if (n_pods < 0) return set_error(ctx, PAS_EINVAL, fn + ": negative count");
+  if (n_pods == 0) return PAS_OK;
+  if (!d_pod_policy) return set_error(ctx, PAS_EINVAL, fn + ": null pod_policy");
+  if ((flags & PAS_TAS_FILTER) && !d_pass_out)
+    return set_error(ctx, PAS_EINVAL, fn + ": FILTER without pass_out");
+  if ((flags & PAS_TAS_PRIORITIZE) && (!d_order_out || !d_order_len))
+    return set_error(ctx, PAS_EINVAL, fn + ": PRIORITIZE without outputs");
+  if ((rc = activate(ctx))) return rc;
+  return policy_eval_launch(ctx, n_pods, d_pod_policy, d_cand, flags, d_pass_out, d_order_out,
+                            d_order_len, pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_filter_requests_policies(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                     const int32_t* req_off, const int32_t* req_policy,
+                                     const int32_t* req_node, uint64_t* pass_out,
+                                     int64_t ld_words) {
+  const char* fn = "pas_tas_filter_requests_policies";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_policies(ctx, gen, fn);
+  if (rc) return rc;
+  int32_t longest = 0;
+  if ((rc = check_requests(ctx, n_requests, req_off, req_node, fn, &longest))) return rc;
+  if (n_requests == 0) return PAS_OK;
+  if ((rc = check_request_rows(ctx, longest, pass_out, ld_words, fn))) return rc;
+  if (!req_policy) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null req_policy");
+  std::vector<char> seen;
+  if ((rc = check_policy_ids(ctx, n_requests, req_policy, fn, &seen))) return rc;
+  // (before the empty-list return: Violated runs before filterNodes looks at the node list)
+  if ((rc = validate_policies(ctx, seen))) return rc;
+  if (longest == 0) return PAS_OK;
+  if ((rc = activate(ctx))) return rc;
+  const int32_t T = req_off[n_requests];
+  const int64_t ld_dev = w64(longest);
+  std::vector<uint64_t> rows((size_t)(n_requests * ld_dev));
+  Staging st(ctx);
+  int32_t* d_req;
+  uint64_t* d_rows;
+  st.in(d_req, req_node, (size_t)T);
+  st.out(d_rows, rows.data(), rows.size());
+  if ((rc = st.upload())) return rc;
+  hipStream_t s = ctx->stream;
+  HostStage stage;  // (req_off / req_policy are the caller's until the fetch has synchronized)
+  if ((rc = filter_requests_policy_launch(ctx, n_requests, req_off, req_policy, d_req, d_rows,
+                                          ld_dev, &stage, s))) {
+    (void)hipStreamSynchronize(s);  // the copies of the host arrays may be in flight
+    return rc;
+  }
+  return fetch_request_rows(ctx, st, n_requests, req_off, rows, ld_dev, pass_out, ld_words);
+}
+
+int pas_tas_filter_requests_policies_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
+                                            const int32_t* req_off, const int32_t* req_policy,
+                                            const int32_t* d_req_node, uint64_t* d_pass_out,
+                                            int64_t ld_words, void* hip_stream) {
+  const char* fn = "pas_tas_filter_requests_policies_device";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_policies(ctx, gen, fn);
+  if (rc) return rc;
+  int32_t longest = 0;
+  if ((rc = check_requests(ctx, n_requests, req_off, d_req_node, fn, &longest))) return rc;
+  if (n_requests == 0) return PAS_OK;
+  if ((rc = check_request_rows(ctx, longest, d_pass_out, ld_words, fn))) return rc;
+  if (!req_policy) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null req_policy");
+  if ((rc = activate(ctx))) return rc;
+  return filter_requests_policy_launch(ctx, n_requests, req_off, req_policy, d_req_node,
+                                       d_pass_out, ld_words, nullptr,
+                                       pick_stream(ctx, hip_stream));
 }
 
 // --------------------------------------------------------------------------- GAS

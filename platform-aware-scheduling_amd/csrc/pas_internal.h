@@ -191,6 +191,39 @@ struct GasSnapshot {
   DerivedSync derived_sync;  // the derived values' build
 };
 
+// The resident TASPolicy table (pas_tas_policies_set, tas_policy.hip): the policies' rules as
+// the reference's cache holds the TASPolicy objects (cache.ReadPolicy), on the host (the host
+// forms' validation, pas_tas_policies_info) and on the device (one allocation: rules |
+// rule_off | prio).  `col_epoch` is the context's column epoch at the set: a later change of
+// the snapshot's column numbering makes the table stale.  `serial` counts the sets.
+// Derived: viol [n_policies][W64], the policies' dontschedule violating sets
+// (dontschedule/strategy.go:25-44 depends on the rules and the metric cache only), built by
+// the first policy verb after the snapshot's content or the table changed, on that verb's
+// stream; later verbs on other streams wait for viol_sync's event.  The table lives beside
+// the snapshot struct, not in it: reshape and compact build a new struct and swap it in.
+struct TasPolicies {
+  bool valid = false;
+  int32_t n_policies = 0;
+  int32_t n_rules = 0;
+  uint64_t serial = 0;
+  uint64_t col_epoch = 0;
+  std::vector<pas_rule> rules;     // [n_rules]
+  std::vector<int32_t> rule_off;   // [n_policies + 1]
+  std::vector<pas_rule> prio;      // [n_policies]
+  void* dev = nullptr;
+  size_t dev_bytes = 0;
+  pas_rule* d_rules = nullptr;
+  int32_t* d_rule_off = nullptr;
+  pas_rule* d_prio = nullptr;
+  uint64_t* viol = nullptr;
+  size_t viol_bytes = 0;
+  bool viol_built = false;  // viol holds the sets of (viol_epoch, viol_gen, viol_serial)
+  uint64_t viol_epoch = 0;  // TasSnapshot::epoch
+  uint64_t viol_gen = 0;
+  uint64_t viol_serial = 0;
+  DerivedSync viol_sync;
+};
+
 // slot_buf buffers
 enum SlotBuf {
   kBufGpass = 0,  // pass bitmaps of clusters past the LDS bitmap (tas_eval)
@@ -201,7 +234,10 @@ enum SlotBuf {
   // buffer for pod events and node updates, since two calls on one slot are ordered (stream
   // order, or the slot's event), so a batch never finds the other's storage still in use
   kBufRuns = 4,
-  kSlotBufs = 5
+  // per-pod prio rules and the all-zero rule offsets of an evaluation by policy id, or the
+  // request offsets and policy ids of a request filter by policy id (tas_policy.hip)
+  kBufPolicy = 5,
+  kSlotBufs = 6
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -274,6 +310,10 @@ struct pas_ctx {
   std::string err;
   pas::TasSnapshot tas;
   pas::GasSnapshot gas;
+  pas::TasPolicies policies;
+  // counts the calls that can renumber or re-create the TAS snapshot's metric columns
+  // (snapshot_set, reshape, drop): a policy table set at an older value is stale
+  uint64_t tas_col_epoch = 1;
   // per-call scratch of the host-buffer entry points, which all run on ctx->stream and
   // synchronize it before they return (grown on demand; the _device entry points use the
   // per-stream AuxSlot buffers instead)
@@ -411,6 +451,21 @@ int gas_fit_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req
 int tas_violations_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,
                           const pas_rule* d_rules, const int32_t* d_rule_off, uint64_t* d_viol,
                           hipStream_t s);
+// The verbs by policy id (tas_policy.hip) over the resident table ctx->policies (valid and
+// current: the caller has checked).  policies_viol: the table's violation bitmaps, built on s
+// if the snapshot or the table changed since the last build, else s ordered after that build.
+int policies_viol(pas_ctx* ctx, hipStream_t s, const uint64_t** d_viol);
+// pas_tas_eval_policies on device arrays (d_pod_policy [n_pods], an id outside
+// [0, n_policies) read as -1), enqueued on s.
+int policy_eval_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy,
+                       const uint64_t* d_cand, uint32_t flags, uint64_t* d_pass,
+                       int32_t* d_order, int32_t* d_len, hipStream_t s);
+// pas_tas_filter_requests_policies: req_off [R + 1] and req_policy [R] are host arrays, stage
+// as for filter_requests_launch.
+int filter_requests_policy_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
+                                  const int32_t* req_policy, const int32_t* d_req,
+                                  uint64_t* d_pass, int64_t ld_words, HostStage* stage,
+                                  hipStream_t s);
 // A GAS fit whose side-stream wait timed out (device flags) reports here: after the fit's
 // stream was synchronized, PAS_EDEVICE (and the side streams drained) if a wait gave up since
 // the last report, else PAS_OK.

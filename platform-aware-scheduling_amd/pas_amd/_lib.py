@@ -158,6 +158,18 @@ SIGNATURES = {
     ),
     "pas_tas_violations": (c_int, [_P, c_uint64, c_int32, _P, _P, _P]),
     "pas_tas_violations_device": (c_int, [_P, c_uint64, c_int32, c_int32, _P, _P, _P, _P]),
+    "pas_tas_policies_set": (c_int, [_P, c_int32, _P, _P, _P]),
+    "pas_tas_policies_info": (c_int, [_P, POINTER(c_int32), POINTER(c_int32)]),
+    "pas_tas_policies_drop": (c_int, [_P]),
+    "pas_tas_policies_violated": (c_int, [_P, c_uint64, _P]),
+    "pas_tas_policies_violated_device": (c_int, [_P, c_uint64, _P, _P]),
+    "pas_tas_eval_policies": (c_int, [_P, c_uint64, c_int32, _P, _P, c_uint32, _P, _P, _P]),
+    "pas_tas_eval_policies_device": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, c_uint32, _P, _P, _P, _P]),
+    "pas_tas_filter_requests_policies": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, c_int64]),
+    "pas_tas_filter_requests_policies_device": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, c_int64, _P]),
     "pas_tas_label_plan": (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "pas_tas_label_plan_device": (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "pas_tas_deschedule_device": (c_int, [_P, c_uint64, c_int32, c_int32, _P, _P, _P, _P, _P, _P,

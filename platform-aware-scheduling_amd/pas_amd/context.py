@@ -497,6 +497,90 @@ class Context:
                                                _stream(stream))
         self._check(rc, "pas_tas_violations_device")
 
+    # -- the resident policy table (pas_tas_policies_set) and the verbs by policy id
+    def tas_policies_set(self, rules, rule_off, prio):
+        """Install the policy table: policy i owns rules[rule_off[i] : rule_off[i + 1]] as its
+        dontschedule rules and prio[i] as its scheduleonmetric rule (metric < 0: none)."""
+        rule_off = np.ascontiguousarray(rule_off, dtype=np.int32)
+        n = len(rule_off) - 1
+        rules = np.ascontiguousarray(rules, dtype=RULE_DTYPE)
+        prio = np.ascontiguousarray(prio, dtype=RULE_DTYPE)
+        assert prio.shape == (n,)
+        rc = self._l.pas_tas_policies_set(self._h, n, _ptr(rules) if rules.size else None,
+                                          _ptr(rule_off), _ptr(prio) if prio.size else None)
+        self._check(rc, "pas_tas_policies_set")
+
+    def tas_policies_info(self) -> Tuple[int, int]:
+        """(n_policies, n_rules) of the resident table."""
+        n, r = c_int32(), c_int32()
+        rc = self._l.pas_tas_policies_info(self._h, byref(n), byref(r))
+        if rc != _lib.PAS_OK:
+            raise PasError(rc, "pas_tas_policies_info: no policy table")
+        return n.value, r.value
+
+    def tas_policies_drop(self):
+        self._check(self._l.pas_tas_policies_drop(self._h), "pas_tas_policies_drop")
+
+    def tas_policies_violated(self, gen: int) -> np.ndarray:
+        """viol [n_policies][W64]: the cached violating sets of the table's policies."""
+        n, _ = self.tas_policies_info()
+        out = np.zeros((n, w64(self.n_nodes)), np.uint64)
+        rc = self._l.pas_tas_policies_violated(self._h, gen, _ptr(out) if out.size else None)
+        self._check(rc, "pas_tas_policies_violated")
+        return out
+
+    def tas_policies_violated_device(self, gen: int, viol_t, stream=None):
+        rc = self._l.pas_tas_policies_violated_device(self._h, gen, _dptr(viol_t),
+                                                      _stream(stream))
+        self._check(rc, "pas_tas_policies_violated_device")
+
+    def tas_eval_policies(self, gen: int, pod_policy, cand: Optional[np.ndarray] = None,
+                          flags: int = _lib.PAS_TAS_FILTER | _lib.PAS_TAS_PRIORITIZE):
+        """tas_eval with pod p's rules and prio taken from table row pod_policy[p] (-1: none).
+        Returns (pass, order, len) as tas_eval."""
+        pol = np.ascontiguousarray(pod_policy, dtype=np.int32).reshape(-1)
+        n_pods, n = len(pol), self.n_nodes
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+            assert cand.shape == (n_pods, w64(n))
+        pass_out = np.zeros((n_pods, w64(n)), np.uint64) if flags & _lib.PAS_TAS_FILTER else None
+        order = np.zeros((n_pods, n), np.int32) if flags & _lib.PAS_TAS_PRIORITIZE else None
+        lens = np.zeros(n_pods, np.int32) if flags & _lib.PAS_TAS_PRIORITIZE else None
+        rc = self._l.pas_tas_eval_policies(self._h, gen, n_pods, _ptr(pol), _ptr(cand), flags,
+                                           _ptr(pass_out), _ptr(order), _ptr(lens))
+        self._check(rc, "pas_tas_eval_policies")
+        return pass_out, order, lens
+
+    def tas_eval_policies_device(self, gen: int, n_pods: int, pod_policy_t, cand_t, flags: int,
+                                 pass_t, order_t, len_t, stream=None):
+        rc = self._l.pas_tas_eval_policies_device(self._h, gen, n_pods, _dptr(pod_policy_t),
+                                                  _dptr(cand_t), flags, _dptr(pass_t),
+                                                  _dptr(order_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_eval_policies_device")
+
+    def tas_filter_requests_policies(self, gen: int, req_off, req_policy, req_node,
+                                     out: Optional[np.ndarray] = None) -> np.ndarray:
+        """tas_filter_requests with request r's rules being table row req_policy[r]."""
+        req_off, req_node, r, longest = self._requests(req_off, req_node)
+        pol = np.ascontiguousarray(req_policy, dtype=np.int32)
+        assert pol.shape == (r,)
+        if out is None:
+            out = np.zeros((r, max(w64(longest), 1)), np.uint64)
+        assert out.dtype == np.uint64 and out.ndim == 2 and out.shape[0] == r
+        rc = self._l.pas_tas_filter_requests_policies(self._h, gen, r, _ptr(req_off), _ptr(pol),
+                                                      _ptr(req_node), _ptr(out), out.shape[1])
+        self._check(rc, "pas_tas_filter_requests_policies")
+        return out
+
+    def tas_filter_requests_policies_device(self, gen: int, req_off, req_policy, req_t, pass_t,
+                                            ld_words: int, stream=None):
+        req_off = np.ascontiguousarray(req_off, dtype=np.int32)
+        pol = np.ascontiguousarray(req_policy, dtype=np.int32)
+        rc = self._l.pas_tas_filter_requests_policies_device(
+            self._h, gen, len(req_off) - 1, _ptr(req_off), _ptr(pol), _dptr(req_t),
+            _dptr(pass_t), ld_words, _stream(stream))
+        self._check(rc, "pas_tas_filter_requests_policies_device")
+
     @staticmethod
     def _name_ids(names, n_strat: int):
         """int32 name ids of policy names (None: all distinct) as pas_tas_label_plan takes

@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib, wire
 from .context import Context, make_rules, parse_operator, quantity_as_int64, w64
+from .policy_cache import PolicyCache
 
 TAS_POLICY_LABEL = "telemetry-policy"  # telemetryscheduler.go: tasPolicy
 I915 = "gpu.intel.com/i915"
@@ -89,6 +90,10 @@ class MetricsExtender:
     policies: {(namespace, name): {"dontschedule": [(metric, op, target)],
                                    "scheduleonmetric": [(metric, op, target)]}}
     The context holds the TAS snapshot of generation `gen` over `node_names` x `metric_names`.
+    policies may be a PolicyCache instead (the resident policy table, fed by the controller's
+    events): the batch verbs then name each request's policy by its id
+    (pas_tas_filter_requests_policies; the prioritize rule from the cache's host copy) and no
+    rule array is built per request.  Every status and body is what the dict form answers.
     """
 
     def __init__(self, ctx: Context, gen: int, node_names: Sequence[str],
@@ -98,6 +103,7 @@ class MetricsExtender:
         self.node_index = {n: i for i, n in enumerate(node_names)}
         self.metric_index = {m: i for i, m in enumerate(metric_names)}
         self.policies = policies
+        self.policy_cache = policies if isinstance(policies, PolicyCache) else None
         self.table = wire.NodeTable(node_names)
         self.name_table = wire.NameTable(node_names)
 
@@ -115,6 +121,8 @@ class MetricsExtender:
         self.metric_index = {m: i for i, m in enumerate(metric_names) if m is not None}
         self.table = wire.NodeTable(self.node_names)
         self.name_table = wire.NameTable(self.node_names)
+        if self.policy_cache is not None:  # the table's metric indices are columns
+            self.policy_cache.snapshot_changed(gen, node_names, metric_names)
 
     # -- helpers ------------------------------------------------------------------
     def _decode(self, body: bytes):
@@ -243,14 +251,22 @@ class MetricsExtender:
             if policy is None or not rules:
                 out[b] = (404, b"null\n")
                 continue
-            pend.append((b, info, idx, spans, self._rules(rules)))
+            if self.policy_cache is not None:  # the policy's row of the resident table
+                pend.append((b, info, idx, spans, self.policy_cache.id_of(policy_ref)))
+            else:
+                pend.append((b, info, idx, spans, self._rules(rules)))
         if pend:
             req_off = _offsets(len(p[2]) for p in pend)
-            rule_off = _offsets(len(p[4]) for p in pend)
             try:
-                rows = self.ctx.tas_filter_requests(
-                    self.gen, req_off, np.concatenate([p[4] for p in pend]), rule_off,
-                    np.concatenate([p[2] for p in pend]))
+                if self.policy_cache is not None:
+                    rows = self.ctx.tas_filter_requests_policies(
+                        self.gen, req_off, [p[4] for p in pend],
+                        np.concatenate([p[2] for p in pend]))
+                else:
+                    rule_off = _offsets(len(p[4]) for p in pend)
+                    rows = self.ctx.tas_filter_requests(
+                        self.gen, req_off, np.concatenate([p[4] for p in pend]), rule_off,
+                        np.concatenate([p[2] for p in pend]))
             except _lib.PasError as e:
                 if e.code == _lib.PAS_EINVAL and "unknown operator" in str(e):
                     for p in pend:  # the first request whose own verb panics raises it
@@ -286,6 +302,11 @@ class MetricsExtender:
             if (policy is None or not prio or not prio[0][0]
                     or prio[0][0] not in self.metric_index):
                 out[b] = (status, b"[]\n")
+                continue
+            if self.policy_cache is not None:  # the table's host copy of the rule
+                rule = self.policy_cache.prio_of(self.policy_cache.id_of(policy_ref))
+                pend.append((b, info, idx, status,
+                             (int(rule["metric"]), int(rule["op"]), int(rule["target"]))))
                 continue
             pend.append((b, info, idx, status,
                          (self.metric_index[prio[0][0]], _op_code(prio[0][1]), int(prio[0][2]))))
