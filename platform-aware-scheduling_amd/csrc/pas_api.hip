@@ -185,7 +185,8 @@ void tas_free_storage(TasSnapshot& t) {
   free_ptr(reinterpret_cast<void*&>(t.present));
   free_ptr(reinterpret_cast<void*&>(t.vals_t));
   free_ptr(reinterpret_cast<void*&>(t.pres_t));
-  t.t_bytes = 0;
+  t.vals_t_bytes = 0;
+  t.pres_t_bytes = 0;
   t.t_epoch = 0;
   free_ptr(reinterpret_cast<void*&>(t.cnt));
   free_ptr(reinterpret_cast<void*&>(t.sorted));

@@ -96,7 +96,8 @@ struct TasSnapshot {
   uint64_t t_epoch = 0;
   int64_t* vals_t = nullptr;
   uint64_t* pres_t = nullptr;
-  size_t t_bytes = 0;
+  size_t vals_t_bytes = 0;  // the two allocations' sizes
+  size_t pres_t_bytes = 0;
   DerivedSync t_sync;  // the copies' build
 };
 
@@ -481,14 +482,6 @@ int tas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
                     const int32_t* d_rule_off, const pas_rule* d_prio, const uint64_t* d_cand,
                     int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
                     int32_t* d_node, int32_t* d_len, hipStream_t s);
-// The eval prep's grouping alone: pods bucketed by prioritize order row (metric x asc / desc
-// / index), desc[2 pos] = {pod, order * M + metric or -1, present count, 0},
-// desc[2 pos + 1] = {rule_off[pod], rule_off[pod + 1], 0, 0}; keys [P] scratch.  With
-// d_ranges, also every rule's range of the metric's ascending order (EvaluateRule, a3):
-// ranges[r] = {first, end} positions of the nodes the rule selects.
-int tas_group_launch(pas_ctx* ctx, int32_t n_pods, const pas_rule* d_prio,
-                     const int32_t* d_rule_off, int4* d_desc, int2* d_keys, int32_t n_rules,
-                     const pas_rule* d_rules, int2* d_ranges, hipStream_t s);
 // d_after_key / d_after_sub (wide records) / d_after_node: the pods' cursors, the lists resume
 // strictly after them (pas.h); null d_after_key = the lists from their beginning.
 int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,

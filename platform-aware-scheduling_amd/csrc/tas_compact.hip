@@ -341,10 +341,11 @@ int tas_snapshot_compact(pas_ctx* ctx, uint64_t gen, int32_t N, const int32_t* s
     nt.n_wide = t.n_wide;
   }
   // the node-major copies stay with the context: the next user finds their epoch behind and
-  // rebuilds them (into new storage when the size differs)
+  // rebuilds them (into new storage when either is too small for the new shape)
   nt.vals_t = t.vals_t;
   nt.pres_t = t.pres_t;
-  nt.t_bytes = t.t_bytes;
+  nt.vals_t_bytes = t.vals_t_bytes;
+  nt.pres_t_bytes = t.pres_t_bytes;
   nt.t_epoch = t.t_epoch;
   nt.t_sync = t.t_sync;
   nt.epoch = t.epoch + 1;

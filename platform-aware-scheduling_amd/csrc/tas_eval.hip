@@ -940,6 +940,10 @@ int env_int(const char* name, int dflt) {
 // sweeps (scripts/tas_sweep.sh); every one of them leaves the outputs unchanged (launch
 // shape, pod order across workgroups, store cache policy) — tests/test_env_knobs.py checks
 // that.  Output-changing diagnostics (PAS_EVAL_ABLATE, PAS_PREP_ABLATE) are compile-time.
+// Two more are read at every call, not once (tas_eval_launch): PAS_EVAL_GLOBAL_PASS=1 keeps
+// the pass bitmaps in global scratch at any cluster size, and PAS_EVAL_GPASS_PODS=<n>, n > 0,
+// caps the pods per launch of that global-pass path (0 or unset: 256 MiB of bitmap rows per
+// launch), so that tests reach its several-launch form at small shapes.  Outputs unchanged.
 struct TasTuning {
   int32_t waves = 4;         // waves per eval workgroup (2, 4 or 8)
   int32_t seg_per_wave = 1;  // adjacent order segments per wave per round (1 or 2)
@@ -1017,6 +1021,8 @@ int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
     eval_lds = sizeof(uint32_t) * ((size_t)kMiscWords + 4 * (size_t)kStageWords);
     const size_t row = sizeof(uint32_t) * (size_t)ep.W32p;
     chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(n_pods, (256u << 20) / row));
+    const int cap = env_int("PAS_EVAL_GPASS_PODS", 0);  // per call, as PAS_EVAL_GLOBAL_PASS
+    if (cap > 0) chunk = std::min(chunk, cap);
     gpass_bytes = row * (size_t)chunk;  // the stream's slot buffer (below)
   }
   if (n_pods == 0) return PAS_OK;
@@ -1093,19 +1099,6 @@ int tas_eval_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
   PAS_HIP(ctx, hipGetLastError());
   timing_end(ctx, s, &span);
   return PAS_OK;
-}
-
-int tas_group_launch(pas_ctx* ctx, int32_t n_pods, const pas_rule* d_prio,
-                     const int32_t* d_rule_off, int4* d_desc, int2* d_keys, int32_t n_rules,
-                     const pas_rule* d_rules, int2* d_ranges, hipStream_t s) {
-  const TasSnapshot& t = ctx->tas;
-  const int32_t M = t.n_metrics;
-  if (M > kMaxGroupMetrics)
-    return set_error(ctx, PAS_ECAPACITY, "more than 4096 metric columns");
-  // (the top-k entry points refuse a snapshot with wide columns: narrow ranges only)
-  return prep_launch(ctx, PAS_TAS_FILTER | PAS_TAS_PRIORITIZE, n_pods, d_prio, d_rule_off,
-                     n_rules, d_ranges ? n_rules : 0, d_rules, d_ranges, d_desc, d_keys, 0, false,
-                     false, s);
 }
 
 int tas_violations_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,

@@ -777,18 +777,20 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
   // node-major copies, once per snapshot change
   if (t.t_epoch != t.epoch && N > 0 && M > 0) {
     const size_t bv = sizeof(int64_t) * (size_t)N * M, bp = sizeof(uint64_t) * (size_t)N * WM;
-    if (t.t_bytes != bv + bp) {
-      if (t.vals_t) {
+    // (two allocations, each with its own size: a reshape can keep their sum and grow one)
+    if (t.vals_t_bytes < bv || t.pres_t_bytes < bp) {
+      if (t.vals_t || t.pres_t) {
         PAS_HIP(ctx, hipStreamSynchronize(s));
-        PAS_HIP(ctx, hipFree(t.vals_t));
-        PAS_HIP(ctx, hipFree(t.pres_t));
+        if (t.vals_t) PAS_HIP(ctx, hipFree(t.vals_t));
+        if (t.pres_t) PAS_HIP(ctx, hipFree(t.pres_t));
         t.vals_t = nullptr;
         t.pres_t = nullptr;
       }
-      t.t_bytes = 0;
+      t.vals_t_bytes = t.pres_t_bytes = 0;
       PAS_HIP(ctx, hipMalloc(&t.vals_t, bv));
+      t.vals_t_bytes = bv;
       PAS_HIP(ctx, hipMalloc(&t.pres_t, bp));
-      t.t_bytes = bv + bp;
+      t.pres_t_bytes = bp;
     }
     transpose_vals_kernel<<<dim3((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64)), kTpb, 0,
                             s>>>(N, M, t.vals, t.vals_t);
