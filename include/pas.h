@@ -1104,6 +1104,71 @@ int pas_tas_gas_topk_wide_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t 
                                        int32_t* d_top_node, int32_t* d_top_len,
                                        void* hip_stream);
 
+/* The top-k entry points by policy id, over the resident policy table (pas_tas_policies_set):
+ * each gives exactly the outputs of its counterpart without _policies (top_key, [top_sub,]
+ * top_node, top_len, the padding records included) called with pod p's rules and prio being
+ * table row d_pod_policy[p].  d_pod_policy is [n_pods] on the device; an id outside
+ * [0, n_policies) is read as -1: no dontschedule rules and no prio rule, i.e. the empty list
+ * (top_len 0, padding only).  A table with n_policies = 0 is valid: every id is then -1.  No
+ * access leaves its array, whatever the ids are.  Unknown operators are skipped, as in the
+ * device forms of the counterparts.
+ * A node's dontschedule verdict is one bit of the policy's cached violating set (viol
+ * [n_policies][W64], above), built by the first policy verb after the snapshot's content or
+ * the table changed, on that verb's stream, and ordered before calls on other streams by an
+ * event: the rules are not evaluated per pod, and a round of placement on an unchanged TAS
+ * snapshot costs no rule evaluation at all.  These calls neither build nor read the node-major
+ * snapshot copies the rules forms keep (8 bytes per node and metric).
+ * Checks: those of the counterpart (generations, k >= 1, node_base >= 0, node_base + n_nodes
+ * within int32, equal node counts of the TAS and GAS snapshots, null arguments: PAS_EINVAL;
+ * the 64-bit forms PAS_ENOTEXACT on a snapshot with wide columns) and those of the policy
+ * verbs (PAS_EINVAL without a table; PAS_ESTALE, the message naming the policy table, when the
+ * table was set before a call that renumbered columns).  Null d_pod_policy with n_pods > 0 is
+ * PAS_EINVAL; n_pods = 0 returns PAS_OK.  The _after forms resume as their counterparts
+ * ("Resuming a top-k list"); the TAS-only forms walk the pods' orders as the TAS + GAS forms
+ * do, without the fit. */
+int pas_tas_topk_policies_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods,
+                                 const int32_t* d_pod_policy, const uint64_t* d_cand, int32_t k,
+                                 int32_t node_base, int64_t* d_top_key, int32_t* d_top_node,
+                                 int32_t* d_top_len, void* hip_stream);
+int pas_tas_topk_policies_wide_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods,
+                                      const int32_t* d_pod_policy, const uint64_t* d_cand,
+                                      int32_t k, int32_t node_base, int64_t* d_top_key,
+                                      uint32_t* d_top_sub, int32_t* d_top_node,
+                                      int32_t* d_top_len, void* hip_stream);
+int pas_tas_gas_topk_policies_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                     int32_t n_pods, const int32_t* d_pod_policy,
+                                     const uint64_t* d_cand, int32_t max_containers,
+                                     int32_t i915_index, const int64_t* d_req,
+                                     const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                     int32_t k, int32_t node_base, int64_t* d_top_key,
+                                     int32_t* d_top_node, int32_t* d_top_len, void* hip_stream);
+int pas_tas_gas_topk_policies_wide_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                          int32_t n_pods, const int32_t* d_pod_policy,
+                                          const uint64_t* d_cand, int32_t max_containers,
+                                          int32_t i915_index, const int64_t* d_req,
+                                          const uint32_t* d_req_mask,
+                                          const int32_t* d_n_containers, int32_t k,
+                                          int32_t node_base, int64_t* d_top_key,
+                                          uint32_t* d_top_sub, int32_t* d_top_node,
+                                          int32_t* d_top_len, void* hip_stream);
+int pas_tas_gas_topk_policies_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                           int32_t n_pods, const int32_t* d_pod_policy,
+                                           const uint64_t* d_cand, int32_t max_containers,
+                                           int32_t i915_index, const int64_t* d_req,
+                                           const uint32_t* d_req_mask,
+                                           const int32_t* d_n_containers, int32_t k,
+                                           int32_t node_base, const int64_t* d_after_key,
+                                           const int32_t* d_after_node, int64_t* d_top_key,
+                                           int32_t* d_top_node, int32_t* d_top_len,
+                                           void* hip_stream);
+int pas_tas_gas_topk_policies_wide_after_device(
+    pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, int32_t n_pods,
+    const int32_t* d_pod_policy, const uint64_t* d_cand, int32_t max_containers,
+    int32_t i915_index, const int64_t* d_req, const uint32_t* d_req_mask,
+    const int32_t* d_n_containers, int32_t k, int32_t node_base, const int64_t* d_after_key,
+    const uint32_t* d_after_sub, const int32_t* d_after_node, int64_t* d_top_key,
+    uint32_t* d_top_sub, int32_t* d_top_node, int32_t* d_top_len, void* hip_stream);
+
 /* pas_topk_merge_device over wide records: keys / subs / nodes [n_shards][n_pods][k], the k
  * smallest (key, sub, node) records' nodes in order.  PAS_ECAPACITY when n_shards * k > 4096
  * (16 bytes of LDS per record). */

@@ -2465,6 +2465,127 @@ int pas_tas_gas_topk_wide_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t 
                           d_after_sub, d_after_node, hip_stream);
 }
 
+// The top-k entry points by policy id: the checks of tas_topk_api / tas_gas_topk_api (gas:
+// with the GAS snapshot) and those of the policy verbs.
+static int topk_policies_api(pas_ctx* ctx, const char* fn, bool gas, bool wide, uint64_t tas_gen,
+                             uint64_t gas_gen, int32_t n_pods, const int32_t* d_pod_policy,
+                             const uint64_t* d_cand, int32_t max_containers, int32_t i915_index,
+                             const int64_t* d_req, const uint32_t* d_req_mask,
+                             const int32_t* d_n_containers, int32_t k, int32_t node_base,
+                             int64_t* d_top_key, uint32_t* d_top_sub, int32_t* d_top_node,
+                             int32_t* d_top_len, bool after, const int64_t* d_after_key,
+                             const uint32_t* d_after_sub, const int32_t* d_after_node,
+                             void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_policies(ctx, tas_gen, fn);
+  if (rc) return rc;
+  if (gas) {
+    if ((rc = check_gas_gen(ctx, gas_gen))) return rc;
+    if (ctx->gas.n_nodes != ctx->tas.n_nodes)
+      return set_error(ctx, PAS_EINVAL,
+                       std::string(fn) + ": TAS and GAS snapshots differ in node count");
+    if (max_containers < 0 || i915_index >= ctx->gas.n_res || i915_index < -1)
+      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  }
+  if (n_pods < 0 || k < 1 || node_base < 0)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape");
+  if (!wide && (rc = check_no_wide(ctx, fn))) return rc;
+  if ((int64_t)node_base + ctx->tas.n_nodes > INT32_MAX)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": node ids past int32");
+  if (n_pods == 0) return PAS_OK;
+  if (!d_pod_policy || !d_top_key || !d_top_node || !d_top_len || (wide && !d_top_sub) ||
+      (gas && (!d_n_containers || (max_containers > 0 && (!d_req || !d_req_mask)))) ||
+      (after && (!d_after_key || !d_after_node || (wide && !d_after_sub))))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
+  if ((rc = activate(ctx))) return rc;
+  return tas_gas_topk_policies_launch(ctx, n_pods, d_pod_policy, d_cand, gas, max_containers,
+                                      i915_index, d_req, d_req_mask, d_n_containers, k,
+                                      node_base, d_top_key, wide ? d_top_sub : nullptr,
+                                      d_top_node, d_top_len, after ? d_after_key : nullptr,
+                                      wide ? d_after_sub : nullptr, d_after_node,
+                                      pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_topk_policies_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods,
+                                 const int32_t* d_pod_policy, const uint64_t* d_cand, int32_t k,
+                                 int32_t node_base, int64_t* d_top_key, int32_t* d_top_node,
+                                 int32_t* d_top_len, void* hip_stream) {
+  return topk_policies_api(ctx, "pas_tas_topk_policies_device", false, false, gen, 0, n_pods,
+                           d_pod_policy, d_cand, 0, -1, nullptr, nullptr, nullptr, k, node_base,
+                           d_top_key, nullptr, d_top_node, d_top_len, false, nullptr, nullptr,
+                           nullptr, hip_stream);
+}
+
+int pas_tas_topk_policies_wide_device(pas_ctx* ctx, uint64_t gen, int32_t n_pods,
+                                      const int32_t* d_pod_policy, const uint64_t* d_cand,
+                                      int32_t k, int32_t node_base, int64_t* d_top_key,
+                                      uint32_t* d_top_sub, int32_t* d_top_node,
+                                      int32_t* d_top_len, void* hip_stream) {
+  return topk_policies_api(ctx, "pas_tas_topk_policies_wide_device", false, true, gen, 0, n_pods,
+                           d_pod_policy, d_cand, 0, -1, nullptr, nullptr, nullptr, k, node_base,
+                           d_top_key, d_top_sub, d_top_node, d_top_len, false, nullptr, nullptr,
+                           nullptr, hip_stream);
+}
+
+int pas_tas_gas_topk_policies_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                     int32_t n_pods, const int32_t* d_pod_policy,
+                                     const uint64_t* d_cand, int32_t max_containers,
+                                     int32_t i915_index, const int64_t* d_req,
+                                     const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                     int32_t k, int32_t node_base, int64_t* d_top_key,
+                                     int32_t* d_top_node, int32_t* d_top_len, void* hip_stream) {
+  return topk_policies_api(ctx, "pas_tas_gas_topk_policies_device", true, false, tas_gen,
+                           gas_gen, n_pods, d_pod_policy, d_cand, max_containers, i915_index,
+                           d_req, d_req_mask, d_n_containers, k, node_base, d_top_key, nullptr,
+                           d_top_node, d_top_len, false, nullptr, nullptr, nullptr, hip_stream);
+}
+
+int pas_tas_gas_topk_policies_wide_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                          int32_t n_pods, const int32_t* d_pod_policy,
+                                          const uint64_t* d_cand, int32_t max_containers,
+                                          int32_t i915_index, const int64_t* d_req,
+                                          const uint32_t* d_req_mask,
+                                          const int32_t* d_n_containers, int32_t k,
+                                          int32_t node_base, int64_t* d_top_key,
+                                          uint32_t* d_top_sub, int32_t* d_top_node,
+                                          int32_t* d_top_len, void* hip_stream) {
+  return topk_policies_api(ctx, "pas_tas_gas_topk_policies_wide_device", true, true, tas_gen,
+                           gas_gen, n_pods, d_pod_policy, d_cand, max_containers, i915_index,
+                           d_req, d_req_mask, d_n_containers, k, node_base, d_top_key, d_top_sub,
+                           d_top_node, d_top_len, false, nullptr, nullptr, nullptr, hip_stream);
+}
+
+int pas_tas_gas_topk_policies_after_device(pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen,
+                                           int32_t n_pods, const int32_t* d_pod_policy,
+                                           const uint64_t* d_cand, int32_t max_containers,
+                                           int32_t i915_index, const int64_t* d_req,
+                                           const uint32_t* d_req_mask,
+                                           const int32_t* d_n_containers, int32_t k,
+                                           int32_t node_base, const int64_t* d_after_key,
+                                           const int32_t* d_after_node, int64_t* d_top_key,
+                                           int32_t* d_top_node, int32_t* d_top_len,
+                                           void* hip_stream) {
+  return topk_policies_api(ctx, "pas_tas_gas_topk_policies_after_device", true, false, tas_gen,
+                           gas_gen, n_pods, d_pod_policy, d_cand, max_containers, i915_index,
+                           d_req, d_req_mask, d_n_containers, k, node_base, d_top_key, nullptr,
+                           d_top_node, d_top_len, true, d_after_key, nullptr, d_after_node,
+                           hip_stream);
+}
+
+int pas_tas_gas_topk_policies_wide_after_device(
+    pas_ctx* ctx, uint64_t tas_gen, uint64_t gas_gen, int32_t n_pods,
+    const int32_t* d_pod_policy, const uint64_t* d_cand, int32_t max_containers,
+    int32_t i915_index, const int64_t* d_req, const uint32_t* d_req_mask,
+    const int32_t* d_n_containers, int32_t k, int32_t node_base, const int64_t* d_after_key,
+    const uint32_t* d_after_sub, const int32_t* d_after_node, int64_t* d_top_key,
+    uint32_t* d_top_sub, int32_t* d_top_node, int32_t* d_top_len, void* hip_stream) {
+  return topk_policies_api(ctx, "pas_tas_gas_topk_policies_wide_after_device", true, true,
+                           tas_gen, gas_gen, n_pods, d_pod_policy, d_cand, max_containers,
+                           i915_index, d_req, d_req_mask, d_n_containers, k, node_base,
+                           d_top_key, d_top_sub, d_top_node, d_top_len, true, d_after_key,
+                           d_after_sub, d_after_node, hip_stream);
+}
+
 static int topk_merge_api(pas_ctx* ctx, const char* fn, bool wide, int32_t n_pods, int32_t k,
                           int32_t n_shards, const int64_t* d_keys, const uint32_t* d_subs,
                           const int32_t* d_nodes, int32_t* d_out_node, int32_t* d_out_len,

@@ -461,6 +461,10 @@ int policies_viol(pas_ctx* ctx, hipStream_t s, const uint64_t** d_viol);
 int policy_eval_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy,
                        const uint64_t* d_cand, uint32_t flags, uint64_t* d_pass,
                        int32_t* d_order, int32_t* d_len, hipStream_t s);
+// The pods' prio rules gathered out of the table ({-1, 0, 0} for id -1) and n_pods + 1 zero rule
+// offsets, in buffer kBufPolicy of the acquired slot; enqueued on s.  d_off may be null.
+int policy_prio_gather(pas_ctx* ctx, AuxSlot* slot, int32_t n_pods, const int32_t* d_pod_policy,
+                       pas_rule** d_prio, int32_t** d_off, hipStream_t s);
 // pas_tas_filter_requests_policies: req_off [R + 1] and req_policy [R] are host arrays, stage
 // as for filter_requests_launch.
 int filter_requests_policy_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
@@ -492,6 +496,17 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
                         int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
                         const int64_t* d_after_key, const uint32_t* d_after_sub,
                         const int32_t* d_after_node, hipStream_t s);
+// The same walk by policy id over the resident table (valid and current: the caller has
+// checked) and its cached violating sets; fit = false: TAS only (no GAS snapshot, the GAS and
+// cursor arguments unused).  Neither builds nor reads the node-major copies.
+int tas_gas_topk_policies_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy,
+                                 const uint64_t* d_cand, bool fit, int32_t max_containers,
+                                 int32_t i915_index, const int64_t* d_req,
+                                 const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                 int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
+                                 int32_t* d_node, int32_t* d_len, const int64_t* d_after_key,
+                                 const uint32_t* d_after_sub, const int32_t* d_after_node,
+                                 hipStream_t s);
 int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
                       const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
                       int32_t* d_out_node, int64_t out_ld, int32_t* d_out_len, hipStream_t s);

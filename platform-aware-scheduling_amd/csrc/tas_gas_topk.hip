@@ -34,6 +34,12 @@
 // after the cursor are a prefix of the row whose length topk_start_kernel finds by binary
 // search (the value's tie run, then the node id within the run); the kAfter instantiations of
 // the walk begin at that position instead of 0 and are otherwise the same kernel.
+//
+// By policy id (pas_tas[_gas]_topk_policies*_device): the pod names a row of the resident
+// policy table and the dontschedule verdict of a node is one bit of the policy's cached
+// violating set (tas_policy.hip, policies_viol).  The kPolicy instantiations of the walk read
+// that bit where the rules form evaluates the pod's rules: no rule LDS, no node-major copies.
+// With kFit = false the same walk is the TAS-only top-k (no GAS snapshot).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -86,6 +92,12 @@ struct LazyTopkParams {
   const uint32_t* sorted_nano;  // [M][R] and fences [M][R/1024], [M][R/32] (the jumps' search)
   const uint32_t* f1k_nano;
   const uint32_t* f32_nano;
+  // the policy form (kPolicy instantiations only): rules / rule_off / prio are then the
+  // resident table's, indexed by policy, not by pod; pod_policy [P], an id outside
+  // [0, n_policies) read as -1; viol [n_policies][W64] the policies' violating sets
+  const int32_t* pod_policy;
+  int32_t n_policies;
+  const uint64_t* viol;
 };
 
 
@@ -346,16 +358,27 @@ constexpr int topk_waves() { return KMAX <= 8 && QW <= 3 ? (kWide ? 3 : 4) : 1; 
 // wide columns; the narrow instantiations (kWide = false) hold none of that code.
 // kAfter: the walk begins at the pod's start position, which topk_start_kernel left in
 // len_out[p] (the walk writes the list's length there at its end); nothing else differs.
-template <int KMAX, int QW, bool kWide, bool kAfter>
+// kPolicy (pas_tas[_gas]_topk_policies*_device): the pod names a row of the resident policy
+// table (tas_policy.hip).  Its prio rule and rule span are the table's, and a node's
+// dontschedule verdict is one bit of the policy's cached violating set, viol [n_policies][W64]:
+// no rule is compiled into LDS or evaluated, vals_t / pres_t are not read.  The jumps still
+// read the table's rules, through the same code.  The sweep that builds viol skips what the
+// rule loops here skip (unknown operators, metrics outside the snapshot, absent values), so
+// the lists are those of the rules form.
+// kFit = false (kPolicy only): no GAS fit, the TAS-only top-k; KMAX / QW are then unused.
+template <int KMAX, int QW, bool kWide, bool kAfter, bool kPolicy = false, bool kFit = true>
 __global__ __launch_bounds__(kTpb)
 __attribute__((amdgpu_waves_per_eu(topk_waves<KMAX, QW, kWide>())))
 void tas_gas_topk_kernel(LazyTopkParams a) {
-  // the pods' compiled rules, kStageRules per pod (pods of at most that many rules)
-  __shared__ LazyRule srule[kPodsPerBlock][kStageRules];
-  __shared__ int32_t smetric[kPodsPerBlock][kStageRules];
+  static_assert(kFit || kPolicy, "the rules form always fits");
+  // the pods' compiled rules, kStageRules per pod (pods of at most that many rules); none in
+  // the kPolicy instantiations, which reference no LDS
+  __shared__ LazyRule srule[kPolicy ? 1 : kPodsPerBlock][kPolicy ? 1 : kStageRules];
+  __shared__ int32_t smetric[kPolicy ? 1 : kPodsPerBlock][kPolicy ? 1 : kStageRules];
   // (kWide) the rules' edge value and mode (compile_rule_wide)
-  __shared__ int64_t sedge[kWide ? kPodsPerBlock : 1][kWide ? kStageRules : 1];
-  __shared__ int32_t smode[kWide ? kPodsPerBlock : 1][kWide ? kStageRules : 1];
+  constexpr bool kEdgeLds = kWide && !kPolicy;
+  __shared__ int64_t sedge[kEdgeLds ? kPodsPerBlock : 1][kEdgeLds ? kStageRules : 1];
+  __shared__ int32_t smode[kEdgeLds ? kPodsPerBlock : 1][kEdgeLds ? kStageRules : 1];
   const int lane = threadIdx.x & 63;
   const int half = lane / kPodLanes, sub = lane % kPodLanes;
   // XCD-aware: blocks b and b + 8 share an XCD; each XCD takes a contiguous run of the
@@ -372,8 +395,17 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
   // eval prep does, was measured slower here: the one-block grouping of 64k pods costs more
   // than the L2 locality gains)
   int4 d0 = make_int4(0, -1, 0, 0), d1 = make_int4(0, 0, 0, 0);
-  if (have) {
-    const pas_rule q = a.prio[pos];
+  // (kPolicy) the pod's policy, -1 = none: no prio rule (the empty list) and no rules; at =
+  // the pod's row of prio and rule_off, which is the policy's there
+  int32_t pol = -1;
+  if constexpr (kPolicy) {
+    if (have) pol = a.pod_policy[pos];
+    if (pol < 0 || pol >= a.n_policies) pol = -1;
+    if (have) d0.x = pos;
+  }
+  const int32_t at = kPolicy ? pol : pos;
+  if (kPolicy ? pol >= 0 : have) {
+    const pas_rule q = a.prio[at];
     const int32_t cq = (q.metric >= 0 && q.metric < a.M) ? a.cnt[q.metric] : 0;
     const int oq = q.op == PAS_OP_GREATER_THAN ? kOrderDesc
                    : q.op == PAS_OP_LESS_THAN  ? kOrderAsc
@@ -381,12 +413,12 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
     d0 = make_int4(pos, cq > 0 ? oq * a.M + q.metric : -1, cq, 0);
     // (clamped into [0, n_rules] and non-decreasing: a device rule_off that is not a CSR
     // never indexes past the rules, as the eval prep's rule_span)
-    const int32_t r0 = min(max(a.rule_off[pos], 0), a.n_rules);
-    d1 = make_int4(r0, min(max(a.rule_off[pos + 1], r0), a.n_rules), 0, 0);
+    const int32_t r0 = min(max(a.rule_off[at], 0), a.n_rules);
+    d1 = make_int4(r0, min(max(a.rule_off[at + 1], r0), a.n_rules), 0, 0);
   }
   const int32_t p = d0.x;
   const int32_t k = a.k;
-  const pas_rule pr = a.prio[p];
+  const pas_rule pr = !kPolicy ? a.prio[p] : pol >= 0 ? a.prio[pol] : pas_rule{-1, 0, 0};
   // bucket -1: no scheduling rule / metric not cached / no node has it: empty list
   // (telemetryscheduler.go:92-96); d0.z = the metric's present count
   const int32_t c0 = (have && d0.y >= 0) ? d0.z : 0;
@@ -461,25 +493,27 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
   // per lane, rule and round.
   const int pslot = (int)(threadIdx.x >> 6) * kPodsPerWave + half;
   const bool staged = !__ballot(have && r1 - r0 > kStageRules);
-  if (staged) {
-    LazyRule cr{0, 0};
-    int32_t cm = -1;
-    if constexpr (kWide) {
-      int64_t ce = 0;
-      int32_t cmode = kEdgeNone;
-      if (have && r0 + sub < r1)
-        compile_rule_wide(a.rules[r0 + sub], a.M, a.scale_tab, a.wide_flag, &cm, &cr, &ce,
-                          &cmode);
-      sedge[pslot][sub] = ce;
-      smode[pslot][sub] = cmode;
-    } else {
-      if (have && r0 + sub < r1) compile_rule(a.rules[r0 + sub], a.M, a.scale_tab, &cm, &cr);
+  if constexpr (!kPolicy) {
+    if (staged) {
+      LazyRule cr{0, 0};
+      int32_t cm = -1;
+      if constexpr (kWide) {
+        int64_t ce = 0;
+        int32_t cmode = kEdgeNone;
+        if (have && r0 + sub < r1)
+          compile_rule_wide(a.rules[r0 + sub], a.M, a.scale_tab, a.wide_flag, &cm, &cr, &ce,
+                            &cmode);
+        sedge[pslot][sub] = ce;
+        smode[pslot][sub] = cmode;
+      } else {
+        if (have && r0 + sub < r1) compile_rule(a.rules[r0 + sub], a.M, a.scale_tab, &cm, &cr);
+      }
+      srule[pslot][sub] = cr;
+      smetric[pslot][sub] = cm;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
     }
-    srule[pslot][sub] = cr;
-    smetric[pslot][sub] = cm;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
   }
   const int32_t nr = have ? r1 - r0 : 0;
   const int32_t* row = a.perm + (int64_t)(d0.y >= 0 ? d0.y : 0) * a.R;
@@ -505,84 +539,93 @@ void tas_gas_topk_kernel(LazyTopkParams a) {
     // dontschedule.Violated (strategy.go:25-44) at this node: any rule whose metric the node
     // has and whose EvaluateRule holds; rules on metrics outside the cache or with an
     // unknown operator are skipped.  kRuleBatch rules' loads in flight at once.
-    const int64_t* vrow = a.vals_t + (int64_t)n * a.M;
-    const uint64_t* prow = a.pres_t + (int64_t)n * a.WM;
     bool viol = false;
-    if (staged) {
-      for (int32_t rb = 0; __ballot(ok && rb < nr); rb += kRuleBatch) {
-        int32_t m[kRuleBatch];
+    if constexpr (kPolicy) {
+      // the policy's cached verdict: one word of its violating set, by the lanes still
+      // passing (n < N: an entry of the order row below the present count)
+      if (ok && pol >= 0)
+        viol = (a.viol[(int64_t)pol * a.W64 + (n >> 6)] >> (n & 63)) & 1ull;
+    } else {
+      const int64_t* vrow = a.vals_t + (int64_t)n * a.M;
+      const uint64_t* prow = a.pres_t + (int64_t)n * a.WM;
+      if (staged) {
+        for (int32_t rb = 0; __ballot(ok && rb < nr); rb += kRuleBatch) {
+          int32_t m[kRuleBatch];
+          int64_t v[kRuleBatch];
+          uint64_t pw[kRuleBatch];
+#pragma unroll
+          for (int u = 0; u < kRuleBatch; ++u) m[u] = smetric[pslot][min(rb + u, kStageRules - 1)];
+          // (one presence word per node when the snapshot has at most 64 metrics)
+          const uint64_t pw0 = a.WM == 1 ? prow[0] : 0;
+#pragma unroll
+          for (int u = 0; u < kRuleBatch; ++u) {
+            const int32_t mm = m[u] >= 0 ? m[u] : 0;
+            v[u] = vrow[mm];
+            pw[u] = a.WM == 1 ? pw0 : prow[mm >> 6];
+          }
+#pragma unroll
+          for (int u = 0; u < kRuleBatch; ++u) {
+            const LazyRule cr = srule[pslot][min(rb + u, kStageRules - 1)];
+            bool hit = rb + u < nr && m[u] >= 0 &&
+                       (uint64_t)v[u] - (uint64_t)cr.lo <= cr.span &&
+                       ((pw[u] >> (m[u] & 63)) & 1ull);
+            if constexpr (kWide) {
+              // the range's edge on a wide column: the node's nano decides (a rare gather of
+              // the metric-major nano column, by the lanes on the edge only)
+              const int32_t md = smode[pslot][min(rb + u, kStageRules - 1)];
+              if (hit && md != kEdgeNone && v[u] == sedge[pslot][min(rb + u, kStageRules - 1)]) {
+                const uint32_t f = a.nano[(int64_t)m[u] * a.N + n];
+                hit = (f != 0u) == (md == kEdgeNanoNonZero);
+              }
+            }
+            viol = viol || hit;
+          }
+        }
+      }
+      for (int32_t rb = r0; !staged && __ballot(ok && rb < r1); rb += kRuleBatch) {
+        pas_rule ru[kRuleBatch];
         int64_t v[kRuleBatch];
         uint64_t pw[kRuleBatch];
 #pragma unroll
-        for (int u = 0; u < kRuleBatch; ++u) m[u] = smetric[pslot][min(rb + u, kStageRules - 1)];
-        // (one presence word per node when the snapshot has at most 64 metrics)
-        const uint64_t pw0 = a.WM == 1 ? prow[0] : 0;
+        for (int u = 0; u < kRuleBatch; ++u) ru[u] = a.rules[max(min(rb + u, r1 - 1), 0)];
 #pragma unroll
         for (int u = 0; u < kRuleBatch; ++u) {
-          const int32_t mm = m[u] >= 0 ? m[u] : 0;
-          v[u] = vrow[mm];
-          pw[u] = a.WM == 1 ? pw0 : prow[mm >> 6];
+          const int32_t m = (ru[u].metric >= 0 && ru[u].metric < a.M) ? ru[u].metric : 0;
+          v[u] = vrow[m];
+          pw[u] = prow[m >> 6];
         }
 #pragma unroll
         for (int u = 0; u < kRuleBatch; ++u) {
-          const LazyRule cr = srule[pslot][min(rb + u, kStageRules - 1)];
-          bool hit = rb + u < nr && m[u] >= 0 &&
-                     (uint64_t)v[u] - (uint64_t)cr.lo <= cr.span &&
-                     ((pw[u] >> (m[u] & 63)) & 1ull);
+          const pas_rule rule = ru[u];
+          if (rb + u >= r1 || rule.metric < 0 || rule.metric >= a.M || rule.op < 0 || rule.op > 2)
+            continue;
           if constexpr (kWide) {
-            // the range's edge on a wide column: the node's nano decides (a rare gather of
-            // the metric-major nano column, by the lanes on the edge only)
-            const int32_t md = smode[pslot][min(rb + u, kStageRules - 1)];
-            if (hit && md != kEdgeNone && v[u] == sedge[pslot][min(rb + u, kStageRules - 1)]) {
-              const uint32_t f = a.nano[(int64_t)m[u] * a.N + n];
-              hit = (f != 0u) == (md == kEdgeNanoNonZero);
+            if (a.wide_flag && a.wide_flag[rule.metric]) {
+              const int64_t t = rule.target;
+              uint32_t f = 0;
+              if (v[u] == t && rule.op != PAS_OP_LESS_THAN)
+                f = a.nano[(int64_t)rule.metric * a.N + n];
+              const bool wh = rule.op == PAS_OP_LESS_THAN      ? wide_below(v[u], f, t)
+                              : rule.op == PAS_OP_GREATER_THAN ? wide_above(v[u], f, t)
+                                                               : wide_equal(v[u], f, t);
+              viol = viol || (wh && ((pw[u] >> (rule.metric & 63)) & 1ull));
+              continue;
             }
           }
-          viol = viol || hit;
+          int64_t tm = 0;
+          const int sat = target_scaled(rule.target, a.scale_tab, rule.metric, &tm);
+          bool hit;
+          if (rule.op == PAS_OP_LESS_THAN) hit = sat > 0 || (sat == 0 && v[u] < tm);
+          else if (rule.op == PAS_OP_GREATER_THAN) hit = sat < 0 || (sat == 0 && v[u] > tm);
+          else hit = sat == 0 && v[u] == tm;
+          viol = viol || (hit && ((pw[u] >> (rule.metric & 63)) & 1ull));
         }
-      }
-    }
-    for (int32_t rb = r0; !staged && __ballot(ok && rb < r1); rb += kRuleBatch) {
-      pas_rule ru[kRuleBatch];
-      int64_t v[kRuleBatch];
-      uint64_t pw[kRuleBatch];
-#pragma unroll
-      for (int u = 0; u < kRuleBatch; ++u) ru[u] = a.rules[max(min(rb + u, r1 - 1), 0)];
-#pragma unroll
-      for (int u = 0; u < kRuleBatch; ++u) {
-        const int32_t m = (ru[u].metric >= 0 && ru[u].metric < a.M) ? ru[u].metric : 0;
-        v[u] = vrow[m];
-        pw[u] = prow[m >> 6];
-      }
-#pragma unroll
-      for (int u = 0; u < kRuleBatch; ++u) {
-        const pas_rule rule = ru[u];
-        if (rb + u >= r1 || rule.metric < 0 || rule.metric >= a.M || rule.op < 0 || rule.op > 2)
-          continue;
-        if constexpr (kWide) {
-          if (a.wide_flag && a.wide_flag[rule.metric]) {
-            const int64_t t = rule.target;
-            uint32_t f = 0;
-            if (v[u] == t && rule.op != PAS_OP_LESS_THAN)
-              f = a.nano[(int64_t)rule.metric * a.N + n];
-            const bool wh = rule.op == PAS_OP_LESS_THAN      ? wide_below(v[u], f, t)
-                            : rule.op == PAS_OP_GREATER_THAN ? wide_above(v[u], f, t)
-                                                             : wide_equal(v[u], f, t);
-            viol = viol || (wh && ((pw[u] >> (rule.metric & 63)) & 1ull));
-            continue;
-          }
-        }
-        int64_t tm = 0;
-        const int sat = target_scaled(rule.target, a.scale_tab, rule.metric, &tm);
-        bool hit;
-        if (rule.op == PAS_OP_LESS_THAN) hit = sat > 0 || (sat == 0 && v[u] < tm);
-        else if (rule.op == PAS_OP_GREATER_THAN) hit = sat < 0 || (sat == 0 && v[u] > tm);
-        else hit = sat == 0 && v[u] == tm;
-        viol = viol || (hit && ((pw[u] >> (rule.metric & 63)) & 1ull));
       }
     }
     ok = ok && !viol;
-    if (ok) ok = lane_fit<KMAX, QW>(a, p, n);
+    if constexpr (kFit) {
+      if (ok) ok = lane_fit<KMAX, QW>(a, p, n);
+    }
     const uint64_t keep = __ballot(ok) & half_mask;
     if (ok) {
       const int32_t rank = kept + __popcll(keep & below);
@@ -759,6 +802,136 @@ void topk_dispatch(const LazyTopkParams& a, unsigned grid, hipStream_t s) {
   }
 }
 
+// The same tiers for the policy form (kPolicy, with the fit).
+template <bool kWide, bool kAfter>
+void topk_policy_dispatch(const LazyTopkParams& a, unsigned grid, hipStream_t s) {
+  if (a.K <= 8) {
+    switch (a.Q) {
+      case 1: tas_gas_topk_kernel<8, 1, kWide, kAfter, true><<<grid, kTpb, 0, s>>>(a); break;
+      case 2: tas_gas_topk_kernel<8, 2, kWide, kAfter, true><<<grid, kTpb, 0, s>>>(a); break;
+      case 3: tas_gas_topk_kernel<8, 3, kWide, kAfter, true><<<grid, kTpb, 0, s>>>(a); break;
+      default: tas_gas_topk_kernel<8, kMaxRes, kWide, kAfter, true><<<grid, kTpb, 0, s>>>(a); break;
+    }
+  } else if (a.K <= 16) {
+    tas_gas_topk_kernel<16, kMaxRes, kWide, kAfter, true><<<grid, kTpb, 0, s>>>(a);
+  } else {
+    tas_gas_topk_kernel<PAS_GAS_MAX_CARDS, kMaxRes, kWide, kAfter, true><<<grid, kTpb, 0, s>>>(a);
+  }
+}
+
+template <bool kWide, bool kAfter, bool kPolicy>
+void topk_launch_walk(const LazyTopkParams& a, unsigned grid, hipStream_t s) {
+  if constexpr (kPolicy) topk_policy_dispatch<kWide, kAfter>(a, grid, s);
+  else topk_dispatch<kWide, kAfter>(a, grid, s);
+}
+
+// The walk's parameters that come from the TAS snapshot and the call's outputs (d_sub null =
+// the 64-bit records); the rules, the GAS side and the policy fields are the caller's to set.
+LazyTopkParams topk_params(const TasSnapshot& t, int32_t n_pods, const uint64_t* d_cand,
+                           int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
+                           int32_t* d_node, int32_t* d_len) {
+  LazyTopkParams a{};
+  a.n_pods = n_pods;
+  a.N = t.n_nodes;
+  a.M = t.n_metrics;
+  a.R = t.row;
+  a.W64 = (int32_t)w64(t.n_nodes);
+  a.k = k;
+  a.node_base = node_base;
+  a.cand = d_cand;
+  a.perm = t.perm;
+  a.cnt = t.cnt;
+  a.vals = t.vals;
+  a.WM = (t.n_metrics + 63) / 64;
+  a.sorted = t.sorted;
+  a.f1k = t.f1k;
+  a.f32 = t.f32;
+  a.scale_tab = t.scale_tab;
+  a.key_out = d_key;
+  a.node_out = d_node;
+  a.len_out = d_len;
+  a.sub_out = d_sub;
+  a.nano = t.n_wide > 0 ? t.nano : nullptr;
+  a.wide_flag = t.n_wide > 0 ? t.wide_flag : nullptr;
+  a.sorted_nano = t.sorted_nano;
+  a.f1k_nano = t.f1k_nano;
+  a.f32_nano = t.f32_nano;
+  return a;
+}
+
+void topk_gas_params(LazyTopkParams& a, const GasSnapshot& g, int32_t max_containers,
+                     int32_t i915_index, const int64_t* d_req, const uint32_t* d_req_mask,
+                     const int32_t* d_n_containers) {
+  a.K = g.max_cards;
+  a.Q = g.n_res;
+  a.C = max_containers;
+  a.i915 = i915_index;
+  a.n_cards = g.n_cards;
+  a.cap = g.cap;
+  a.used = g.used;
+  a.req = d_req;
+  a.mask = d_req_mask;
+  a.ncont = d_n_containers;
+}
+
+// The walk on s, timed as PAS_K_TAS_GAS_TOPK: from the lists' beginning, or (d_after_key)
+// resumed after the cursors, whose start positions topk_start_kernel leaves in len_out where
+// the walk reads them.  d_start_prio [P]: the pods' prio rules for the start kernel (the rules
+// form's a.prio; the policy form's gathered out of the table).  fit = false: the kFit = false
+// walk (kPolicy, not resumed).
+template <bool kPolicy>
+int topk_walk(pas_ctx* ctx, const LazyTopkParams& a, bool fit, const pas_rule* d_start_prio,
+              const int64_t* d_after_key, const uint32_t* d_after_sub,
+              const int32_t* d_after_node, hipStream_t s) {
+  const TasSnapshot& t = ctx->tas;
+  TimedLaunch tl;
+  timing_begin(ctx, s, PAS_K_TAS_GAS_TOPK, &tl);
+  const unsigned grid = (unsigned)((a.n_pods + kPodsPerBlock - 1) / kPodsPerBlock);
+  if constexpr (kPolicy) {
+    if (!fit) {
+      if (a.sub_out) tas_gas_topk_kernel<8, 1, true, false, true, false><<<grid, kTpb, 0, s>>>(a);
+      else tas_gas_topk_kernel<8, 1, false, false, true, false><<<grid, kTpb, 0, s>>>(a);
+      timing_end(ctx, s, &tl);
+      PAS_HIP(ctx, hipGetLastError());
+      return PAS_OK;
+    }
+  }
+  if (d_after_key) {
+    TopkStartParams b;
+    b.n_pods = a.n_pods;
+    b.N = a.N;
+    b.M = a.M;
+    b.R = t.row;
+    b.node_base = a.node_base;
+    b.prio = d_start_prio;
+    b.perm = t.perm;
+    b.cnt = t.cnt;
+    b.sorted = t.sorted;
+    b.sorted_nano = t.sorted_nano;
+    b.scale_tab = t.scale_tab;
+    b.wide_flag = a.wide_flag;
+    b.after_key = d_after_key;
+    b.after_sub = d_after_sub;
+    b.after_node = d_after_node;
+    b.start = a.len_out;
+    const unsigned sgrid = (unsigned)((a.n_pods + kTpb - 1) / kTpb);
+    if (a.sub_out) {
+      topk_start_kernel<true><<<sgrid, kTpb, 0, s>>>(b);
+      topk_launch_walk<true, true, kPolicy>(a, grid, s);
+    } else {
+      topk_start_kernel<false><<<sgrid, kTpb, 0, s>>>(b);
+      topk_launch_walk<false, true, kPolicy>(a, grid, s);
+    }
+  } else if (a.sub_out) {
+    topk_launch_walk<true, false, kPolicy>(a, grid, s);
+  } else {
+    topk_launch_walk<false, false, kPolicy>(a, grid, s);
+  }
+  timing_end(ctx, s, &tl);
+  PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
+}
+
 }  // namespace
 
 int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
@@ -771,7 +944,6 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
                         const int32_t* d_after_node, hipStream_t s) {
   if (n_pods == 0) return PAS_OK;
   TasSnapshot& t = ctx->tas;
-  const GasSnapshot& g = ctx->gas;
   const int32_t N = t.n_nodes, M = t.n_metrics;
   const int32_t WM = (M + 63) / 64;
   // node-major copies, once per snapshot change
@@ -802,86 +974,54 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
   } else if (int e = derived_wait(ctx, t.t_sync, s)) {
     return e;  // built by a call on another stream, maybe still running
   }
-  TimedLaunch tl;
-  timing_begin(ctx, s, PAS_K_TAS_GAS_TOPK, &tl);
-  LazyTopkParams a;
-  a.n_pods = n_pods;
-  a.N = N;
-  a.M = M;
-  a.R = t.row;
-  a.W64 = (int32_t)w64(N);
-  a.k = k;
-  a.node_base = node_base;
+  LazyTopkParams a = topk_params(t, n_pods, d_cand, k, node_base, d_key, d_sub, d_node, d_len);
   a.rules = d_rules;
   a.rule_off = d_rule_off;
   a.n_rules = std::max(n_rules, 0);
   a.prio = d_prio;
-  a.cand = d_cand;
-  a.perm = t.perm;
-  a.cnt = t.cnt;
-  a.vals = t.vals;
   a.vals_t = t.vals_t;
   a.pres_t = t.pres_t;
-  a.WM = WM;
-  a.sorted = t.sorted;
-  a.f1k = t.f1k;
-  a.f32 = t.f32;
-  a.scale_tab = t.scale_tab;
-  a.K = g.max_cards;
-  a.Q = g.n_res;
-  a.C = max_containers;
-  a.i915 = i915_index;
-  a.n_cards = g.n_cards;
-  a.cap = g.cap;
-  a.used = g.used;
-  a.req = d_req;
-  a.mask = d_req_mask;
-  a.ncont = d_n_containers;
-  a.key_out = d_key;
-  a.node_out = d_node;
-  a.len_out = d_len;
-  a.sub_out = d_sub;
-  a.nano = t.n_wide > 0 ? t.nano : nullptr;
-  a.wide_flag = t.n_wide > 0 ? t.wide_flag : nullptr;
-  a.sorted_nano = t.sorted_nano;
-  a.f1k_nano = t.f1k_nano;
-  a.f32_nano = t.f32_nano;
-  const unsigned grid = (unsigned)((n_pods + kPodsPerBlock - 1) / kPodsPerBlock);
-  if (d_after_key) {
-    // the start positions into d_len, where the walk reads them
-    TopkStartParams b;
-    b.n_pods = n_pods;
-    b.N = N;
-    b.M = M;
-    b.R = t.row;
-    b.node_base = node_base;
-    b.prio = d_prio;
-    b.perm = t.perm;
-    b.cnt = t.cnt;
-    b.sorted = t.sorted;
-    b.sorted_nano = t.sorted_nano;
-    b.scale_tab = t.scale_tab;
-    b.wide_flag = a.wide_flag;
-    b.after_key = d_after_key;
-    b.after_sub = d_after_sub;
-    b.after_node = d_after_node;
-    b.start = d_len;
-    const unsigned sgrid = (unsigned)((n_pods + kTpb - 1) / kTpb);
-    if (d_sub) {
-      topk_start_kernel<true><<<sgrid, kTpb, 0, s>>>(b);
-      topk_dispatch<true, true>(a, grid, s);
-    } else {
-      topk_start_kernel<false><<<sgrid, kTpb, 0, s>>>(b);
-      topk_dispatch<false, true>(a, grid, s);
-    }
-  } else if (d_sub) {
-    topk_dispatch<true, false>(a, grid, s);
-  } else {
-    topk_dispatch<false, false>(a, grid, s);
-  }
-  timing_end(ctx, s, &tl);
-  PAS_HIP(ctx, hipGetLastError());
-  return PAS_OK;
+  topk_gas_params(a, ctx->gas, max_containers, i915_index, d_req, d_req_mask, d_n_containers);
+  return topk_walk<false>(ctx, a, true, d_prio, d_after_key, d_after_sub, d_after_node, s);
+}
+
+// The policy form: the walk over the resident table and its cached violating sets.  Neither
+// builds nor reads the node-major copies (vals_t / pres_t): a context that only ever calls
+// this form never allocates them.
+int tas_gas_topk_policies_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy,
+                                 const uint64_t* d_cand, bool fit, int32_t max_containers,
+                                 int32_t i915_index, const int64_t* d_req,
+                                 const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                 int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
+                                 int32_t* d_node, int32_t* d_len, const int64_t* d_after_key,
+                                 const uint32_t* d_after_sub, const int32_t* d_after_node,
+                                 hipStream_t s) {
+  if (n_pods == 0) return PAS_OK;
+  const TasPolicies& pt = ctx->policies;
+  // built on s if the snapshot or the table changed, else s waits for the build's event
+  const uint64_t* viol = nullptr;
+  int rc = policies_viol(ctx, s, &viol);
+  if (rc) return rc;
+  LazyTopkParams a =
+      topk_params(ctx->tas, n_pods, d_cand, k, node_base, d_key, d_sub, d_node, d_len);
+  a.rules = pt.d_rules;
+  a.rule_off = pt.d_rule_off;
+  a.n_rules = pt.n_rules;
+  a.prio = pt.d_prio;
+  a.pod_policy = d_pod_policy;
+  a.n_policies = pt.n_policies;
+  a.viol = viol;
+  if (!fit) return topk_walk<true>(ctx, a, false, nullptr, nullptr, nullptr, nullptr, s);
+  topk_gas_params(a, ctx->gas, max_containers, i915_index, d_req, d_req_mask, d_n_containers);
+  if (!d_after_key) return topk_walk<true>(ctx, a, true, nullptr, nullptr, nullptr, nullptr, s);
+  // the start kernel takes per-pod prio rules: gathered out of the table into the stream's
+  // slot, which stays this call's until the walk is enqueued
+  SlotScope sc(ctx, s, 0, &rc);
+  if (!sc.slot) return rc;
+  pas_rule* d_prio = nullptr;
+  if ((rc = policy_prio_gather(ctx, sc.slot, n_pods, d_pod_policy, &d_prio, nullptr, s)))
+    return rc;
+  return topk_walk<true>(ctx, a, true, d_prio, d_after_key, d_after_sub, d_after_node, s);
 }
 
 }  // namespace pas

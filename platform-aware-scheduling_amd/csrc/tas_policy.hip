@@ -175,6 +175,23 @@ int policies_viol(pas_ctx* ctx, hipStream_t s, const uint64_t** d_viol) {
   return PAS_OK;
 }
 
+int policy_prio_gather(pas_ctx* ctx, AuxSlot* slot, int32_t n_pods, const int32_t* d_pod_policy,
+                       pas_rule** d_prio, int32_t** d_off, hipStream_t s) {
+  const size_t b_prio = sizeof(pas_rule) * (size_t)n_pods;
+  const size_t b_off = sizeof(int32_t) * ((size_t)n_pods + 1);
+  int rc = PAS_OK;
+  void* buf = slot_buf(ctx, slot, kBufPolicy, carve_size({b_prio, b_off}), s, &rc);
+  if (!buf) return rc;
+  Carve cv{static_cast<char*>(buf)};
+  *d_prio = cv.take<pas_rule>((size_t)n_pods);
+  int32_t* off = cv.take<int32_t>((size_t)n_pods + 1);
+  if (d_off) *d_off = off;
+  prio_gather_kernel<<<(unsigned)(n_pods / 256 + 1), 256, 0, s>>>(
+      n_pods, ctx->policies.n_policies, d_pod_policy, ctx->policies.d_prio, *d_prio, off);
+  PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
+}
+
 int policy_eval_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy,
                        const uint64_t* d_cand, uint32_t flags, uint64_t* d_pass,
                        int32_t* d_order, int32_t* d_len, hipStream_t s) {
@@ -203,18 +220,10 @@ int policy_eval_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy
   pas_rule* d_prio = nullptr;
   int32_t* d_off = nullptr;
   {
-    const size_t b_prio = sizeof(pas_rule) * (size_t)n_pods;
-    const size_t b_off = sizeof(int32_t) * ((size_t)n_pods + 1);
     SlotScope sc(ctx, s, 0, &rc);
     if (!sc.slot) return rc;
-    void* buf = slot_buf(ctx, sc.slot, kBufPolicy, carve_size({b_prio, b_off}), s, &rc);
-    if (!buf) return rc;
-    Carve cv{static_cast<char*>(buf)};
-    d_prio = cv.take<pas_rule>((size_t)n_pods);
-    d_off = cv.take<int32_t>((size_t)n_pods + 1);
-    prio_gather_kernel<<<(unsigned)(n_pods / 256 + 1), 256, 0, s>>>(
-        n_pods, pt.n_policies, d_pod_policy, pt.d_prio, d_prio, d_off);
-    PAS_HIP(ctx, hipGetLastError());
+    if ((rc = policy_prio_gather(ctx, sc.slot, n_pods, d_pod_policy, &d_prio, &d_off, s)))
+      return rc;
   }
   // pas_tas_eval's candidate rule: the lists over pass when the filter ran, else over cand
   // (then the bitmaps are not consulted at all)

@@ -291,6 +291,32 @@ SIGNATURES = {
         [_P, c_uint64, c_uint64, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P,
          c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P],
     ),
+    # the top-k entry points by policy id: the counterparts' lists with (n_rules, rules,
+    # rule_off, prio) replaced by the pod_policy pointer
+    "pas_tas_topk_policies_device": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P, _P]),
+    "pas_tas_topk_policies_wide_device": (
+        c_int, [_P, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "pas_tas_gas_topk_policies_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int32, c_int32, _P, _P, _P, _P],
+    ),
+    "pas_tas_gas_topk_policies_wide_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int32, c_int32, _P, _P, _P, _P, _P],
+    ),
+    "pas_tas_gas_topk_policies_after_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int32, c_int32, _P, _P, _P, _P, _P, _P],
+    ),
+    "pas_tas_gas_topk_policies_wide_after_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P],
+    ),
     "pas_topk_merge_wide_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
                                            _P]),
     "pas_list_merge_wide_device": (c_int, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P,

@@ -1093,3 +1093,73 @@ class Context:
                                                 _dptr(out_node_t), out_ld, _dptr(out_len_t),
                                                 _stream(stream))
         self._check(rc, "pas_list_merge_wide_device")
+
+    # ------------------------------------------------------------------ top-k by policy id
+    def tas_topk_policies_device(self, gen: int, n_pods: int, pod_policy_t, cand_t, k: int,
+                                 node_base: int, key_t, node_t, len_t, stream=None):
+        """tas_topk_device with pod p's rules and prio being row pod_policy_t[p] (int32 [P]) of
+        the resident policy table (pas_tas_topk_policies_device); -1 = the empty list."""
+        rc = self._l.pas_tas_topk_policies_device(
+            self._h, gen, n_pods, _dptr(pod_policy_t), _dptr(cand_t), k, node_base,
+            _dptr(key_t), _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_topk_policies_device")
+
+    def tas_topk_policies_wide_device(self, gen: int, n_pods: int, pod_policy_t, cand_t, k: int,
+                                      node_base: int, key_t, sub_t, node_t, len_t, stream=None):
+        """tas_topk_wide_device by policy id (pas_tas_topk_policies_wide_device)."""
+        rc = self._l.pas_tas_topk_policies_wide_device(
+            self._h, gen, n_pods, _dptr(pod_policy_t), _dptr(cand_t), k, node_base,
+            _dptr(key_t), _dptr(sub_t), _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_topk_policies_wide_device")
+
+    def tas_gas_topk_policies_device(self, tas_gen: int, gas_gen: int, n_pods: int, pod_policy_t,
+                                     cand_t, max_containers: int, i915_index: int, req_t, mask_t,
+                                     ncont_t, k: int, node_base: int, key_t, node_t, len_t,
+                                     stream=None):
+        """tas_gas_topk_device by policy id (pas_tas_gas_topk_policies_device): a node's
+        dontschedule verdict is one bit of the policy's cached violating set."""
+        rc = self._l.pas_tas_gas_topk_policies_device(
+            self._h, tas_gen, gas_gen, n_pods, _dptr(pod_policy_t), _dptr(cand_t),
+            max_containers, i915_index, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), k,
+            node_base, _dptr(key_t), _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_gas_topk_policies_device")
+
+    def tas_gas_topk_policies_wide_device(self, tas_gen: int, gas_gen: int, n_pods: int,
+                                          pod_policy_t, cand_t, max_containers: int,
+                                          i915_index: int, req_t, mask_t, ncont_t, k: int,
+                                          node_base: int, key_t, sub_t, node_t, len_t,
+                                          stream=None):
+        """tas_gas_topk_wide_device by policy id (pas_tas_gas_topk_policies_wide_device)."""
+        rc = self._l.pas_tas_gas_topk_policies_wide_device(
+            self._h, tas_gen, gas_gen, n_pods, _dptr(pod_policy_t), _dptr(cand_t),
+            max_containers, i915_index, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), k,
+            node_base, _dptr(key_t), _dptr(sub_t), _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_gas_topk_policies_wide_device")
+
+    def tas_gas_topk_policies_after_device(self, tas_gen: int, gas_gen: int, n_pods: int,
+                                           pod_policy_t, cand_t, max_containers: int,
+                                           i915_index: int, req_t, mask_t, ncont_t, k: int,
+                                           node_base: int, after_key_t, after_node_t, key_t,
+                                           node_t, len_t, stream=None):
+        """tas_gas_topk_after_device by policy id (pas_tas_gas_topk_policies_after_device)."""
+        rc = self._l.pas_tas_gas_topk_policies_after_device(
+            self._h, tas_gen, gas_gen, n_pods, _dptr(pod_policy_t), _dptr(cand_t),
+            max_containers, i915_index, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), k,
+            node_base, _dptr(after_key_t), _dptr(after_node_t), _dptr(key_t), _dptr(node_t),
+            _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_gas_topk_policies_after_device")
+
+    def tas_gas_topk_policies_wide_after_device(self, tas_gen: int, gas_gen: int, n_pods: int,
+                                                pod_policy_t, cand_t, max_containers: int,
+                                                i915_index: int, req_t, mask_t, ncont_t, k: int,
+                                                node_base: int, after_key_t, after_sub_t,
+                                                after_node_t, key_t, sub_t, node_t, len_t,
+                                                stream=None):
+        """tas_gas_topk_wide_after_device by policy id
+        (pas_tas_gas_topk_policies_wide_after_device)."""
+        rc = self._l.pas_tas_gas_topk_policies_wide_after_device(
+            self._h, tas_gen, gas_gen, n_pods, _dptr(pod_policy_t), _dptr(cand_t),
+            max_containers, i915_index, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), k,
+            node_base, _dptr(after_key_t), _dptr(after_sub_t), _dptr(after_node_t),
+            _dptr(key_t), _dptr(sub_t), _dptr(node_t), _dptr(len_t), _stream(stream))
+        self._check(rc, "pas_tas_gas_topk_policies_wide_after_device")

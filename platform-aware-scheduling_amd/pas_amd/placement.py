@@ -3,8 +3,9 @@ pod is placed or has tried every node of its list.
 
 One pas_tas_gas_topk_device -> pas_gas_place_device pass leaves a pod unplaced as soon as its
 k candidates were taken by the pods before it.  Here such a pod continues: its next row
-resumes the list strictly after the last record it tried (pas_tas_gas_topk[_wide]_after_device,
-include/pas.h "Resuming a top-k list") on the usage the round before left behind.
+resumes the list strictly after the last record it tried (pas_tas_gas_topk[_wide]_after_device
+or, by policy id, pas_tas_gas_topk_policies[_wide]_after_device; include/pas.h "Resuming a
+top-k list") on the usage the round before left behind.
 
 Equivalence.  During the call the usage only grows, so a node that did not fit a pod at a
 round's start never fits it later in the call: a row holds the next k nodes of the pod's list
@@ -35,12 +36,18 @@ rounds (top-k + place passes run) and gas_gen (the GAS generation after the last
 def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: int, rules_t,
                         rule_off_t, prio_t, cand_t, max_containers: int, i915_index: int, req_t,
                         mask_t, ncont_t, k: int, node_base: int = 0, wide: bool = False,
-                        max_rounds=None, stream=None) -> PlacementResult:
+                        max_rounds=None, stream=None, pod_policy_t=None) -> PlacementResult:
     """Place a batch until every pod is placed or has provably run out of nodes (the module's
     docstring has the equivalence).  The pod batch tensors are those of
     Context.tas_gas_topk[_wide]_device and Context.gas_place_device; wide selects the wide
     records (required on a snapshot with wide columns).  Every pass moves the GAS snapshot one
     generation on, from gas_gen; the result names the last one.
+
+    pod_policy_t (int32 [P] on the device): the pods name rows of the resident policy table
+    and every round calls pas_tas_gas_topk_policies[_wide]_after_device; n_rules, rules_t,
+    rule_off_t and prio_t are then ignored and may be None.  The policies' violating sets are
+    built at most once per call, by the first round if they are not current: the TAS snapshot
+    does not change between rounds, so the later rounds evaluate no dontschedule rule at all.
 
     max_rounds defaults to ceil(N / k) + 1, which the loop cannot exceed: every unfinished
     cursor advances by k records per round.  Passing it raises RuntimeError (the passes run so
@@ -73,14 +80,20 @@ def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: i
             if rounds >= max_rounds:
                 raise RuntimeError(f"place_to_completion: pods still queued after {rounds} "
                                    f"rounds (max_rounds)")
-            head = (tas_gen, gen, p, n_rules, rules_t, rule_off_t, prio_t, cand_t,
-                    max_containers, i915_index, req_t, mask_t, ncont_t, k, node_base)
-            if wide:
-                ctx.tas_gas_topk_wide_after_device(*head, after_key, after_sub, after_node, key,
-                                                   sub, top_node, top_len, stream=stream)
+            tail = (cand_t, max_containers, i915_index, req_t, mask_t, ncont_t, k, node_base)
+            if pod_policy_t is not None:
+                head = (tas_gen, gen, p, pod_policy_t) + tail
+                topk = ctx.tas_gas_topk_policies_after_device
+                topk_wide = ctx.tas_gas_topk_policies_wide_after_device
             else:
-                ctx.tas_gas_topk_after_device(*head, after_key, after_node, key, top_node,
-                                              top_len, stream=stream)
+                head = (tas_gen, gen, p, n_rules, rules_t, rule_off_t, prio_t) + tail
+                topk = ctx.tas_gas_topk_after_device
+                topk_wide = ctx.tas_gas_topk_wide_after_device
+            if wide:
+                topk_wide(*head, after_key, after_sub, after_node, key, sub, top_node, top_len,
+                          stream=stream)
+            else:
+                topk(*head, after_key, after_node, key, top_node, top_len, stream=stream)
             placed_now, _ = ctx.gas_place_device(gen, gen + 1, p, max_containers, i915_index,
                                                  req_t, mask_t, ncont_t, k, k, node_base,
                                                  top_node, top_len, r_node, r_rank, r_res,

@@ -7,8 +7,9 @@ and onDelete write the policy, register its strategies with the MetricEnforcer
 (strategies/core/enforcer.go:64-103) and register each rule's metric with the metric cache.
 Here the same decisions are made on the host, as TasCache makes the metric half's: every
 policy gets a stable id, its row of the table installed by pas_tas_policies_set, and the verbs
-by policy id (pas_tas_eval_policies, pas_tas_filter_requests_policies) read that row where the
-reference reads the object with cache.ReadPolicy.
+by policy id (pas_tas_eval_policies, pas_tas_filter_requests_policies, the
+pas_tas[_gas]_topk_policies* entry points) read that row where the reference reads the object
+with cache.ReadPolicy.
 """
 from __future__ import annotations
 
@@ -152,6 +153,13 @@ class PolicyCache:
     def id_of(self, key: Tuple[str, str]) -> int:
         """The policy's row of the table (KeyError for a policy the cache does not hold)."""
         return self.ids[key]
+
+    def ids_of(self, keys: Sequence[Tuple[str, str]]) -> np.ndarray:
+        """The rows of a pod batch's policies as int32 [len(keys)], -1 for a policy the cache
+        does not hold: the pod_policy array of the verbs and top-k entry points by policy id,
+        which read -1 as no dontschedule rules and no prio rule."""
+        return np.fromiter((self.ids.get(key, -1) for key in keys), dtype=np.int32,
+                           count=len(keys))
 
     def prio_of(self, policy_id: int):
         """The host pas_rule of row policy_id's scheduleonmetric rule; metric -1: none."""

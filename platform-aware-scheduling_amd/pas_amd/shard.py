@@ -219,6 +219,34 @@ class ShardedTopK:
                                              self.node_base, key, node, ln, s)
         return self._run(n_pods, records, stream)
 
+    def run_policies(self, gen: int, n_pods: int, pod_policy_t, cand_t=None, stream=None):
+        """`run` with pod p's rules and prio being row pod_policy_t[p] (int32 [P] on the device)
+        of the rank's resident policy table (pas_tas_topk_policies[_wide]_device).  Every rank
+        must hold the same table rows for the ids to mean the same policies."""
+        def records(key, sub, node, ln, s):
+            if self.wide:
+                self.ctx.tas_topk_policies_wide_device(gen, n_pods, pod_policy_t, cand_t, self.k,
+                                                       self.node_base, key, sub, node, ln, s)
+            else:
+                self.ctx.tas_topk_policies_device(gen, n_pods, pod_policy_t, cand_t, self.k,
+                                                  self.node_base, key, node, ln, s)
+        return self._run(n_pods, records, stream)
+
+    def run_tas_gas_policies(self, tas_gen: int, gas_gen: int, n_pods: int, pod_policy_t,
+                             max_containers: int, i915_index: int, req_t, mask_t, ncont_t,
+                             cand_t=None, stream=None):
+        """`run_tas_gas` by policy id (pas_tas_gas_topk_policies[_wide]_device)."""
+        def records(key, sub, node, ln, s):
+            if self.wide:
+                self.ctx.tas_gas_topk_policies_wide_device(
+                    tas_gen, gas_gen, n_pods, pod_policy_t, cand_t, max_containers, i915_index,
+                    req_t, mask_t, ncont_t, self.k, self.node_base, key, sub, node, ln, s)
+            else:
+                self.ctx.tas_gas_topk_policies_device(
+                    tas_gen, gas_gen, n_pods, pod_policy_t, cand_t, max_containers, i915_index,
+                    req_t, mask_t, ncont_t, self.k, self.node_base, key, node, ln, s)
+        return self._run(n_pods, records, stream)
+
     def _run(self, n_pods, records, stream):
         k = self.k
         on_gpu = torch.cuda.is_available() and str(self.device).startswith("cuda")
