@@ -533,6 +533,80 @@ int pas_tas_deschedule_device(pas_ctx* ctx, uint64_t gen, int32_t n_strategies,
 int pas_label_patch_json(int32_t n_strategies, const char* const* names, uint64_t add_mask,
                          uint64_t remove_mask, char* buf, int64_t cap, int64_t* len);
 
+/* The label plan as a patch list: one record per node whose PATCH body is not "[]", in
+ * ascending node index, compacted on the device, so that an enforcer reads and patches only
+ * the nodes that change.  viol, name_id, labels and total_out are those of pas_tas_label_plan,
+ * and add[node] / rem[node] below are its masks.  Two optional bitmaps describe the VALUES of
+ * the carried labels, in the shape and row convention of labels ([s][W64], only the rows of
+ * each name's first strategy k read, and only where the labels bit is set; both ignored when
+ * labels is NULL):
+ *   violating    bit (k, node): the node's label <name k> has the value "violating"
+ *   null_        bit (k, node): it has the value "null"
+ * The reduced masks drop what would write a value the label already holds:
+ *   add'[node]   add[node] without the bits of EVERY strategy of name k where
+ *                labels & violating has bit (k, node) (two violating strategies of one name
+ *                write the same label)
+ *   rem'[node]   rem[node] & ~(labels & null_)[k]
+ * Applying the reduced patch gives the node the labels the full patch gives it.  A bit set in
+ * both value bitmaps is contradictory input; each bitmap is applied as stated, so the result is
+ * defined.  With both NULL the list is exactly the nodes of a non-empty reference body.
+ *   patch_node   [cap] int32 node index, ascending
+ *   patch_add    [cap] add' of that node
+ *   patch_rem    [cap] rem' of that node
+ *   n_patches    the nodes with add' | rem' != 0, also when that exceeds cap
+ *   total_out    as pas_tas_label_plan (it does not depend on the values)
+ * Records [0, min(cap, n_patches)) are written and are the first in node order; nothing at or
+ * past that is touched: call again with larger arrays, as with the side buffer of
+ * pas_gas_fit_ex.  cap = 0 with NULL record arrays only counts.  n_nodes = 0 or
+ * n_strategies = 0: n_patches = 0, total 0.  Shape limits and errors as pas_tas_label_plan.
+ * The order comes from a segmented count, a scan and a ranked scatter: no atomics, so a list is
+ * reproducible.  The host form copies back only min(cap, n_patches) records.  The _device form
+ * takes device bitmaps and outputs (d_n_patches and d_total_out: device int64, valid after the
+ * stream) and a host name_id, and is asynchronous on hip_stream. */
+int pas_tas_label_patches(pas_ctx* ctx, int32_t n_nodes, int32_t n_strategies,
+                          const uint64_t* viol, const int32_t* name_id, const uint64_t* labels,
+                          const uint64_t* violating, const uint64_t* null_, int64_t cap,
+                          int32_t* patch_node, uint64_t* patch_add, uint64_t* patch_rem,
+                          int64_t* n_patches, int64_t* total_out);
+int pas_tas_label_patches_device(pas_ctx* ctx, int32_t n_nodes, int32_t n_strategies,
+                                 const uint64_t* d_viol, const int32_t* name_id,
+                                 const uint64_t* d_labels, const uint64_t* d_violating,
+                                 const uint64_t* d_null, int64_t cap, int32_t* d_patch_node,
+                                 uint64_t* d_patch_add, uint64_t* d_patch_rem,
+                                 int64_t* d_n_patches, int64_t* d_total_out, void* hip_stream);
+
+/* The deschedule sweep and its patch list in one call, as pas_tas_deschedule_device is to
+ * pas_tas_violations_device + pas_tas_label_plan_device: the sweep of pas_tas_violations over
+ * the resident snapshot, then pas_tas_label_patches on its bitmaps for the snapshot's n_nodes.
+ * viol_out [s][W64] is optional: NULL keeps the bitmaps in the call's own workspace (the
+ * stream's, in the _device form).  Generation, rule and offset checks as pas_tas_violations
+ * (host form) and pas_tas_deschedule_device (_device form, d_rule_off read clamped);
+ * n_strategies <= 64. */
+int pas_tas_deschedule_patches(pas_ctx* ctx, uint64_t gen, int32_t n_strategies,
+                               const pas_rule* rules, const int32_t* rule_off,
+                               const int32_t* name_id, const uint64_t* labels,
+                               const uint64_t* violating, const uint64_t* null_,
+                               uint64_t* viol_out, int64_t cap, int32_t* patch_node,
+                               uint64_t* patch_add, uint64_t* patch_rem, int64_t* n_patches,
+                               int64_t* total_out);
+int pas_tas_deschedule_patches_device(pas_ctx* ctx, uint64_t gen, int32_t n_strategies,
+                                      int32_t n_rules, const pas_rule* d_rules,
+                                      const int32_t* d_rule_off, const int32_t* name_id,
+                                      const uint64_t* d_labels, const uint64_t* d_violating,
+                                      const uint64_t* d_null, uint64_t* d_viol_out, int64_t cap,
+                                      int32_t* d_patch_node, uint64_t* d_patch_add,
+                                      uint64_t* d_patch_rem, int64_t* d_n_patches,
+                                      int64_t* d_total_out, void* hip_stream);
+
+/* The bodies of a whole patch list in one call: body i is buf[offsets[i] .. offsets[i + 1]),
+ * byte-equal to pas_label_patch_json on (add[i], rem[i]); offsets has n_patches + 1 entries.
+ * Writes at most cap bytes; *total_len and every offset hold the full sizes also when
+ * PAS_ECAPACITY is returned.  PAS_EINVAL (nothing written) for a mask bit at or past
+ * n_strategies in any record.  Host-only. */
+int pas_label_patch_json_batch(int32_t n_strategies, const char* const* names,
+                               int64_t n_patches, const uint64_t* add, const uint64_t* rem,
+                               char* buf, int64_t cap, int64_t* offsets, int64_t* total_len);
+
 /* ------------------------------------------------------------------------- */
 /* GPU Aware Scheduling                                                      */
 /* ------------------------------------------------------------------------- */

@@ -2316,6 +2316,171 @@ int pas_tas_deschedule_device(pas_ctx* ctx, uint64_t gen, int32_t n_strategies,
                                d_remove_out, d_total_out, pick_stream(ctx, hip_stream));
 }
 
+// What the patch-list entry points check alike (the shape as check_label_plan).
+static int check_label_patches(pas_ctx* ctx, int32_t n_nodes, int32_t n_strat, const void* viol,
+                               int64_t cap, const void* node, const void* add, const void* rem,
+                               const void* n_patches, const void* total, const char* fn) {
+  if (n_nodes < 0 || n_strat < 0 || n_strat > 64)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad shape (0 <= n_strat <= 64)");
+  if (cap < 0) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": cap < 0");
+  if (!total || !n_patches || (cap > 0 && (!node || !add || !rem)) ||
+      (n_nodes > 0 && n_strat > 0 && !viol))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
+  return PAS_OK;
+}
+
+// The host forms' records: device arrays of min(cap, n_nodes) records (a list is never longer),
+// of which the first min(cap, n_patches) are copied back once the count is known.
+struct PatchRecords {
+  int32_t* d_node;
+  uint64_t *d_add, *d_rem;
+  int64_t* d_n;
+  int64_t room;
+  void state(Staging& st, int32_t n_nodes, int64_t cap, int64_t* n_patches) {
+    room = std::min<int64_t>(cap, n_nodes);
+    st.work(d_node, (size_t)room);
+    st.work(d_add, (size_t)room);
+    st.work(d_rem, (size_t)room);
+    st.out(d_n, n_patches, 1);
+  }
+  // after st.fetch(): *n_patches is the list's length
+  int fetch(pas_ctx* ctx, int64_t n_patches, int32_t* node, uint64_t* add, uint64_t* rem) {
+    const size_t n = (size_t)std::min(room, n_patches);
+    if (n == 0) return PAS_OK;
+    PAS_HIP(ctx, hipMemcpyAsync(node, d_node, sizeof(int32_t) * n, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    PAS_HIP(ctx, hipMemcpyAsync(add, d_add, sizeof(uint64_t) * n, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    PAS_HIP(ctx, hipMemcpyAsync(rem, d_rem, sizeof(uint64_t) * n, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    PAS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PAS_OK;
+  }
+};
+
+int pas_tas_label_patches(pas_ctx* ctx, int32_t n_nodes, int32_t n_strat, const uint64_t* viol,
+                          const int32_t* name_id, const uint64_t* labels,
+                          const uint64_t* violating, const uint64_t* null_, int64_t cap,
+                          int32_t* patch_node, uint64_t* patch_add, uint64_t* patch_rem,
+                          int64_t* n_patches, int64_t* total_out) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_label_patches(ctx, n_nodes, n_strat, viol, cap, patch_node, patch_add,
+                               patch_rem, n_patches, total_out, "pas_tas_label_patches");
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  const size_t bits = (size_t)n_strat * (size_t)w64(n_nodes);
+  Staging st(ctx);
+  uint64_t *d_viol, *d_labels, *d_violating, *d_null;
+  int64_t* d_total;
+  PatchRecords rec;
+  st.in(d_viol, viol, bits);
+  st.in_opt(d_labels, labels, bits);
+  st.in_opt(d_violating, labels ? violating : nullptr, bits);
+  st.in_opt(d_null, labels ? null_ : nullptr, bits);
+  rec.state(st, n_nodes, cap, n_patches);
+  st.out(d_total, total_out, 1);
+  if ((rc = st.upload())) return rc;
+  rc = label_patches_launch(ctx, n_nodes, n_strat, make_name_plan(n_strat, name_id), d_viol,
+                            d_labels, d_violating, d_null, rec.room, rec.d_node, rec.d_add,
+                            rec.d_rem, rec.d_n, d_total, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return rec.fetch(ctx, *n_patches, patch_node, patch_add, patch_rem);
+}
+
+int pas_tas_label_patches_device(pas_ctx* ctx, int32_t n_nodes, int32_t n_strat,
+                                 const uint64_t* d_viol, const int32_t* name_id,
+                                 const uint64_t* d_labels, const uint64_t* d_violating,
+                                 const uint64_t* d_null, int64_t cap, int32_t* d_patch_node,
+                                 uint64_t* d_patch_add, uint64_t* d_patch_rem,
+                                 int64_t* d_n_patches, int64_t* d_total_out, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_label_patches(ctx, n_nodes, n_strat, d_viol, cap, d_patch_node, d_patch_add,
+                               d_patch_rem, d_n_patches, d_total_out,
+                               "pas_tas_label_patches_device");
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  return label_patches_launch(ctx, n_nodes, n_strat, make_name_plan(n_strat, name_id), d_viol,
+                              d_labels, d_violating, d_null, cap, d_patch_node, d_patch_add,
+                              d_patch_rem, d_n_patches, d_total_out,
+                              pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_deschedule_patches(pas_ctx* ctx, uint64_t gen, int32_t n_strat,
+                               const pas_rule* rules, const int32_t* rule_off,
+                               const int32_t* name_id, const uint64_t* labels,
+                               const uint64_t* violating, const uint64_t* null_,
+                               uint64_t* viol_out, int64_t cap, int32_t* patch_node,
+                               uint64_t* patch_add, uint64_t* patch_rem, int64_t* n_patches,
+                               int64_t* total_out) {
+  const char* fn = "pas_tas_deschedule_patches";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  const int32_t N = ctx->tas.n_nodes;
+  // (the sweep's bitmaps are the call's own when viol_out is null)
+  if ((rc = check_label_patches(ctx, N, n_strat, ctx, cap, patch_node, patch_add, patch_rem,
+                                n_patches, total_out, fn)))
+    return rc;
+  int32_t n_rules = 0;
+  if (n_strat > 0) {
+    if (!rule_off) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null rule_off");
+    if ((rc = validate_csr(ctx, n_strat, rule_off, "rule_off"))) return rc;
+    n_rules = rule_off[n_strat];
+    if (n_rules > 0 && !rules) return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null rules");
+    if ((rc = validate_rules(ctx, n_rules, rules))) return rc;
+  }
+  if ((rc = activate(ctx))) return rc;
+  const size_t bits = (size_t)n_strat * (size_t)w64(N);
+  Staging st(ctx);
+  pas_rule* d_rules;
+  int32_t* d_off;
+  uint64_t *d_viol, *d_labels, *d_violating, *d_null;
+  int64_t* d_total;
+  PatchRecords rec;
+  st.in(d_rules, rules, (size_t)n_rules);
+  st.in(d_off, rule_off, n_strat > 0 ? (size_t)n_strat + 1 : 0);
+  st.in_opt(d_labels, labels, bits);
+  st.in_opt(d_violating, labels ? violating : nullptr, bits);
+  st.in_opt(d_null, labels ? null_ : nullptr, bits);
+  st.out_opt(d_viol, viol_out, bits);
+  rec.state(st, N, cap, n_patches);
+  st.out(d_total, total_out, 1);
+  if ((rc = st.upload())) return rc;
+  rc = tas_deschedule_patches_launch(ctx, n_strat, n_rules, d_rules, d_off, d_viol,
+                                     make_name_plan(n_strat, name_id), d_labels, d_violating,
+                                     d_null, rec.room, rec.d_node, rec.d_add, rec.d_rem, rec.d_n,
+                                     d_total, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return rec.fetch(ctx, *n_patches, patch_node, patch_add, patch_rem);
+}
+
+int pas_tas_deschedule_patches_device(pas_ctx* ctx, uint64_t gen, int32_t n_strat,
+                                      int32_t n_rules, const pas_rule* d_rules,
+                                      const int32_t* d_rule_off, const int32_t* name_id,
+                                      const uint64_t* d_labels, const uint64_t* d_violating,
+                                      const uint64_t* d_null, uint64_t* d_viol_out, int64_t cap,
+                                      int32_t* d_patch_node, uint64_t* d_patch_add,
+                                      uint64_t* d_patch_rem, int64_t* d_n_patches,
+                                      int64_t* d_total_out, void* hip_stream) {
+  const char* fn = "pas_tas_deschedule_patches_device";
+  if (!ctx) return PAS_EINVAL;
+  int rc = check_tas_gen(ctx, gen);
+  if (rc) return rc;
+  if (n_rules < 0) return set_error(ctx, PAS_EINVAL, "negative count");
+  if ((rc = check_label_patches(ctx, ctx->tas.n_nodes, n_strat, ctx, cap, d_patch_node,
+                                d_patch_add, d_patch_rem, d_n_patches, d_total_out, fn)))
+    return rc;
+  if (n_strat > 0 && (!d_rule_off || (n_rules > 0 && !d_rules)))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  if ((rc = activate(ctx))) return rc;
+  return tas_deschedule_patches_launch(ctx, n_strat, n_rules, d_rules, d_rule_off, d_viol_out,
+                                       make_name_plan(n_strat, name_id), d_labels, d_violating,
+                                       d_null, cap, d_patch_node, d_patch_add, d_patch_rem,
+                                       d_n_patches, d_total_out, pick_stream(ctx, hip_stream));
+}
+
 // --------------------------------------------------------------------------- node shards
 
 // (d_top_sub: the wide entry points' third record array; fn names the entry point)

@@ -238,7 +238,9 @@ enum SlotBuf {
   // per-pod prio rules and the all-zero rule offsets of an evaluation by policy id, or the
   // request offsets and policy ids of a request filter by policy id (tas_policy.hip)
   kBufPolicy = 5,
-  kSlotBufs = 6
+  kBufPatch = 6,      // segment counts and violated pairs of a patch list (tas_patches.hip)
+  kBufPatchViol = 7,  // the sweep's bitmaps of pas_tas_deschedule_patches without viol_out
+  kSlotBufs = 8
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -592,5 +594,23 @@ int tas_deschedule_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,
                           const NamePlan& names,
                           const uint64_t* d_labels, uint64_t* d_add, uint64_t* d_rem,
                           int64_t* d_total, hipStream_t s);
+// The plan as a patch list (tas_patches.hip): the nodes whose reduced masks (pas.h,
+// pas_tas_label_patches) are not both zero, in ascending node index, as records d_node / d_add
+// / d_rem [0 .. min(cap, n)), n to *d_n_patches, total as label_plan_launch.  d_labels,
+// d_violating and d_null may be null; the record arrays too when cap is 0.
+int label_patches_launch(pas_ctx* ctx, int32_t n_nodes, int32_t n_strat, const NamePlan& names,
+                         const uint64_t* d_viol, const uint64_t* d_labels,
+                         const uint64_t* d_violating, const uint64_t* d_null, int64_t cap,
+                         int32_t* d_node, uint64_t* d_add, uint64_t* d_rem, int64_t* d_n_patches,
+                         int64_t* d_total, hipStream_t s);
+// tas_violations_launch into d_viol (null: the stream's slot), then label_patches_launch on
+// those bitmaps for the snapshot's nodes.
+int tas_deschedule_patches_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,
+                                  const pas_rule* d_rules, const int32_t* d_rule_off,
+                                  uint64_t* d_viol, const NamePlan& names,
+                                  const uint64_t* d_labels, const uint64_t* d_violating,
+                                  const uint64_t* d_null, int64_t cap, int32_t* d_node,
+                                  uint64_t* d_add, uint64_t* d_rem, int64_t* d_n_patches,
+                                  int64_t* d_total, hipStream_t s);
 
 }  // namespace pas

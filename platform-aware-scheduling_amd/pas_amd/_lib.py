@@ -178,6 +178,19 @@ SIGNATURES = {
         c_int,
         [c_int32, POINTER(c_char_p), c_uint64, c_uint64, c_char_p, c_int64, POINTER(c_int64)],
     ),
+    "pas_tas_label_patches": (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P, _P, c_int64, _P, _P,
+                                      _P, POINTER(c_int64), POINTER(c_int64)]),
+    "pas_tas_label_patches_device": (c_int, [_P, c_int32, c_int32, _P, _P, _P, _P, _P, c_int64,
+                                             _P, _P, _P, _P, _P, _P]),
+    "pas_tas_deschedule_patches": (c_int, [_P, c_uint64, c_int32, _P, _P, _P, _P, _P, _P, _P,
+                                           c_int64, _P, _P, _P, POINTER(c_int64),
+                                           POINTER(c_int64)]),
+    "pas_tas_deschedule_patches_device": (c_int, [_P, c_uint64, c_int32, c_int32, _P, _P, _P, _P,
+                                                  _P, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
+    "pas_label_patch_json_batch": (
+        c_int,
+        [c_int32, POINTER(c_char_p), c_int64, _P, _P, _P, c_int64, _P, POINTER(c_int64)],
+    ),
     "pas_gas_snapshot_set": (c_int, [_P, c_uint64, c_int32, c_int32, c_int32, _P, _P, _P]),
     "pas_gas_snapshot_set_device": (
         c_int,

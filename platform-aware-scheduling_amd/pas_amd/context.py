@@ -128,6 +128,30 @@ def label_patch_json(names, add_mask: int, remove_mask: int) -> bytes:
         cap = n.value
 
 
+def label_patch_json_batch(names, add, rem) -> list:
+    """The PATCH bodies of a whole patch list (pas_label_patch_json_batch): body i is
+    label_patch_json(names, add[i], rem[i]), all rendered in one host call."""
+    l = _lib.load()
+    add = np.ascontiguousarray(add, dtype=np.uint64).reshape(-1)
+    rem = np.ascontiguousarray(rem, dtype=np.uint64).reshape(-1)
+    assert add.shape == rem.shape, "one add and one remove mask per record"
+    n = add.shape[0]
+    arr = (ctypes.c_char_p * max(len(names), 1))(*[x.encode() for x in names])
+    off = np.zeros(n + 1, np.int64)
+    total = c_int64()
+    cap = 64 * n + 64
+    while True:
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        rc = l.pas_label_patch_json_batch(len(names), arr, n, _ptr(add), _ptr(rem), buf, cap,
+                                          _ptr(off), byref(total))
+        if rc == _lib.PAS_OK:
+            raw, o = buf.raw, off.tolist()
+            return [raw[o[i]:o[i + 1]] for i in range(n)]
+        if rc != _lib.PAS_ECAPACITY:
+            raise PasError(rc, "pas_label_patch_json_batch")
+        cap = total.value
+
+
 class Context:
     """One pas_ctx bound to a HIP device."""
 
@@ -630,6 +654,111 @@ class Context:
                                                _dptr(labels_t), _dptr(add_t), _dptr(rem_t),
                                                _dptr(total_t), _stream(stream))
         self._check(rc, "pas_tas_deschedule_device")
+
+    # -- the label plan as a patch list (pas_tas_label_patches, pas_tas_deschedule_patches)
+    @staticmethod
+    def _bitmaps(shape, **maps):
+        """Optional [S][W64] bitmaps as contiguous uint64 arrays of `shape` (None stays None)."""
+        out = []
+        for what, m in maps.items():
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint64)
+                assert m.shape == shape, f"{what} must have the shape of viol"
+            out.append(m)
+        return out
+
+    @staticmethod
+    def _patch_records(cap: int, out):
+        """The record arrays of a host patch-list call: `out` = (node, add, rem) arrays of at
+        least cap entries to write into (entries past the list stay as they are), else new."""
+        if out is None:
+            return np.zeros(cap, np.int32), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        node, add, rem = out
+        assert node.dtype == np.int32 and add.dtype == np.uint64 and rem.dtype == np.uint64
+        assert min(node.size, add.size, rem.size) >= cap, "record arrays shorter than cap"
+        return node, add, rem
+
+    def tas_label_patches(self, n_nodes: int, viol: np.ndarray,
+                          labels: Optional[np.ndarray] = None, names=None,
+                          violating: Optional[np.ndarray] = None,
+                          null: Optional[np.ndarray] = None, cap: Optional[int] = None, out=None):
+        """(node, add, rem, n_patches, total): the nodes whose patch body is not "[]" in
+        ascending index with their masks (pas_tas_label_patches), from viol[S][W64] and the
+        optional labels / violating / null bitmaps of that shape.  cap (default n_nodes) bounds
+        the records; without `out` the arrays returned hold the min(cap, n_patches) records,
+        with `out` they are the caller's arrays."""
+        viol = np.ascontiguousarray(viol, dtype=np.uint64)
+        s = viol.shape[0]
+        labels, violating, null = self._bitmaps(viol.shape, labels=labels, violating=violating,
+                                                null=null)
+        ids = self._name_ids(names, s)
+        cap = n_nodes if cap is None else cap
+        node, add, rem = self._patch_records(cap, out)
+        n, total = c_int64(), c_int64()
+        opt = lambda m: _ptr(m) if m is not None and m.size else None  # noqa: E731
+        rc = self._l.pas_tas_label_patches(self._h, n_nodes, s, opt(viol), _ptr(ids), opt(labels),
+                                           opt(violating), opt(null), cap, opt(node), opt(add),
+                                           opt(rem), byref(n), byref(total))
+        self._check(rc, "pas_tas_label_patches")
+        if out is None:
+            k = min(cap, n.value)
+            node, add, rem = node[:k], add[:k], rem[:k]
+        return node, add, rem, n.value, total.value
+
+    def tas_label_patches_device(self, n_nodes: int, n_strat: int, viol_t, labels_t, violating_t,
+                                 null_t, cap: int, node_t, add_t, rem_t, n_patches_t, total_t,
+                                 stream=None, names=None):
+        ids = self._name_ids(names, n_strat)
+        rc = self._l.pas_tas_label_patches_device(
+            self._h, n_nodes, n_strat, _dptr(viol_t), _ptr(ids), _dptr(labels_t),
+            _dptr(violating_t), _dptr(null_t), cap, _dptr(node_t), _dptr(add_t), _dptr(rem_t),
+            _dptr(n_patches_t), _dptr(total_t), _stream(stream))
+        self._check(rc, "pas_tas_label_patches_device")
+
+    def tas_deschedule_patches(self, gen: int, rules: np.ndarray, rule_off: np.ndarray,
+                               labels: Optional[np.ndarray] = None, names=None,
+                               violating: Optional[np.ndarray] = None,
+                               null: Optional[np.ndarray] = None, cap: Optional[int] = None,
+                               out=None, want_viol: bool = False):
+        """The sweep of tas_violations and tas_label_patches on its bitmaps in one call
+        (pas_tas_deschedule_patches): (node, add, rem, n_patches, total), and the sweep's
+        viol[S][W64] as a sixth item with want_viol."""
+        rule_off = np.ascontiguousarray(rule_off, dtype=np.int32)
+        s = rule_off.shape[0] - 1
+        rules = np.ascontiguousarray(rules, dtype=RULE_DTYPE)
+        n_nodes = self.n_nodes
+        shape = (s, w64(n_nodes))
+        labels, violating, null = self._bitmaps(shape, labels=labels, violating=violating,
+                                                null=null)
+        ids = self._name_ids(names, s)
+        cap = n_nodes if cap is None else cap
+        node, add, rem = self._patch_records(cap, out)
+        viol = np.zeros(shape, np.uint64) if want_viol else None
+        n, total = c_int64(), c_int64()
+        opt = lambda m: _ptr(m) if m is not None and m.size else None  # noqa: E731
+        rc = self._l.pas_tas_deschedule_patches(
+            self._h, gen, s, opt(rules), _ptr(rule_off), _ptr(ids), opt(labels), opt(violating),
+            opt(null), opt(viol), cap, opt(node), opt(add), opt(rem), byref(n), byref(total))
+        self._check(rc, "pas_tas_deschedule_patches")
+        if out is None:
+            k = min(cap, n.value)
+            node, add, rem = node[:k], add[:k], rem[:k]
+        res = (node, add, rem, n.value, total.value)
+        return res + (viol,) if want_viol else res
+
+    def tas_deschedule_patches_device(self, gen: int, n_strat: int, n_rules: int, rules_t,
+                                      rule_off_t, labels_t, violating_t, null_t, viol_t,
+                                      cap: int, node_t, add_t, rem_t, n_patches_t, total_t,
+                                      stream=None, names=None):
+        """pas_tas_deschedule_patches_device: viol_t None keeps the sweep's bitmaps in the
+        stream's workspace."""
+        ids = self._name_ids(names, n_strat)
+        rc = self._l.pas_tas_deschedule_patches_device(
+            self._h, gen, n_strat, n_rules, _dptr(rules_t), _dptr(rule_off_t), _ptr(ids),
+            _dptr(labels_t), _dptr(violating_t), _dptr(null_t), _dptr(viol_t), cap,
+            _dptr(node_t), _dptr(add_t), _dptr(rem_t), _dptr(n_patches_t), _dptr(total_t),
+            _stream(stream))
+        self._check(rc, "pas_tas_deschedule_patches_device")
 
     # ------------------------------------------------------------------ GAS
     def gas_snapshot_set(self, gen: int, n_cards: np.ndarray, cap_per_gpu: np.ndarray,

@@ -549,3 +549,73 @@ class DescheduleEnforcer:
         bodies = {self.node_names[i]: b"[" + b",".join(adds[i] + rems[i]) + b"]"
                   for i in range(n)}
         return total, bodies
+
+    def _group_rules(self, g: List[int]):
+        """(rules, rule_off) of the strategies of plan group g, in the group's order."""
+        idx = [np.arange(self.rule_off[j], self.rule_off[j + 1]) for j in g]
+        off = np.concatenate([[0], np.cumsum([len(i) for i in idx])]).astype(np.int32)
+        return self.rules[np.concatenate(idx).astype(np.int64)], off
+
+    def enforce_changes(self, node_labels: Sequence[Mapping[str, str]],
+                        skip_settled: bool = False):
+        """(totalViolations, {node name: PATCH body}) as enforce, for the nodes whose body is
+        not "[]" only: the sweep and the patch list of each plan group in one call
+        (pas_tas_deschedule_patches) and the bodies of a list in one
+        (pas_label_patch_json_batch).  skip_settled also leaves out what would write a value
+        the node's label already has ("violating" added again, "null" removed and re-added):
+        the labels after the patch are the same, and a settled node gets no body."""
+        from .context import label_patch_json_batch
+        n, s = len(self.node_names), len(self.names)
+        w = w64(n)
+        labels = np.zeros((s, w), np.uint64)
+        violating = np.zeros((s, w), np.uint64) if skip_settled else None
+        null = np.zeros((s, w), np.uint64) if skip_settled else None
+        rows: Dict[str, List[int]] = {}
+        for j, name in enumerate(self.names):
+            rows.setdefault(name, []).append(j)
+        for i, lab in enumerate(node_labels):
+            bit = np.uint64(1 << (i & 63))
+            for name, value in lab.items():
+                for j in rows.get(name, ()):
+                    labels[j, i >> 6] |= bit
+                    if skip_settled and value == "violating":
+                        violating[j, i >> 6] |= bit
+                    if skip_settled and value == "null":
+                        null[j, i >> 6] |= bit
+        total = 0
+        lists = []  # per group: (names, node, add, rem)
+        for g in self.groups:
+            if not g:
+                continue
+            rules, off = self._group_rules(g)
+            names = [self.names[j] for j in g]
+            try:
+                node, add, rem, _, t = self.ctx.tas_deschedule_patches(
+                    self.gen, rules, off, labels[g], names,
+                    violating[g] if skip_settled else None, null[g] if skip_settled else None)
+            except _lib.PasError as e:
+                _raise_if_panic(e)
+            total += t
+            lists.append((names, node, add, rem))
+        if not lists:
+            return total, {}
+        if len(lists) == 1:
+            names, node, add, rem = lists[0]
+            bodies = label_patch_json_batch(names, add, rem)
+            return total, {self.node_names[i]: b for i, b in zip(node.tolist(), bodies)}
+        # several groups: the listed nodes of all of them, each group's masks spread over that
+        # list, then per listed node the adds of all groups and the removes of all groups
+        listed = np.unique(np.concatenate([l[1] for l in lists]))
+        parts = []
+        for names, node, add, rem in lists:
+            at = np.searchsorted(listed, node)
+            a = np.zeros(len(listed), np.uint64)
+            r = np.zeros(len(listed), np.uint64)
+            a[at], r[at] = add, rem
+            parts.append((label_patch_json_batch(names, a, np.zeros_like(a)),
+                          label_patch_json_batch(names, np.zeros_like(r), r)))
+        bodies = {}
+        for k, i in enumerate(listed.tolist()):
+            pieces = [p[0][k][1:-1] for p in parts] + [p[1][k][1:-1] for p in parts]
+            bodies[self.node_names[i]] = b"[" + b",".join(x for x in pieces if x) + b"]"
+        return total, bodies
