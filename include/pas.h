@@ -164,7 +164,10 @@ int pas_tas_snapshot_info(const pas_ctx* ctx, uint64_t* gen, int32_t* n_nodes,
  * telemetrypolicy/api/v1alpha1/types.go:31-35), so core.EvaluateRule's CmpInt64
  * (operator.go:16-22) is exact against target * 10^scale (saturated past int64), and
  * OrderedList's Cmp (:37,39) is the integer order of one column: sub-milli metric values
- * evaluate on the device exactly.  Order this call after evaluations on
+ * evaluate on the device exactly.  Every int64 value is valid in a narrow
+ * column at any scale, -2^63 and 2^63 - 1 included, and every int64 target is compared
+ * exactly against it (at scale 0 nothing saturates: the target is compared as it is).
+ * Order this call after evaluations on
  * other streams that still read the snapshot, as a snapshot change; it is synchronous on
  * hip_stream (NULL: the context's stream). */
 int pas_tas_snapshot_set_scale(pas_ctx* ctx, uint64_t gen, int32_t n_metrics,

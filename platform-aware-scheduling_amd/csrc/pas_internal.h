@@ -112,11 +112,16 @@ __host__ __device__ __forceinline__ uint64_t word_mask(uint64_t bits, int64_t w,
 //   n_cards int32 [N], cap int64 [N][Q], used int64 [N][K][Q]
 // core.EvaluateRule's CmpInt64 (operator.go:16-22) against column m's fixed point: the
 // integer target * 10^scale[m] in *tm (0), or the saturation when that is past int64: +1 above
-// every value, -1 below every value.  A column at scale 0 never saturates
-// below: its values are ParseQuantity's, >= -(2^63 - 1).
+// every value, -1 below every value.  A column at scale 0 never saturates:
+// every int64 is a valid value there (-2^63 included), so the target is compared as it is,
+// and a caller that forms tm - 1 or tm + 1 guards tm == INT64_MIN / INT64_MAX itself.
 __device__ __forceinline__ int target_scaled(int64_t t, const int64_t* __restrict__ scale_tab,
                                              int32_t m, int64_t* tm) {
   const int64_t mult = scale_tab[2 * m], maxq = scale_tab[2 * m + 1];
+  if (mult == 1) {
+    *tm = t;
+    return 0;
+  }
   if (t > maxq) return 1;
   if (t < -maxq) return -1;
   *tm = t * mult;

@@ -43,3 +43,20 @@ def test_topk_card_tiers():
     tiers = [int(x) for x in re.findall(r"if \(a\.K <= (\d+)\)", m.group(0))]
     assert tiers == [8, 16], f"tas_gas_topk.hip: topk_dispatch tiers on a.K are {tiers}: {HINT}"
     assert "tas_gas_topk_kernel<PAS_GAS_MAX_CARDS, kMaxRes, kWide, kAfter>" in m.group(0), HINT
+
+
+def test_narrow_limit_shapes():
+    """tests/test_narrow_limits.py: pods of <= 32 and of 33..40 rules on either side of
+    kStageRules, 1 / 4 / 6 rules on the prioritize metric around kSkip, requests of 70 rules
+    past one kRuleTile."""
+    hint = "move the shapes of tests/test_narrow_limits.py with it"
+    topk, req = _source("tas_gas_topk.hip"), _source("tas_request_batch.hip")
+    for src, name, want in ((topk, "kPodLanes", 32), (topk, "kSkip", 4), (req, "kRuleTile", 64)):
+        m = re.search(rf"constexpr\s+int\s+{name}\s*=\s*(\d+)\s*;", src)
+        assert m, f"{name} is no longer a plain integer: {hint}"
+        assert int(m.group(1)) == want, f"{name} is {m.group(1)}, was {want}: {hint}"
+    # kStageRules is the pod's lane count, and the staging decision a ballot over the wave
+    for text in ("constexpr int kStageRules = kPodLanes;",
+                 "!__ballot(have && r1 - r0 > kStageRules)",
+                 "t0 < r1; t0 += kRuleTile"):
+        assert text in topk + req, f"the sources no longer hold `{text}`: {hint}"
