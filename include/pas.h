@@ -137,6 +137,35 @@ int pas_quantity_to_wide(const char* quantity, int64_t* whole, uint32_t* nano);
  * PAS_EINVAL if ParseQuantity would fail. */
 int pas_quantity_as_int64(const char* quantity, int64_t* out);
 
+/* One literal given as a byte span (no terminator; a byte 0 inside is PAS_EINVAL, as is an empty
+ * span), parsed by the fixed-width ParseQuantity the device runs per literal
+ * (csrc/quantity_fixed.h).  Host only.  Returns the status: PAS_OK, PAS_EINVAL or PAS_ENOTEXACT,
+ * those of pas_quantity_to_wide.  Outputs (each may be NULL):
+ *   whole, nano   pas_quantity_to_wide's pair (0, 0 unless PAS_OK)
+ *   decimals      pas_quantity_decimals, defined unless PAS_EINVAL ("1e19": 0)
+ *   fit           the largest places in 0..9 at which pas_quantity_to_scaled succeeds, or -1 if
+ *                 none does; never below decimals otherwise
+ * An e/E exponent is ParseInt's int64 truncated to int32, as in ParseQuantity, and every sum
+ * formed from it is exact: "1e2147483647" is PAS_ENOTEXACT, "1e-2147483647" is (0, 1). */
+int pas_quantity_parse_fixed(const char* bytes, int64_t len, int64_t* whole, uint32_t* nano,
+                             int32_t* decimals, int32_t* fit);
+
+/* A batch of literals parsed on the device, one lane per literal: literal i is
+ * bytes[lit_off[i] .. lit_off[i + 1]).  Per literal the outputs of pas_quantity_parse_fixed
+ * (whole, nano 0 unless its status is PAS_OK; an output array may be NULL).  The call returns
+ * PAS_OK whatever the literals' statuses are; n = 0 is valid.
+ * The host form stages its arrays and returns PAS_EINVAL unless lit_off starts at 0 and never
+ * decreases.  The _device form checks nothing of d_lit_off: both ends of every span are read
+ * clamped into [0, n_bytes] and the end not before the begin, so no offset takes the kernel
+ * outside d_bytes; a span that clamps to empty is PAS_EINVAL in its status.  It is asynchronous
+ * on hip_stream. */
+int pas_quantities_to_wide(pas_ctx* ctx, int64_t n, const int64_t* lit_off, const char* bytes,
+                           int64_t* whole, uint32_t* nano, int32_t* decimals, int32_t* status);
+int pas_quantities_to_wide_device(pas_ctx* ctx, int64_t n, int64_t n_bytes,
+                                  const int64_t* d_lit_off, const char* d_bytes,
+                                  int64_t* d_whole, uint32_t* d_nano, int32_t* d_decimals,
+                                  int32_t* d_status, void* hip_stream);
+
 /* ------------------------------------------------------------------------- */
 /* Telemetry Aware Scheduling                                                */
 /* ------------------------------------------------------------------------- */
@@ -216,6 +245,56 @@ int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_
                                         int32_t n_cols, const int32_t* cols,
                                         const int64_t* d_whole, const uint32_t* d_nano,
                                         const uint64_t* d_present, void* hip_stream);
+
+/* Column refresh from the Quantity literals themselves: a metric refresh as it arrives
+ * (NodeMetricsInfo, {node: resource.Quantity}, metrics/client.go:25-32) installs its columns in
+ * one call, parsed, scaled and encoded on the device.  The result is exactly what
+ * snapshot.tas_snapshot_from_metrics_wide + pas_tas_snapshot_update + pas_tas_snapshot_update_wide
+ * + pas_tas_snapshot_set_scale install.
+ *   cols, col_off  host arrays in both forms: column cols[c] (distinct, inside the snapshot, else
+ *                  PAS_EINVAL) is replaced by the entries [col_off[c], col_off[c + 1]), as
+ *                  updateMetric replaces a metric's whole node map; col_off starts at 0, never
+ *                  decreases, T = col_off[n_cols] <= INT32_MAX
+ *   entry_node [T] the node slot of each entry
+ *   lit_off [T+1], bytes   entry i's literal is bytes[lit_off[i] .. lit_off[i + 1])
+ *   kind_out [n_cols]      0 narrow, 1 wide (may be NULL)
+ *   scale_out [n_cols]     the column's recorded scale after the call (may be NULL)
+ *   bad_entry              see 1 (may be NULL)
+ * 1. Every entry of every column is parsed (pas_quantity_parse_fixed), whatever its node.  If
+ *    any status is not PAS_OK the call returns the status of the lowest such entry, writes that
+ *    entry's index to bad_entry and changes nothing: the snapshot stays valid at gen_from.
+ *    Otherwise bad_entry is -1.
+ * 2. The entries with 0 <= entry_node < n_nodes are in range; the others take no further part.
+ * 3. k = the most decimals among the column's in-range entries (0 if none), s = max(k, 3).
+ * 4. The column is narrow at scale s iff every in-range entry has fit >= s: it then holds
+ *    value * 10^s and its recorded scale becomes s.  Otherwise it is wide, holds the (whole,
+ *    nano) pairs, and its recorded scale stays what it was.
+ * 5. Presence is exactly the in-range nodes; a column with no in-range entry becomes empty,
+ *    narrow, milli.  A node listed twice in one column is PAS_EINVAL in the host form.  In the
+ *    _device form the entry with the highest index gives the value, while 3 and 4 count every
+ *    in-range entry.
+ * 6. The orders of these columns, and only these, are rebuilt; the narrow ones' scale table
+ *    entries are written on the same stream before; the generation is published once, as
+ *    gen_to, and no state between gen_from and gen_to is ever valid.  n_cols = 0 moves the
+ *    generation only.  PAS_ESTALE and PAS_ENOSNAP as pas_tas_snapshot_update.
+ * The narrow / wide marks and the scales are host state, decided from a per-column summary the
+ * call reads back: both forms are synchronous on hip_stream (the host form on the context's
+ * stream), like pas_tas_snapshot_set_scale and pas_tas_snapshot_reshape.  The _device form
+ * reads d_lit_off clamped as pas_quantities_to_wide_device does.  Workspace comes from the
+ * stream's slot and only grows. */
+int pas_tas_snapshot_update_quantities(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                       int32_t n_cols, const int32_t* cols,
+                                       const int64_t* col_off, const int32_t* entry_node,
+                                       const int64_t* lit_off, const char* bytes,
+                                       int32_t* kind_out, int32_t* scale_out,
+                                       int64_t* bad_entry);
+int pas_tas_snapshot_update_quantities_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                              int32_t n_cols, const int32_t* cols,
+                                              const int64_t* col_off, int64_t n_bytes,
+                                              const int32_t* d_entry_node,
+                                              const int64_t* d_lit_off, const char* d_bytes,
+                                              int32_t* kind_out, int32_t* scale_out,
+                                              int64_t* bad_entry, void* hip_stream);
 /* Change the shape of the resident snapshot on the device: node slots are appended and metric
  * columns added, dropped or moved, without a host copy and without a sort (the orders of a
  * kept column do not change; its rows are gathered into the new pitch and their pads

@@ -466,6 +466,146 @@ int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_
                                   pick_stream(ctx, hip_stream));
 }
 
+// ---- Quantity literals parsed on the device (tas_ingest.hip)
+
+// offsets [n + 1] of a host form: from 0 and non-decreasing
+static int check_offsets(pas_ctx* ctx, int64_t n, const int64_t* off, const std::string& what) {
+  if (!off || off[0] != 0) return set_error(ctx, PAS_EINVAL, what + ": offsets must start at 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return set_error(ctx, PAS_EINVAL, what + ": offsets decrease");
+  return PAS_OK;
+}
+
+int pas_quantities_to_wide(pas_ctx* ctx, int64_t n, const int64_t* lit_off, const char* bytes,
+                           int64_t* whole, uint32_t* nano, int32_t* decimals, int32_t* status) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_quantities_to_wide";
+  if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
+  if (n == 0) return PAS_OK;
+  int rc = check_offsets(ctx, n, lit_off, fn);
+  if (rc) return rc;
+  if (lit_off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  int64_t *d_off, *d_whole;
+  char* d_bytes;
+  uint32_t* d_nano;
+  int32_t *d_dec, *d_status;
+  st.in(d_off, lit_off, (size_t)n + 1);
+  st.in(d_bytes, bytes, (size_t)lit_off[n]);
+  st.out_opt(d_whole, whole, (size_t)n);
+  st.out_opt(d_nano, nano, (size_t)n);
+  st.out_opt(d_dec, decimals, (size_t)n);
+  st.out_opt(d_status, status, (size_t)n);
+  if ((rc = st.upload())) return rc;
+  rc = quantities_parse_launch(ctx, n, lit_off[n], d_off, d_bytes, d_whole, d_nano, d_dec,
+                               d_status, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+int pas_quantities_to_wide_device(pas_ctx* ctx, int64_t n, int64_t n_bytes,
+                                  const int64_t* d_lit_off, const char* d_bytes,
+                                  int64_t* d_whole, uint32_t* d_nano, int32_t* d_decimals,
+                                  int32_t* d_status, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_quantities_to_wide_device";
+  if (n < 0 || n_bytes < 0) return set_error(ctx, PAS_EINVAL, fn + ": n or n_bytes < 0");
+  if (n == 0) return PAS_OK;
+  if (!d_lit_off || (n_bytes > 0 && !d_bytes))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  int rc = activate(ctx);
+  if (rc) return rc;
+  return quantities_parse_launch(ctx, n, n_bytes, d_lit_off, d_bytes, d_whole, d_nano,
+                                 d_decimals, d_status, pick_stream(ctx, hip_stream));
+}
+
+// The checks both forms of pas_tas_snapshot_update_quantities share: the snapshot and its
+// generation, the columns, and col_off as a CSR of at most INT32_MAX entries.
+static int check_update_quantities(pas_ctx* ctx, uint64_t gen_from, int32_t n_cols,
+                                   const int32_t* cols, const int64_t* col_off,
+                                   const std::string& fn) {
+  int rc = check_update(ctx, gen_from, n_cols, cols, col_off, col_off, fn.c_str());
+  if (rc) return rc;
+  if (n_cols == 0) return PAS_OK;
+  if ((rc = check_offsets(ctx, n_cols, col_off, fn + ": col_off"))) return rc;
+  if (col_off[n_cols] > INT32_MAX)
+    return set_error(ctx, PAS_EINVAL, fn + ": more than INT32_MAX entries");
+  return PAS_OK;
+}
+
+int pas_tas_snapshot_update_quantities_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                              int32_t n_cols, const int32_t* cols,
+                                              const int64_t* col_off, int64_t n_bytes,
+                                              const int32_t* d_entry_node,
+                                              const int64_t* d_lit_off, const char* d_bytes,
+                                              int32_t* kind_out, int32_t* scale_out,
+                                              int64_t* bad_entry, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities_device";
+  if (bad_entry) *bad_entry = -1;
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
+  if (rc) return rc;
+  if (n_cols > 0 && col_off[n_cols] > 0 &&
+      (!d_entry_node || !d_lit_off || n_bytes < 0 || (n_bytes > 0 && !d_bytes)))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input or n_bytes < 0");
+  if ((rc = activate(ctx))) return rc;
+  return tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, n_bytes, d_entry_node,
+                                      d_lit_off, d_bytes, kind_out, scale_out, bad_entry,
+                                      pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_snapshot_update_quantities(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                       int32_t n_cols, const int32_t* cols,
+                                       const int64_t* col_off, const int32_t* entry_node,
+                                       const int64_t* lit_off, const char* bytes,
+                                       int32_t* kind_out, int32_t* scale_out,
+                                       int64_t* bad_entry) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities";
+  if (bad_entry) *bad_entry = -1;
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
+  if (rc) return rc;
+  const int64_t T = n_cols > 0 ? col_off[n_cols] : 0;
+  int64_t n_bytes = 0;
+  if (T > 0) {
+    if (!entry_node) return set_error(ctx, PAS_EINVAL, fn + ": null input");
+    if ((rc = check_offsets(ctx, T, lit_off, fn + ": lit_off"))) return rc;
+    n_bytes = lit_off[T];
+    if (n_bytes > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
+    // updateMetric replaces a node map: a node listed twice in one column is no map
+    const int32_t N = ctx->tas.n_nodes;
+    std::vector<uint64_t> seen((size_t)w64(N));
+    for (int32_t c = 0; c < n_cols; ++c) {
+      std::fill(seen.begin(), seen.end(), 0);
+      for (int64_t i = col_off[c]; i < col_off[c + 1]; ++i) {
+        const int32_t nd = entry_node[i];
+        if (nd < 0 || nd >= N) continue;
+        uint64_t& w = seen[(size_t)(nd >> 6)];
+        if ((w >> (nd & 63)) & 1ull)
+          return set_error(ctx, PAS_EINVAL, fn + ": column " + std::to_string(cols[c]) +
+                                                " lists node " + std::to_string(nd) + " twice");
+        w |= 1ull << (nd & 63);
+      }
+    }
+  }
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  int32_t* d_node;
+  int64_t* d_off;
+  char* d_bytes;
+  st.in(d_node, entry_node, (size_t)T);
+  st.in(d_off, lit_off, T > 0 ? (size_t)T + 1 : 0);
+  st.in(d_bytes, bytes, (size_t)n_bytes);
+  if ((rc = st.upload())) return rc;
+  rc = tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, n_bytes, d_node, d_off,
+                                    d_bytes, kind_out, scale_out, bad_entry, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
 int pas_tas_snapshot_drop(pas_ctx* ctx) {
   if (!ctx) return PAS_EINVAL;
   ctx->tas.valid = false;

@@ -245,7 +245,10 @@ enum SlotBuf {
   kBufPolicy = 5,
   kBufPatch = 6,      // segment counts and violated pairs of a patch list (tas_patches.hip)
   kBufPatchViol = 7,  // the sweep's bitmaps of pas_tas_deschedule_patches without viol_out
-  kSlotBufs = 8
+  // parsed entries, per-column summary and plan, and the column buffers of a refresh from
+  // Quantity literals (tas_ingest.hip)
+  kBufIngest = 8,
+  kSlotBufs = 9
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -409,6 +412,29 @@ int tas_snapshot_update(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_
 int tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const int32_t* cols,
                              const int64_t* d_whole, const uint32_t* d_nano,
                              const uint64_t* d_present, hipStream_t s);
+// Both in one step: rows [0, n_narrow) of d_vals / d_present replace the columns cols_narrow
+// as narrow columns, rows [n_narrow, n_narrow + n_wide) replace cols_wide as wide ones with
+// the same rows of d_nano (the two column lists are host arrays, together distinct).  The
+// snapshot is not valid between the two rebuilds; gen is published once, after both.
+int tas_snapshot_update_mixed(pas_ctx* ctx, uint64_t gen, int32_t n_narrow,
+                              const int32_t* cols_narrow, int32_t n_wide,
+                              const int32_t* cols_wide, const int64_t* d_vals,
+                              const uint32_t* d_nano, const uint64_t* d_present, hipStream_t s);
+// Quantity literals (tas_ingest.hip).  The parse of n literals bytes[off[i] .. off[i + 1]) on
+// device arrays, enqueued on s: offsets are read clamped into [0, n_bytes]; an output may be
+// null.
+int quantities_parse_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_lit_off,
+                            const char* d_bytes, int64_t* d_whole, uint32_t* d_nano,
+                            int32_t* d_decimals, int32_t* d_status, hipStream_t s);
+// pas_tas_snapshot_update_quantities_device past its argument checks (cols distinct and in
+// range, col_off a CSR from 0 with at most INT32_MAX entries): synchronous on s, workspace
+// from the slot of s.  A literal that does not parse: its status, *bad_entry its index,
+// nothing changed.
+int tas_update_quantities_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
+                                 const int32_t* cols, const int64_t* col_off, int64_t n_bytes,
+                                 const int32_t* d_entry_node, const int64_t* d_lit_off,
+                                 const char* d_bytes, int32_t* kind_out, int32_t* scale_out,
+                                 int64_t* bad_entry, hipStream_t s);
 // The resident snapshot gathered into storage of n_nodes_new (>= the resident count) x
 // n_metrics_new (tas_reshape.hip): new column m is old column src_col[m] or, for -1, empty
 // (src_col: host [n_metrics_new], distinct old columns or -1; the caller has checked it and

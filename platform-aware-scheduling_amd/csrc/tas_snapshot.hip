@@ -420,4 +420,19 @@ int tas_snapshot_update_wide(pas_ctx* ctx, uint64_t gen, int32_t n_cols, const i
   return update_columns<true>(ctx, gen, n_cols, cols, d_whole, d_nano, d_present, s);
 }
 
+int tas_snapshot_update_mixed(pas_ctx* ctx, uint64_t gen, int32_t n_narrow,
+                              const int32_t* cols_narrow, int32_t n_wide,
+                              const int32_t* cols_wide, const int64_t* d_vals,
+                              const uint32_t* d_nano, const uint64_t* d_present, hipStream_t s) {
+  TasSnapshot& t = ctx->tas;
+  const int64_t N = t.n_nodes, W = w64(N);
+  if (int rc = update_columns<false>(ctx, gen, n_narrow, cols_narrow, d_vals, nullptr, d_present,
+                                     s))
+    return rc;
+  if (n_wide == 0) return PAS_OK;
+  t.valid = false;  // half of the columns: not a state anything may read
+  return update_columns<true>(ctx, gen, n_wide, cols_wide, d_vals + n_narrow * N,
+                              d_nano + n_narrow * N, d_present + n_narrow * W, s);
+}
+
 }  // namespace pas

@@ -132,6 +132,17 @@ SIGNATURES = {
     "pas_tas_snapshot_update_wide": (c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P]),
     "pas_tas_snapshot_update_wide_device": (
         c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P]),
+    "pas_quantity_parse_fixed": (
+        c_int, [c_char_p, c_int64, POINTER(c_int64), POINTER(c_uint32), POINTER(c_int32),
+                POINTER(c_int32)]),
+    "pas_quantities_to_wide": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P]),
+    "pas_quantities_to_wide_device": (
+        c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "pas_tas_snapshot_update_quantities": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P, _P, _P, POINTER(c_int64)]),
+    "pas_tas_snapshot_update_quantities_device": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P,
+                POINTER(c_int64), _P]),
     "pas_tas_snapshot_wide_count": (c_int, [_P, POINTER(c_int32)]),
     "pas_tas_snapshot_reshape": (c_int, [_P, c_uint64, c_uint64, c_int32, c_int32, _P, _P]),
     "pas_tas_snapshot_compact": (c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P]),

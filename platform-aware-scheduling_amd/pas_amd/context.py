@@ -103,6 +103,21 @@ def quantity_decimals(q: str) -> int:
     return out.value
 
 
+def quantity_parse_fixed(q) -> Tuple[int, int, int, int, int]:
+    """(status, whole, nano, decimals, fit) of one literal (str or bytes, no terminator needed)
+    from the fixed-width parser the device runs (pas_quantity_parse_fixed): whole / nano as
+    quantity_to_wide, decimals as quantity_decimals, fit the largest places at which
+    quantity_to_scaled succeeds or -1.  The status is returned, not raised."""
+    b = q.encode() if isinstance(q, str) else bytes(q)
+    whole = c_int64()
+    nano = ctypes.c_uint32()
+    dec = ctypes.c_int32()
+    fit = ctypes.c_int32()
+    rc = _lib.load().pas_quantity_parse_fixed(b, len(b), byref(whole), byref(nano), byref(dec),
+                                              byref(fit))
+    return rc, whole.value, nano.value, dec.value, fit.value
+
+
 def quantity_as_int64(q: str) -> int:
     """resource.Quantity.AsInt64 with `ok` ignored (gpuscheduler/utils.go:23)."""
     out = c_int64()
@@ -282,6 +297,81 @@ class Context:
             self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None,
             _dptr(whole_t), _dptr(nano_t), _dptr(p_t), _stream(stream)),
             "pas_tas_snapshot_update_wide_device")
+
+    # ---- Quantity literals parsed on the device (csrc/tas_ingest.hip)
+    @staticmethod
+    def _blob(blob) -> np.ndarray:
+        b = np.frombuffer(bytes(blob), dtype=np.uint8)
+        return b if b.size else np.zeros(1, np.uint8)
+
+    def quantities_to_wide(self, lit_off, blob):
+        """(whole, nano, decimals, status) [n] of the literals blob[lit_off[i]:lit_off[i + 1]]
+        (pas_quantities_to_wide): per literal what quantity_parse_fixed gives, whole and nano 0
+        where the status is not PAS_OK."""
+        off = np.ascontiguousarray(lit_off, dtype=np.int64).reshape(-1)
+        n = len(off) - 1
+        whole = np.zeros(max(n, 1), np.int64)
+        nano = np.zeros(max(n, 1), np.uint32)
+        dec = np.zeros(max(n, 1), np.int32)
+        status = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.pas_quantities_to_wide(
+            self._h, n, _ptr(off), _ptr(self._blob(blob)), _ptr(whole), _ptr(nano), _ptr(dec),
+            _ptr(status)), "pas_quantities_to_wide")
+        return whole[:n], nano[:n], dec[:n], status[:n]
+
+    def quantities_to_wide_device(self, n: int, n_bytes: int, lit_off_t, bytes_t, whole_t, nano_t,
+                                  dec_t, status_t, stream=None):
+        self._check(self._l.pas_quantities_to_wide_device(
+            self._h, n, n_bytes, _dptr(lit_off_t), _dptr(bytes_t), _dptr(whole_t), _dptr(nano_t),
+            _dptr(dec_t), _dptr(status_t), _stream(stream)), "pas_quantities_to_wide_device")
+
+    def _update_quantities_result(self, rc: int, what: str, bad, kind, scale):
+        if rc != _lib.PAS_OK:
+            msg = self._l.pas_last_error(self._h)
+            err = PasError(rc, f"{what}: {msg.decode() if msg else ''}")
+            err.bad_entry = bad.value  # -1 unless a literal failed to parse
+            raise err
+        return kind, scale
+
+    def tas_snapshot_update_quantities(self, gen_from: int, gen_to: int, cols, col_off,
+                                       entry_node, lit_off, blob):
+        """Replace metric columns `cols` from Quantity literals (snapshot.pack_quantities):
+        column cols[c] takes the entries [col_off[c], col_off[c + 1]), entry i the literal
+        blob[lit_off[i]:lit_off[i + 1]] for node slot entry_node[i].  Returns (kind [n_cols]
+        0 narrow / 1 wide, scale [n_cols]) as the device chose them.  A literal that does not
+        parse raises PasError with its index in .bad_entry and changes nothing."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        c_off = np.ascontiguousarray(col_off, dtype=np.int64).reshape(-1)
+        node = np.ascontiguousarray(entry_node, dtype=np.int32).reshape(-1)
+        l_off = np.ascontiguousarray(lit_off, dtype=np.int64).reshape(-1)
+        assert len(c_off) == len(cols) + 1 and len(l_off) == len(node) + 1
+        kind = np.zeros(max(len(cols), 1), np.int32)
+        scale = np.zeros(max(len(cols), 1), np.int32)
+        bad = c_int64(-1)
+        rc = self._l.pas_tas_snapshot_update_quantities(
+            self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None, _ptr(c_off),
+            _ptr(node) if node.size else None, _ptr(l_off), _ptr(self._blob(blob)), _ptr(kind),
+            _ptr(scale), byref(bad))
+        return self._update_quantities_result(rc, "pas_tas_snapshot_update_quantities", bad,
+                                              kind[:len(cols)], scale[:len(cols)])
+
+    def tas_snapshot_update_quantities_device(self, gen_from: int, gen_to: int, cols, col_off,
+                                              n_bytes: int, entry_node_t, lit_off_t, bytes_t,
+                                              stream=None):
+        """The same with entry_node / lit_off / bytes on the device (cols and col_off stay host
+        arrays).  Synchronous on the stream."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        c_off = np.ascontiguousarray(col_off, dtype=np.int64).reshape(-1)
+        assert len(c_off) == len(cols) + 1
+        kind = np.zeros(max(len(cols), 1), np.int32)
+        scale = np.zeros(max(len(cols), 1), np.int32)
+        bad = c_int64(-1)
+        rc = self._l.pas_tas_snapshot_update_quantities_device(
+            self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None, _ptr(c_off),
+            n_bytes, _dptr(entry_node_t), _dptr(lit_off_t), _dptr(bytes_t), _ptr(kind),
+            _ptr(scale), byref(bad), _stream(stream))
+        return self._update_quantities_result(rc, "pas_tas_snapshot_update_quantities_device",
+                                              bad, kind[:len(cols)], scale[:len(cols)])
 
     def tas_snapshot_wide_count(self) -> int:
         """Number of wide columns of the resident snapshot."""

@@ -107,6 +107,34 @@ def tas_snapshot_from_metrics_wide(metrics: Mapping[str, Mapping[str, str]],
     return v, present, scale, wide
 
 
+def pack_literals(metrics: Mapping[str, Mapping[str, str]], order: Sequence[str]):
+    """(col_off int64 [len(order) + 1], nodes, lit_off int64 [T + 1], blob bytes): the maps of
+    the metrics `order` names, one entry per (node, quantity) in the maps' own order, the
+    literals end to end in one blob and the entries' node names in the list `nodes`.  Nothing
+    is parsed."""
+    col_off = np.zeros(len(order) + 1, np.int64)
+    nodes: List[str] = []
+    lits: List[bytes] = []
+    for j, name in enumerate(order):
+        mp = metrics.get(name) or {}
+        nodes.extend(mp)
+        lits.extend(q.encode() if isinstance(q, str) else bytes(q) for q in mp.values())
+        col_off[j + 1] = len(nodes)
+    lit_off = np.zeros(len(lits) + 1, np.int64)
+    np.cumsum(np.fromiter(map(len, lits), np.int64, len(lits)), out=lit_off[1:])
+    return col_off, nodes, lit_off, b"".join(lits)
+
+
+def pack_quantities(metrics: Mapping[str, Mapping[str, str]], node_index: Mapping[str, int],
+                    order: Sequence[str]):
+    """(col_off, entry_node int32 [T], lit_off, blob) for Context.tas_snapshot_update_quantities:
+    pack_literals with every entry's node name looked up in node_index (-1 for a name without a
+    slot: its literal is still validated, and it takes no part in the column).  No parsing."""
+    col_off, nodes, lit_off, blob = pack_literals(metrics, order)
+    entry_node = np.fromiter((node_index.get(n, -1) for n in nodes), np.int32, len(nodes))
+    return col_off, entry_node, lit_off, blob
+
+
 def go_sort_strings(names):
     """sort.Strings: bytewise order of the UTF-8 encodings ("card10" < "card2")."""
     return sorted(names, key=lambda s: s.encode())

@@ -16,8 +16,9 @@ from typing import Callable, Dict, List, Mapping, Optional, Sequence, Set
 
 import numpy as np
 
+from . import _lib
 from .context import quantity_to_wide, w64
-from .snapshot import tas_snapshot_from_metrics_wide
+from .snapshot import pack_literals, tas_snapshot_from_metrics_wide
 
 METRIC_GROWTH = 8  # columns added when no free column is left
 
@@ -74,12 +75,24 @@ class TasCache:
     that have no slot there, listing them in skipped_nodes.  Such a node fails the GAS fit
     anyway (FetchNode error); the TAS-only verbs treat it as a node unknown to the snapshot
     (it passes the filter and is left out of the prioritize list).  A skipped entry is
-    installed by the first refresh of its metric after the name got a slot."""
+    installed by the first refresh of its metric after the name got a slot.
+
+    device_ingest=True hands the Quantity strings to the device as they are
+    (pas_tas_snapshot_update_quantities): no value is parsed on the host.  One write or refresh
+    then issues one pas_quantities_to_wide over all its literals, before anything changes (a
+    literal that cannot be held raises PasError naming the metric and the literal and leaves
+    cache and snapshot as they were, as above), at most one reshape, and one
+    pas_tas_snapshot_update_quantities for all its columns, in place of the narrow update, the
+    wide update and the set_scale; `scale` and `wide` follow what that call reports.  The
+    snapshot it installs is the same."""
 
     def __init__(self, ctx, gen: int, node_names: Sequence[Optional[str]],
-                 metric_names: Sequence[Optional[str]], scale=None, wide=None, slots=None):
+                 metric_names: Sequence[Optional[str]], scale=None, wide=None, slots=None,
+                 device_ingest: bool = False):
         self.ctx, self.gen = ctx, gen
         self.slots = slots
+        self.device_ingest = bool(device_ingest)
+        self._undo: Dict[str, tuple] = {}  # device_ingest: data a pending write replaced
         self.node_names: List[Optional[str]] = list(node_names)
         self.node_index: Dict[str, int] = {n: i for i, n in enumerate(node_names)
                                            if n is not None}
@@ -96,7 +109,8 @@ class TasCache:
     @classmethod
     def from_metrics(cls, ctx, gen: int, metrics: Mapping[str, Mapping[str, str]],
                      node_names: Optional[Sequence[str]] = None, spare_nodes: int = 0,
-                     spare_metrics: int = 0, slots=None) -> "TasCache":
+                     spare_metrics: int = 0, slots=None,
+                     device_ingest: bool = False) -> "TasCache":
         """A cache over a first snapshot, uploaded as generation gen: every entry of `metrics`
         as write_metric would take it (a non-empty map is data without a registration, an
         empty one a registration without data), over node_names (default: the maps' nodes in
@@ -116,7 +130,8 @@ class TasCache:
         scale = np.concatenate([scale, np.full(extra, 3, np.int32)])
         ctx.tas_snapshot_set_wide(gen, v, p, scale, wide)
         cols = held + [None] * extra
-        self = cls(ctx, gen, names, cols, scale, [c in wide for c in range(len(cols))], slots)
+        self = cls(ctx, gen, names, cols, scale, [c in wide for c in range(len(cols))], slots,
+                   device_ingest)
         for name, mp in metrics.items():
             if mp:
                 self.data[name] = dict(mp)
@@ -209,8 +224,11 @@ class TasCache:
         if not data:  # nilPayloadCheck: the payload is nil, the cache keeps what it has
             self._register(name)
             return
-        for q in data.values():  # nothing changes when a value cannot be held
-            quantity_to_wide(q)
+        if self.device_ingest:  # checked on the device, by _flush, before anything else changes
+            self._undo.setdefault(name, (name in self.data, self.data.get(name)))
+        else:
+            for q in data.values():  # nothing changes when a value cannot be held
+                quantity_to_wide(q)
         self.data[name] = dict(data)
         pending[name] = self.data[name]
 
@@ -220,7 +238,8 @@ class TasCache:
 
     def _flush(self, pending: Dict[str, Dict[str, str]]):
         """The device calls of one write or refresh: reshape, narrow update, wide update,
-        set_scale, each at most once."""
+        set_scale, each at most once (device_ingest: see _flush_literals)."""
+        packed = self._check_literals(pending) if self.device_ingest and pending else None
         n_old, m_old = len(self.node_names), len(self.metric_names)
         # node slots
         if self.slots is not None:
@@ -262,6 +281,9 @@ class TasCache:
             self.gen += 1
         if not pending:
             return
+        if packed is not None:
+            self._flush_literals(*packed)
+            return
         # the columns, encoded as a from-scratch build encodes them
         order = sorted(pending, key=self.metric_index.__getitem__)
         v, p, scale, wide = tas_snapshot_from_metrics_wide(pending, self.node_names, order)
@@ -286,3 +308,49 @@ class TasCache:
                 rescale = True
         if rescale:
             self.ctx.tas_snapshot_set_scale(self.gen, self.scale)
+
+    # ------------------------------------------------------------ device_ingest
+    def _literal_error(self, code: int, at: int, order, col_off, nodes, lit_off, blob):
+        j = int(np.searchsorted(col_off, at, side="right")) - 1
+        lit = blob[int(lit_off[at]):int(lit_off[at + 1])].decode(errors="replace")
+        what = ("the integer part of {!r} is outside int64" if code == _lib.PAS_ENOTEXACT
+                else "{!r} is no resource.Quantity").format(lit)
+        return _lib.PasError(code, f"metric {order[j]!r}, node {nodes[at]!r}: {what}")
+
+    def _check_literals(self, pending):
+        """The pending maps packed (snapshot.pack_literals, in pending's own order) and every
+        literal parsed once on the device.  A literal that cannot be held: the maps the pending
+        writes replaced are put back, nothing else has changed yet, PasError."""
+        order = list(pending)
+        col_off, nodes, lit_off, blob = pack_literals(pending, order)
+        status = self.ctx.quantities_to_wide(lit_off, blob)[3]
+        bad = np.flatnonzero(status)
+        undo, self._undo = self._undo, {}
+        if bad.size:
+            for name, (had, old) in undo.items():
+                if had:
+                    self.data[name] = old
+                else:
+                    self.data.pop(name, None)
+            at = int(bad[0])
+            raise self._literal_error(int(status[at]), at, order, col_off, nodes, lit_off, blob)
+        return order, col_off, nodes, lit_off, blob
+
+    def _flush_literals(self, order, col_off, nodes, lit_off, blob):
+        """One pas_tas_snapshot_update_quantities for the pending columns (slots and columns
+        are assigned, the snapshot has its new shape)."""
+        index = self.node_index
+        entry_node = np.fromiter((index.get(n, -1) for n in nodes), np.int32, len(nodes))
+        cols = [self.metric_index[name] for name in order]
+        try:
+            kind, scale = self.ctx.tas_snapshot_update_quantities(
+                self.gen, self.gen + 1, cols, col_off, entry_node, lit_off, blob)
+        except _lib.PasError as e:  # (_check_literals has parsed them all: not expected)
+            at = getattr(e, "bad_entry", -1)
+            if at < 0:
+                raise
+            raise self._literal_error(e.code, at, order, col_off, nodes, lit_off, blob) from None
+        self.gen += 1
+        for col, k, s in zip(cols, kind, scale):
+            self.wide[col] = bool(k)
+            self.scale[col] = int(s)
