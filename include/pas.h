@@ -1447,6 +1447,100 @@ int pas_decode_pod_requests(const char* pod, int64_t len, int32_t n_kinds,
                             uint32_t* req_mask, int32_t* n_containers, int32_t* n_unknown);
 
 /* ------------------------------------------------------------------------- */
+/* Resident node-name table: names resolved to slots on the device           */
+/* ------------------------------------------------------------------------- */
+
+/* The reference keys everything by node name (NodeMetricsInfo map[string]NodeMetric,
+ * metrics/client.go:25-32; args.NodeNames, gpuscheduler/scheduler.go:455-470); node slots exist
+ * only here.  The context holds one table from names to slots for all its snapshots (combined
+ * contexts share one slot numbering): n_slots slots, each holding one name or spare.  Names are
+ * opaque byte strings of any length, bytes >= 0x80 and a byte 0 inside included; the empty name
+ * marks a spare slot and so never has a slot itself.  A batch of names is a CSR like a batch of
+ * literals: name i is bytes[name_off[i] .. name_off[i + 1]); host forms return PAS_EINVAL
+ * unless name_off starts at 0 and never decreases, _device forms read both ends of every span
+ * clamped into [0, n_bytes] and the end not before the begin, as pas_quantities_to_wide_device
+ * does.  Every entry point answers PAS_ENOSNAP without a table.  Storage only grows and is
+ * freed with the context.  PAS_ABI_VERSION is unchanged: additions only.
+ *
+ * The one hash of names, on the host and on the device (csrc/name_hash.h): the low bits select
+ * the home bucket of the table (a power of two >= 2 * n_slots buckets, at least 2, linear
+ * probing with wraparound), the high 32 bits are the tag stored beside the slot.  A hit is
+ * decided only by comparing all bytes, never by hash bits. */
+uint64_t pas_name_hash(const char* bytes, int64_t len);
+
+/* Install the table: slot s holds bytes[name_off[s] .. name_off[s + 1]), an empty span is a
+ * spare slot.  Host arrays, synchronous on the context's stream; the hash is built on the
+ * device.  A name in two slots is PAS_EINVAL, the message naming the lowest slot whose name
+ * also stands in a lower slot; after any error the previous table, if any, is still valid. */
+int pas_names_set(pas_ctx* ctx, int32_t n_slots, const int64_t* name_off, const char* bytes);
+/* Slots, named slots and the bytes of all names (each output may be NULL). */
+int pas_names_info(const pas_ctx* ctx, int32_t* n_slots, int32_t* n_named, int64_t* n_bytes);
+/* The names packed in slot order, whatever the table's internal order: name_off_out
+ * [n_slots + 1] always, bytes_out [cap] when cap >= n_bytes, else PAS_ECAPACITY (the size
+ * needed is name_off_out[n_slots], and in the message). */
+int pas_names_get(pas_ctx* ctx, int64_t* name_off_out, char* bytes_out, int64_t cap);
+int pas_names_drop(pas_ctx* ctx);
+
+/* slot_out[i] = the slot of name i, or -1 (an empty name: -1).  Reads the table only; n = 0 is
+ * valid.  The _device form is asynchronous on hip_stream; on a stream other than that of the
+ * last table change it waits for that change's event, not for the host. */
+int pas_names_resolve(pas_ctx* ctx, int64_t n, const int64_t* name_off, const char* bytes,
+                      int32_t* slot_out);
+int pas_names_resolve_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_name_off,
+                             const char* d_bytes, int32_t* d_slot_out, void* hip_stream);
+
+/* Lookup plus first-seen assignment (n <= INT32_MAX).  The distinct non-empty names without a
+ * slot, in order of first appearance among the entries, receive the spare slots in ascending
+ * slot index.  new_entry_out / new_slot_out [new_cap] (host arrays in both forms) list, in
+ * ascending entry index, the first appearance of each new name and the slot it got; *n_new_out
+ * is the number of distinct new names.  If that exceeds min(spare slots, new_cap) the call
+ * returns PAS_ECAPACITY with *n_new_out set, changes nothing, and slot_out holds the plain
+ * lookups.  Otherwise the names are appended and inserted and every entry's slot is written,
+ * repeats of a new name included.  slot_out (d_slot_out) may be NULL.  Synchronous on the
+ * stream: it is a table change, ordered by the caller after readers on other streams like
+ * every snapshot change.  With no new name it is one lookup pass and the read-back of one
+ * word.  No output depends on the order in which the device happens to process the entries. */
+int pas_names_assign(pas_ctx* ctx, int64_t n, const int64_t* name_off, const char* bytes,
+                     int32_t* slot_out, int64_t new_cap, int32_t* new_entry_out,
+                     int32_t* new_slot_out, int64_t* n_new_out);
+int pas_names_assign_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_name_off,
+                            const char* d_bytes, int32_t* d_slot_out, int64_t new_cap,
+                            int32_t* new_entry_out, int32_t* new_slot_out, int64_t* n_new_out,
+                            void* hip_stream);
+
+/* Append spare slots (a smaller n_slots_new is PAS_EINVAL); the hash is rebuilt on the device
+ * when its load factor would pass 1/2.  Synchronous on hip_stream. */
+int pas_names_resize(pas_ctx* ctx, int32_t n_slots_new, void* hip_stream);
+/* Renumber the slots with the map of pas_tas_snapshot_compact / pas_gas_snapshot_compact: new
+ * slot j holds the name of old slot src_slot[j], or is spare for -1; the entries >= 0 are
+ * strictly increasing and below n_slots, anything else is PAS_EINVAL.  The names of the old
+ * slots the map does not list leave the table.  The pool is gathered and the hash rebuilt on
+ * the device.  Synchronous on hip_stream. */
+int pas_names_remap(pas_ctx* ctx, int32_t n_slots_new, const int32_t* src_slot,
+                    void* hip_stream);
+
+/* pas_tas_snapshot_update_quantities with each entry's node given by name: entry i's node is
+ * the slot of name_bytes[name_off[i] .. name_off[i + 1]) (lookup only: the table does not
+ * change).  A name without a slot is entry node -1: its literal is still validated and it
+ * takes no further part (rules 1-2 of that call), like a slot >= the snapshot's n_nodes.
+ * Both forms read rule 5 as the _device form does: the highest entry index of a (column, node)
+ * gives the value.  *n_unknown_out (may be NULL) = the entries whose name has no slot.
+ * Everything else, the synchronisation included, is that call's. */
+int pas_tas_snapshot_update_quantities_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                             int32_t n_cols, const int32_t* cols,
+                                             const int64_t* col_off, const int64_t* name_off,
+                                             const char* name_bytes, const int64_t* lit_off,
+                                             const char* bytes, int32_t* kind_out,
+                                             int32_t* scale_out, int64_t* bad_entry,
+                                             int64_t* n_unknown_out);
+int pas_tas_snapshot_update_quantities_names_device(
+    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_cols, const int32_t* cols,
+    const int64_t* col_off, int64_t n_name_bytes, const int64_t* d_name_off,
+    const char* d_name_bytes, int64_t n_bytes, const int64_t* d_lit_off, const char* d_bytes,
+    int32_t* kind_out, int32_t* scale_out, int64_t* bad_entry, int64_t* n_unknown_out,
+    void* hip_stream);
+
+/* ------------------------------------------------------------------------- */
 /* Instrumentation                                                           */
 /* ------------------------------------------------------------------------- */
 

@@ -1,0 +1,855 @@
+// name_table.hip — the resident node-name table: names resolved to slots on the device.
+//
+// The reference keys everything by node name (NodeMetricsInfo map[string]NodeMetric,
+// telemetry-aware-scheduling/pkg/metrics/client.go:25-32; args.NodeNames,
+// gpu-aware-scheduling/pkg/gpuscheduler/scheduler.go:455-470); slots exist only here.  The
+// table (NameTable, pas_internal.h) maps one to the other beside the snapshots it indexes:
+//   names_lookup    one lane per name: hash (name_hash.h), probe from the home bucket with
+//                   wraparound, compare all bytes against the pool on a tag match
+//   names_insert    one lane per slot: CAS claims an empty bucket, atomicMin keeps the lowest
+//                   slot of a name (pas_names_set's duplicate check: a slot that does not find
+//                   itself afterwards is a loser and flags itself)
+//   assignment      (a) lookup, (b) the unknown entries deduped through a scratch table whose
+//                   word carries the entry index (atomicMin: the first appearance, whatever the
+//                   arrival order), (c) the firsts and the spare slots ranked by scans, the
+//                   k-th first takes the k-th spare slot, (d) the new names appended to the
+//                   pool at scanned offsets and inserted, (e) the repeats take their first's
+//                   slot
+// The names are adjacent in one blob, so neighbouring lanes read neighbouring bytes, as
+// parse_literals does.  The table's layout may depend on arrival order; no output does.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "host_staging.h"
+#include "name_hash.h"
+#include "pas_internal.h"
+
+namespace pas {
+namespace {
+
+constexpr int kTpb = 256;
+constexpr unsigned long long kEmpty = ~0ull;
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTpb - 1) / kTpb); }
+
+struct NameView {
+  int64_t mask;  // buckets - 1
+  unsigned long long* table;
+  int64_t* beg;
+  int64_t* len;
+  char* pool;
+};
+
+inline NameView view_of(const NameTable& t) {
+  return NameView{t.buckets - 1, t.table, t.beg, t.len, t.pool};
+}
+
+inline int64_t buckets_for(int64_t n_slots) {
+  int64_t b = 2;
+  while (b < 2 * n_slots) b <<= 1;
+  return b;
+}
+
+__device__ __forceinline__ int64_t clamp_off(int64_t v, int64_t n) {
+  return v < 0 ? 0 : v > n ? n : v;
+}
+
+// Entry i of a batch: bytes[*b .. *b + return), both ends clamped into [0, n_bytes] and the
+// end not before the begin, as parse_literals reads its literals.
+__device__ __forceinline__ int64_t entry_span(const int64_t* __restrict__ off, int64_t n_bytes,
+                                              int64_t i, int64_t* b) {
+  *b = clamp_off(off[i], n_bytes);
+  const int64_t e = clamp_off(off[i + 1], n_bytes);
+  return e < *b ? 0 : e - *b;
+}
+
+__device__ __forceinline__ bool bytes_equal(const char* __restrict__ a,
+                                            const char* __restrict__ b, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (a[i] != b[i]) return false;
+  return true;
+}
+
+__device__ __forceinline__ unsigned long long make_word(uint64_t h, uint32_t low) {
+  return ((unsigned long long)name_tag(h) << 32) | low;
+}
+
+// The slot of the name p[0 .. n) with hash h, or -1.  The table is at most half full, so a
+// probe always ends at an empty bucket.
+__device__ __forceinline__ int32_t table_find(const NameView& t, const char* __restrict__ p,
+                                              int64_t n, uint64_t h) {
+  if (n == 0) return -1;
+  for (int64_t b = (int64_t)h & t.mask;; b = (b + 1) & t.mask) {
+    const unsigned long long w = t.table[b];
+    if (w == kEmpty) return -1;
+    if ((uint32_t)(w >> 32) != name_tag(h)) continue;
+    const int32_t s = (int32_t)(uint32_t)w;
+    if (t.len[s] == n && bytes_equal(t.pool + t.beg[s], p, n)) return s;
+  }
+}
+
+__global__ void names_lookup(int64_t n, int64_t n_bytes, const int64_t* __restrict__ off,
+                             const char* __restrict__ bytes, NameView t,
+                             int32_t* __restrict__ slot, uint64_t* __restrict__ hash,
+                             uint32_t* unknown, int count_empty) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  bool miss = false;
+  if (i < n) {
+    int64_t b;
+    const int64_t len = entry_span(off, n_bytes, i, &b);
+    const uint64_t h = name_hash(bytes + b, len);
+    const int32_t s = table_find(t, bytes + b, len, h);
+    slot[i] = s;
+    if (hash) hash[i] = h;
+    miss = s < 0 && (len > 0 || count_empty);
+  }
+  if (!unknown) return;  // (uniform)
+  const unsigned long long m = __ballot(miss);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(unknown, (uint32_t)__popcll(m));
+}
+
+// Slot list[i] (null: slot i) into the table.  A bucket belongs to the name that claimed it;
+// slots of the same name only lower its word, so it keeps the lowest of them.
+__global__ void names_insert(int64_t n, const int32_t* __restrict__ list, NameView t) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (i >= n) return;
+  const int32_t s = list ? list[i] : (int32_t)i;
+  const int64_t len = t.len[s];
+  if (len == 0) return;
+  const char* p = t.pool + t.beg[s];
+  const uint64_t h = name_hash(p, len);
+  const unsigned long long word = make_word(h, (uint32_t)s);
+  for (int64_t b = (int64_t)h & t.mask;; b = (b + 1) & t.mask) {
+    unsigned long long w = *(volatile unsigned long long*)&t.table[b];
+    if (w == kEmpty) {
+      w = atomicCAS(&t.table[b], kEmpty, word);
+      if (w == kEmpty) return;
+    }
+    if ((uint32_t)(w >> 32) != name_tag(h)) continue;
+    const int32_t s2 = (int32_t)(uint32_t)w;
+    if (s2 == s) return;
+    if (t.len[s2] == len && bytes_equal(t.pool + t.beg[s2], p, len)) {
+      atomicMin(&t.table[b], word);
+      return;
+    }
+  }
+}
+
+// ctr[0] = the lowest slot that does not find itself (its name stands in a lower slot)
+__global__ void names_flag_losers(int64_t n_slots, NameView t, int32_t* ctr) {
+  const int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (s >= n_slots) return;
+  const int64_t len = t.len[s];
+  if (len == 0) return;
+  const char* p = t.pool + t.beg[s];
+  if (table_find(t, p, len, name_hash(p, len)) != (int32_t)s) atomicMin(&ctr[0], (int32_t)s);
+}
+
+// beg / len of a set from its CSR offsets; ctr[1] += the named slots
+__global__ void names_spans(int64_t n_slots, const int64_t* __restrict__ off,
+                            int64_t* __restrict__ beg, int64_t* __restrict__ len, int32_t* ctr) {
+  const int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  bool named = false;
+  if (s < n_slots) {
+    beg[s] = off[s];
+    len[s] = off[s + 1] - off[s];
+    named = off[s + 1] > off[s];
+  }
+  const unsigned long long m = __ballot(named);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&ctr[1], (int32_t)__popcll(m));
+}
+
+// The lengths of a remapped table: new slot j holds old slot src[j]; ctr[1] += the named ones
+__global__ void names_remap_lens(int64_t n_new, const int32_t* __restrict__ src,
+                                 const int64_t* __restrict__ len_old,
+                                 int64_t* __restrict__ len_new, int32_t* ctr) {
+  const int64_t j = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  bool named = false;
+  if (j < n_new) {
+    const int32_t s = src[j];
+    const int64_t len = s >= 0 ? len_old[s] : 0;
+    len_new[j] = len;
+    named = len > 0;
+  }
+  const unsigned long long m = __ballot(named);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&ctr[1], (int32_t)__popcll(m));
+}
+
+// Name j (old slot src[j], null: slot j) copied to its scanned place dst + beg_new[j]
+__global__ void names_gather(int64_t n, const int32_t* __restrict__ src,
+                             const int64_t* __restrict__ beg_old,
+                             const int64_t* __restrict__ len_old,
+                             const char* __restrict__ pool_old,
+                             const int64_t* __restrict__ beg_new, char* __restrict__ dst) {
+  const int64_t j = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (j >= n) return;
+  const int64_t s = src ? src[j] : j;
+  if (s < 0) return;
+  const int64_t len = len_old[s];
+  const char* p = pool_old + beg_old[s];
+  char* q = dst + beg_new[j];
+  for (int64_t k = 0; k < len; ++k) q[k] = p[k];
+}
+
+// ---- assignment
+
+// (b) every unknown entry into the scratch table (word = tag << 32 | entry index)
+__global__ void assign_dedupe(int64_t n, int64_t n_bytes, const int64_t* __restrict__ off,
+                              const char* __restrict__ bytes, const int32_t* __restrict__ slot,
+                              const uint64_t* __restrict__ hash, int64_t mask,
+                              unsigned long long* scratch) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (i >= n || slot[i] >= 0) return;
+  int64_t b0;
+  const int64_t len = entry_span(off, n_bytes, i, &b0);
+  if (len == 0) return;
+  const uint64_t h = hash[i];
+  const unsigned long long word = make_word(h, (uint32_t)i);
+  for (int64_t b = (int64_t)h & mask;; b = (b + 1) & mask) {
+    unsigned long long w = *(volatile unsigned long long*)&scratch[b];
+    if (w == kEmpty) {
+      w = atomicCAS(&scratch[b], kEmpty, word);
+      if (w == kEmpty) return;
+    }
+    if ((uint32_t)(w >> 32) != name_tag(h)) continue;
+    const int64_t j = (int64_t)(uint32_t)w;
+    if (j == i) return;
+    int64_t bj;
+    if (entry_span(off, n_bytes, j, &bj) == len && bytes_equal(bytes + bj, bytes + b0, len)) {
+      atomicMin(&scratch[b], word);
+      return;
+    }
+  }
+}
+
+// (c) first_of[i] = the first appearance of an unknown entry's name (-1: known or empty);
+// flag / flen [n + 1] = 1 / the name's length at the firsts, 0 elsewhere (the scans' inputs)
+__global__ void assign_firsts(int64_t n, int64_t n_bytes, const int64_t* __restrict__ off,
+                              const char* __restrict__ bytes, const int32_t* __restrict__ slot,
+                              const uint64_t* __restrict__ hash, int64_t mask,
+                              const unsigned long long* __restrict__ scratch,
+                              int32_t* __restrict__ first_of, uint32_t* __restrict__ flag,
+                              int64_t* __restrict__ flen) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (i > n) return;
+  int32_t first = -1;
+  int64_t len = 0, b0 = 0;
+  if (i < n && slot[i] < 0) len = entry_span(off, n_bytes, i, &b0);
+  if (len > 0) {
+    const uint64_t h = hash[i];
+    for (int64_t b = (int64_t)h & mask;; b = (b + 1) & mask) {
+      const unsigned long long w = scratch[b];
+      if (w == kEmpty) break;  // (every unknown entry was inserted: not reached)
+      if ((uint32_t)(w >> 32) != name_tag(h)) continue;
+      const int64_t j = (int64_t)(uint32_t)w;
+      int64_t bj;
+      if (j == i ||
+          (entry_span(off, n_bytes, j, &bj) == len && bytes_equal(bytes + bj, bytes + b0, len))) {
+        first = (int32_t)j;
+        break;
+      }
+    }
+  }
+  const bool is_first = first == (int32_t)i && i < n;
+  if (i < n) first_of[i] = first;
+  flag[i] = is_first ? 1u : 0u;
+  flen[i] = is_first ? len : 0;
+}
+
+__global__ void names_spare_flags(int64_t n_slots, const int64_t* __restrict__ len,
+                                  uint32_t* __restrict__ flag) {
+  const int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (s <= n_slots) flag[s] = s < n_slots && len[s] == 0 ? 1u : 0u;
+}
+
+// the first n_new spare slots in ascending order
+__global__ void assign_spares(int64_t n_slots, uint32_t n_new, const uint32_t* __restrict__ flag,
+                              const uint32_t* __restrict__ rank, int32_t* __restrict__ spare) {
+  const int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (s < n_slots && flag[s] && rank[s] < n_new) spare[rank[s]] = (int32_t)s;
+}
+
+// (d) the k-th first takes the k-th spare slot; its name goes to the pool at its scanned offset
+__global__ void assign_commit(int64_t n, int64_t n_bytes, const int64_t* __restrict__ off,
+                              const char* __restrict__ bytes, const uint32_t* __restrict__ flag,
+                              const uint32_t* __restrict__ rank, const int64_t* __restrict__ fpos,
+                              const int32_t* __restrict__ spare, int64_t pool_used, NameView t,
+                              int32_t* __restrict__ slot, int32_t* __restrict__ new_entry,
+                              int32_t* __restrict__ new_slot) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const uint32_t k = rank[i];
+  const int32_t s = spare[k];
+  int64_t b;
+  const int64_t len = entry_span(off, n_bytes, i, &b);
+  const int64_t at = pool_used + fpos[i];
+  for (int64_t j = 0; j < len; ++j) t.pool[at + j] = bytes[b + j];
+  t.beg[s] = at;
+  t.len[s] = len;
+  slot[i] = s;
+  new_entry[k] = (int32_t)i;
+  new_slot[k] = s;
+}
+
+// (e) the repeats of a new name
+__global__ void assign_repeats(int64_t n, const int32_t* __restrict__ first_of,
+                               const uint32_t* __restrict__ flag, int32_t* slot) {
+  const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
+  if (i >= n || flag[i] || first_of[i] < 0) return;
+  slot[i] = slot[first_of[i]];  // (a first's entry: written by assign_commit, not here)
+}
+
+template <typename T>
+int scan_size(pas_ctx* ctx, size_t n, size_t* bytes) {
+  *bytes = 0;
+  PAS_HIP(ctx, rocprim::exclusive_scan(nullptr, *bytes, (const T*)nullptr, (T*)nullptr, T(0), n,
+                                       rocprim::plus<T>(), (hipStream_t) nullptr));
+  return PAS_OK;
+}
+
+template <typename T>
+int scan_run(pas_ctx* ctx, void* tmp, size_t bytes, const T* in, T* out, size_t n,
+             hipStream_t s) {
+  PAS_HIP(ctx, rocprim::exclusive_scan(tmp, bytes, in, out, T(0), n, rocprim::plus<T>(), s));
+  return PAS_OK;
+}
+
+void free_dev(void* p) {
+  if (p) (void)hipFree(p);
+}
+
+// Span arrays of `cap` slots (+ 1: the scans' last element), len all zero.
+int alloc_spans(pas_ctx* ctx, int64_t cap, int64_t** beg, int64_t** len, hipStream_t s) {
+  *beg = *len = nullptr;
+  const size_t bytes = sizeof(int64_t) * ((size_t)cap + 1);
+  hipError_t e = hipMalloc(beg, bytes);
+  if (e == hipSuccess) e = hipMalloc(len, bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(*len, 0, bytes, s);
+  if (e == hipSuccess) e = hipMemsetAsync(*beg, 0, bytes, s);
+  if (e != hipSuccess) {
+    free_dev(*beg);
+    free_dev(*len);
+    *beg = *len = nullptr;
+    return check_hip(ctx, e, "name table: span arrays");
+  }
+  return PAS_OK;
+}
+
+// A hash of `buckets` buckets over the named slots of t (its spans and pool in place),
+// replacing t.table; synchronous on s when the bucket count changes (the old table is freed).
+int rebuild_table(pas_ctx* ctx, NameTable& t, int64_t buckets, hipStream_t s) {
+  if (buckets != t.buckets) {
+    unsigned long long* nt = nullptr;
+    PAS_HIP(ctx, hipMalloc(&nt, sizeof(unsigned long long) * (size_t)buckets));
+    if (t.table) {
+      const hipError_t e = hipStreamSynchronize(s);
+      if (e != hipSuccess) {
+        free_dev(nt);
+        return check_hip(ctx, e, "name table: hipStreamSynchronize");
+      }
+      free_dev(t.table);
+    }
+    t.table = nt;
+    t.buckets = buckets;
+  }
+  PAS_HIP(ctx, hipMemsetAsync(t.table, 0xff, sizeof(unsigned long long) * (size_t)t.buckets, s));
+  if (t.n_slots > 0) {
+    names_insert<<<blocks_for(t.n_slots), kTpb, 0, s>>>(t.n_slots, nullptr, view_of(t));
+    PAS_HIP(ctx, hipGetLastError());
+  }
+  return PAS_OK;
+}
+
+// Room for pool_used + more bytes; synchronous on s when the pool moves.
+int grow_pool(pas_ctx* ctx, NameTable& t, int64_t more, hipStream_t s) {
+  const int64_t need = t.pool_used + more;
+  if (need <= t.pool_cap) return PAS_OK;
+  const int64_t cap = std::max(need, 2 * t.pool_cap);
+  char* np = nullptr;
+  PAS_HIP(ctx, hipMalloc(&np, (size_t)cap));
+  hipError_t e = hipSuccess;
+  if (t.pool_used > 0)
+    e = hipMemcpyAsync(np, t.pool, (size_t)t.pool_used, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    free_dev(np);
+    return check_hip(ctx, e, "name table: pool copy");
+  }
+  free_dev(t.pool);
+  t.pool = np;
+  t.pool_cap = cap;
+  return PAS_OK;
+}
+
+int no_table(pas_ctx* ctx, const char* fn) {
+  return set_error(ctx, PAS_ENOSNAP, std::string(fn) + ": no name table");
+}
+
+// offsets [n + 1] of a host form: from 0 and non-decreasing
+int check_csr(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
+              const std::string& fn) {
+  if (!off || off[0] != 0) return set_error(ctx, PAS_EINVAL, fn + ": offsets must start at 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return set_error(ctx, PAS_EINVAL, fn + ": offsets decrease");
+  if (off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  return PAS_OK;
+}
+
+// pas_names_assign[_device] on device arrays (d_slot may be null), synchronous on s.
+int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
+                        const char* d_bytes, int32_t* d_slot, int64_t new_cap,
+                        int32_t* new_entry_out, int32_t* new_slot_out, int64_t* n_new_out,
+                        hipStream_t s) {
+  NameTable& t = ctx->names;
+  if (n_new_out) *n_new_out = 0;
+  if (n == 0) return PAS_OK;
+  const size_t nn = (size_t)n, ns = (size_t)t.n_slots;
+  int64_t sb = 2;  // scratch buckets: at most half full even when every entry is new
+  while (sb < 2 * n) sb <<= 1;
+  size_t scan_n = 0, scan_s = 0, scan64 = 0;
+  int rc = scan_size<uint32_t>(ctx, nn + 1, &scan_n);
+  if (!rc) rc = scan_size<uint32_t>(ctx, ns + 1, &scan_s);
+  if (!rc) rc = scan_size<int64_t>(ctx, nn + 1, &scan64);
+  if (rc) return rc;
+  const size_t scan_bytes = std::max({scan_n, scan_s, scan64});
+  SlotScope scope(ctx, s, 0, &rc);
+  if (!scope.slot) return rc;
+  const size_t total = carve_size(
+      {sizeof(uint32_t) * 4, sizeof(int32_t) * nn, sizeof(uint64_t) * nn, sizeof(int32_t) * nn,
+       sizeof(uint32_t) * (nn + 1), sizeof(uint32_t) * (nn + 1), sizeof(int64_t) * (nn + 1),
+       sizeof(int64_t) * (nn + 1), sizeof(uint32_t) * (ns + 1), sizeof(uint32_t) * (ns + 1),
+       sizeof(int32_t) * nn, sizeof(int32_t) * nn, sizeof(int32_t) * nn,
+       sizeof(unsigned long long) * (size_t)sb, scan_bytes});
+  char* base = static_cast<char*>(slot_buf(ctx, scope.slot, kBufNames, total, s, &rc));
+  if (!base) return rc;
+  Carve cv{base};
+  uint32_t* d_ctr = cv.take<uint32_t>(4);
+  int32_t* d_own_slot = cv.take<int32_t>(nn);
+  uint64_t* d_hash = cv.take<uint64_t>(nn);
+  int32_t* d_first_of = cv.take<int32_t>(nn);
+  uint32_t* d_flag = cv.take<uint32_t>(nn + 1);
+  uint32_t* d_rank = cv.take<uint32_t>(nn + 1);
+  int64_t* d_flen = cv.take<int64_t>(nn + 1);
+  int64_t* d_fpos = cv.take<int64_t>(nn + 1);
+  uint32_t* d_sflag = cv.take<uint32_t>(ns + 1);
+  uint32_t* d_srank = cv.take<uint32_t>(ns + 1);
+  int32_t* d_spare = cv.take<int32_t>(nn);
+  int32_t* d_new_entry = cv.take<int32_t>(nn);
+  int32_t* d_new_slot = cv.take<int32_t>(nn);
+  unsigned long long* d_scratch = cv.take<unsigned long long>((size_t)sb);
+  void* d_scan = cv.take<char>(scan_bytes);
+  if (!d_slot) d_slot = d_own_slot;
+
+  // (a) the lookups; one word back: the entries that name a new node
+  PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(uint32_t) * 4, s));
+  rc = names_resolve_launch(ctx, n, n_bytes, d_off, d_bytes, d_slot, d_hash, d_ctr, false, s);
+  if (rc) return rc;
+  uint32_t n_unknown = 0;
+  PAS_HIP(ctx, hipMemcpyAsync(&n_unknown, d_ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  if (n_unknown == 0) return PAS_OK;
+
+  // (b), (c): firsts and spare slots, ranked
+  PAS_HIP(ctx, hipMemsetAsync(d_scratch, 0xff, sizeof(unsigned long long) * (size_t)sb, s));
+  assign_dedupe<<<blocks_for(n), kTpb, 0, s>>>(n, n_bytes, d_off, d_bytes, d_slot, d_hash, sb - 1,
+                                               d_scratch);
+  PAS_HIP(ctx, hipGetLastError());
+  assign_firsts<<<blocks_for(n + 1), kTpb, 0, s>>>(n, n_bytes, d_off, d_bytes, d_slot, d_hash,
+                                                   sb - 1, d_scratch, d_first_of, d_flag, d_flen);
+  PAS_HIP(ctx, hipGetLastError());
+  names_spare_flags<<<blocks_for(t.n_slots + 1), kTpb, 0, s>>>(t.n_slots, t.len, d_sflag);
+  PAS_HIP(ctx, hipGetLastError());
+  if ((rc = scan_run<uint32_t>(ctx, d_scan, scan_bytes, d_flag, d_rank, nn + 1, s))) return rc;
+  if ((rc = scan_run<int64_t>(ctx, d_scan, scan_bytes, d_flen, d_fpos, nn + 1, s))) return rc;
+  if ((rc = scan_run<uint32_t>(ctx, d_scan, scan_bytes, d_sflag, d_srank, ns + 1, s))) return rc;
+  uint32_t n_new = 0, n_spare = 0;
+  int64_t new_bytes = 0;
+  PAS_HIP(ctx, hipMemcpyAsync(&n_new, d_rank + nn, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipMemcpyAsync(&n_spare, d_srank + ns, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipMemcpyAsync(&new_bytes, d_fpos + nn, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  if (n_new_out) *n_new_out = n_new;
+  if ((int64_t)n_new > std::min<int64_t>(n_spare, new_cap))
+    return set_error(ctx, PAS_ECAPACITY,
+                     "pas_names_assign: " + std::to_string(n_new) + " new names, " +
+                         std::to_string(n_spare) + " spare slots, new_cap " +
+                         std::to_string(new_cap));
+  if (!new_entry_out || !new_slot_out)
+    return set_error(ctx, PAS_EINVAL, "pas_names_assign: new names and null output arrays");
+
+  // (d), (e): nothing has changed so far; from here the table does
+  if ((rc = grow_pool(ctx, t, new_bytes, s))) return rc;
+  assign_spares<<<blocks_for(t.n_slots), kTpb, 0, s>>>(t.n_slots, n_new, d_sflag, d_srank,
+                                                       d_spare);
+  PAS_HIP(ctx, hipGetLastError());
+  assign_commit<<<blocks_for(n), kTpb, 0, s>>>(n, n_bytes, d_off, d_bytes, d_flag, d_rank, d_fpos,
+                                               d_spare, t.pool_used, view_of(t), d_slot,
+                                               d_new_entry, d_new_slot);
+  PAS_HIP(ctx, hipGetLastError());
+  names_insert<<<blocks_for(n_new), kTpb, 0, s>>>(n_new, d_new_slot, view_of(t));
+  PAS_HIP(ctx, hipGetLastError());
+  assign_repeats<<<blocks_for(n), kTpb, 0, s>>>(n, d_first_of, d_flag, d_slot);
+  PAS_HIP(ctx, hipGetLastError());
+  t.pool_used += new_bytes;
+  t.n_named += (int32_t)n_new;
+  PAS_HIP(ctx, hipMemcpyAsync(new_entry_out, d_new_entry, sizeof(int32_t) * n_new,
+                              hipMemcpyDeviceToHost, s));
+  PAS_HIP(ctx, hipMemcpyAsync(new_slot_out, d_new_slot, sizeof(int32_t) * n_new,
+                              hipMemcpyDeviceToHost, s));
+  if ((rc = derived_built(ctx, ctx->names_sync, s))) return rc;
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  return PAS_OK;
+}
+
+}  // namespace
+
+void free_names(NameTable& t) {
+  free_dev(t.beg);
+  free_dev(t.len);
+  free_dev(t.pool);
+  free_dev(t.table);
+  t = NameTable{};
+}
+
+int names_resolve_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
+                         const char* d_bytes, int32_t* d_slot, uint64_t* d_hash,
+                         uint32_t* d_unknown, bool count_empty, hipStream_t s) {
+  if (n <= 0) return PAS_OK;
+  int rc = derived_wait(ctx, ctx->names_sync, s);
+  if (rc) return rc;
+  names_lookup<<<blocks_for(n), kTpb, 0, s>>>(n, n_bytes, d_off, d_bytes, view_of(ctx->names),
+                                              d_slot, d_hash, d_unknown, count_empty ? 1 : 0);
+  PAS_HIP(ctx, hipGetLastError());
+  return PAS_OK;
+}
+
+}  // namespace pas
+
+using namespace pas;
+
+extern "C" {
+
+uint64_t pas_name_hash(const char* bytes, int64_t len) {
+  return bytes && len > 0 ? name_hash(bytes, len) : name_hash("", 0);
+}
+
+int pas_names_set(pas_ctx* ctx, int32_t n_slots, const int64_t* name_off, const char* bytes) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_set";
+  if (n_slots < 0) return set_error(ctx, PAS_EINVAL, fn + ": n_slots < 0");
+  int rc = check_csr(ctx, n_slots, name_off, bytes, fn);
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  hipStream_t s = ctx->stream;
+  const int64_t total = name_off[n_slots];
+  NameTable nt;
+  nt.n_slots = n_slots;
+  nt.slot_cap = std::max<int64_t>(n_slots, 1);
+  nt.pool_cap = std::max<int64_t>(total, 1);
+  nt.pool_used = total;
+  int32_t* d_ctr = nullptr;  // {lowest loser, named slots}
+  const int32_t ctr0[2] = {INT32_MAX, 0};
+  int32_t ctr[2] = {INT32_MAX, 0};
+  Staging st(ctx);
+  int64_t* d_off;
+  st.in(d_off, name_off, (size_t)n_slots + 1);
+  st.work(d_ctr, 2);
+  auto build = [&]() -> int {
+    int r = st.upload();
+    if (r) return r;
+    if ((r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s))) return r;
+    PAS_HIP(ctx, hipMalloc(&nt.pool, (size_t)nt.pool_cap));
+    if (total > 0)
+      PAS_HIP(ctx, hipMemcpyAsync(nt.pool, bytes, (size_t)total, hipMemcpyHostToDevice, s));
+    PAS_HIP(ctx, hipMemcpyAsync(d_ctr, ctr0, sizeof(ctr0), hipMemcpyHostToDevice, s));
+    if (n_slots > 0) {
+      names_spans<<<blocks_for(n_slots), kTpb, 0, s>>>(n_slots, d_off, nt.beg, nt.len, d_ctr);
+      PAS_HIP(ctx, hipGetLastError());
+    }
+    if ((r = rebuild_table(ctx, nt, buckets_for(n_slots), s))) return r;
+    if (n_slots > 0) {
+      names_flag_losers<<<blocks_for(n_slots), kTpb, 0, s>>>(n_slots, view_of(nt), d_ctr);
+      PAS_HIP(ctx, hipGetLastError());
+    }
+    PAS_HIP(ctx, hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    PAS_HIP(ctx, hipStreamSynchronize(s));
+    return PAS_OK;
+  };
+  rc = build();
+  if (!rc && ctr[0] != INT32_MAX)
+    rc = set_error(ctx, PAS_EINVAL, fn + ": slot " + std::to_string(ctr[0]) +
+                                        " holds a name that also stands in a lower slot");
+  if (rc) {  // the previous table stays as it was
+    (void)hipStreamSynchronize(s);
+    free_names(nt);
+    return rc;
+  }
+  nt.n_named = ctr[1];
+  nt.valid = true;
+  free_names(ctx->names);
+  ctx->names = nt;
+  return derived_built(ctx, ctx->names_sync, s);
+}
+
+int pas_names_info(const pas_ctx* ctx, int32_t* n_slots, int32_t* n_named, int64_t* n_bytes) {
+  if (!ctx) return PAS_EINVAL;
+  if (!ctx->names.valid) return PAS_ENOSNAP;
+  if (n_slots) *n_slots = ctx->names.n_slots;
+  if (n_named) *n_named = ctx->names.n_named;
+  if (n_bytes) *n_bytes = ctx->names.pool_used;
+  return PAS_OK;
+}
+
+int pas_names_drop(pas_ctx* ctx) {
+  if (!ctx) return PAS_EINVAL;
+  if (!ctx->names.valid) return no_table(ctx, "pas_names_drop");
+  ctx->names.valid = false;
+  return PAS_OK;
+}
+
+int pas_names_get(pas_ctx* ctx, int64_t* name_off_out, char* bytes_out, int64_t cap) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_get";
+  NameTable& t = ctx->names;
+  if (!t.valid) return no_table(ctx, fn.c_str());
+  if (!name_off_out || cap < 0 || (cap > 0 && !bytes_out))
+    return set_error(ctx, PAS_EINVAL, fn + ": null output or cap < 0");
+  int rc = activate(ctx);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  const size_t ns = (size_t)t.n_slots;
+  const bool fits = cap >= t.pool_used;
+  size_t scan_bytes = 0;
+  if ((rc = scan_size<int64_t>(ctx, ns + 1, &scan_bytes))) return rc;
+  Staging st(ctx);
+  int64_t* d_off;
+  char *d_bytes, *d_scan;
+  st.out(d_off, name_off_out, ns + 1);
+  st.out(d_bytes, bytes_out, fits ? (size_t)t.pool_used : 0);
+  st.work(d_scan, scan_bytes);
+  if ((rc = st.upload())) return rc;
+  if ((rc = derived_wait(ctx, ctx->names_sync, s))) return rc;
+  if ((rc = scan_run<int64_t>(ctx, d_scan, scan_bytes, t.len, d_off, ns + 1, s))) return rc;
+  if (fits && ns > 0) {
+    names_gather<<<blocks_for(t.n_slots), kTpb, 0, s>>>(t.n_slots, nullptr, t.beg, t.len, t.pool,
+                                                        d_off, d_bytes);
+    PAS_HIP(ctx, hipGetLastError());
+  }
+  PAS_HIP(ctx, st.fetch());
+  if (!fits)
+    return set_error(ctx, PAS_ECAPACITY, fn + ": " + std::to_string(t.pool_used) +
+                                             " bytes of names, cap " + std::to_string(cap));
+  return PAS_OK;
+}
+
+int pas_names_resolve_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_name_off,
+                             const char* d_bytes, int32_t* d_slot_out, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_resolve_device";
+  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (n < 0 || n_bytes < 0) return set_error(ctx, PAS_EINVAL, fn + ": n or n_bytes < 0");
+  if (n == 0) return PAS_OK;
+  if (!d_name_off || !d_slot_out || (n_bytes > 0 && !d_bytes))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  int rc = activate(ctx);
+  if (rc) return rc;
+  return names_resolve_launch(ctx, n, n_bytes, d_name_off, d_bytes, d_slot_out, nullptr, nullptr,
+                              false, pick_stream(ctx, hip_stream));
+}
+
+int pas_names_resolve(pas_ctx* ctx, int64_t n, const int64_t* name_off, const char* bytes,
+                      int32_t* slot_out) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_resolve";
+  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
+  if (n == 0) return PAS_OK;
+  int rc = check_csr(ctx, n, name_off, bytes, fn);
+  if (rc) return rc;
+  if (!slot_out) return set_error(ctx, PAS_EINVAL, fn + ": null output");
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  int64_t* d_off;
+  char* d_bytes;
+  int32_t* d_slot;
+  st.in(d_off, name_off, (size_t)n + 1);
+  st.in(d_bytes, bytes, (size_t)name_off[n]);
+  st.out(d_slot, slot_out, (size_t)n);
+  if ((rc = st.upload())) return rc;
+  rc = names_resolve_launch(ctx, n, name_off[n], d_off, d_bytes, d_slot, nullptr, nullptr, false,
+                            ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+int pas_names_assign_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_name_off,
+                            const char* d_bytes, int32_t* d_slot_out, int64_t new_cap,
+                            int32_t* new_entry_out, int32_t* new_slot_out, int64_t* n_new_out,
+                            void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_assign_device";
+  if (n_new_out) *n_new_out = 0;
+  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (n < 0 || n > INT32_MAX || n_bytes < 0 || new_cap < 0)
+    return set_error(ctx, PAS_EINVAL, fn + ": n, n_bytes or new_cap out of range");
+  if (n == 0) return PAS_OK;
+  if (!d_name_off || (n_bytes > 0 && !d_bytes))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  int rc = activate(ctx);
+  if (rc) return rc;
+  return names_assign_launch(ctx, n, n_bytes, d_name_off, d_bytes, d_slot_out, new_cap,
+                             new_entry_out, new_slot_out, n_new_out,
+                             pick_stream(ctx, hip_stream));
+}
+
+int pas_names_assign(pas_ctx* ctx, int64_t n, const int64_t* name_off, const char* bytes,
+                     int32_t* slot_out, int64_t new_cap, int32_t* new_entry_out,
+                     int32_t* new_slot_out, int64_t* n_new_out) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_assign";
+  if (n_new_out) *n_new_out = 0;
+  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (n < 0 || n > INT32_MAX || new_cap < 0)
+    return set_error(ctx, PAS_EINVAL, fn + ": n or new_cap out of range");
+  if (n == 0) return PAS_OK;
+  int rc = check_csr(ctx, n, name_off, bytes, fn);
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  int64_t* d_off;
+  char* d_bytes;
+  int32_t* d_slot;
+  st.in(d_off, name_off, (size_t)n + 1);
+  st.in(d_bytes, bytes, (size_t)name_off[n]);
+  st.out_opt(d_slot, slot_out, (size_t)n);
+  if ((rc = st.upload())) return rc;
+  rc = names_assign_launch(ctx, n, name_off[n], d_off, d_bytes, d_slot, new_cap, new_entry_out,
+                           new_slot_out, n_new_out, ctx->stream);
+  if (rc && rc != PAS_ECAPACITY) return rc;
+  const std::string msg = ctx->err;  // (PAS_ECAPACITY: slot_out holds the plain lookups)
+  PAS_HIP(ctx, st.fetch());
+  if (rc) ctx->err = msg;
+  return rc;
+}
+
+int pas_names_resize(pas_ctx* ctx, int32_t n_slots_new, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_resize";
+  NameTable& t = ctx->names;
+  if (!t.valid) return no_table(ctx, fn.c_str());
+  if (n_slots_new < t.n_slots)
+    return set_error(ctx, PAS_EINVAL, fn + ": " + std::to_string(n_slots_new) + " slots, the " +
+                                          "table has " + std::to_string(t.n_slots));
+  int rc = activate(ctx);
+  if (rc) return rc;
+  hipStream_t s = pick_stream(ctx, hip_stream);
+  if (n_slots_new > t.slot_cap) {
+    int64_t *beg, *len;
+    if ((rc = alloc_spans(ctx, n_slots_new, &beg, &len, s))) return rc;
+    const size_t old = sizeof(int64_t) * (size_t)t.n_slots;
+    hipError_t e = hipSuccess;
+    if (old) e = hipMemcpyAsync(beg, t.beg, old, hipMemcpyDeviceToDevice, s);
+    if (old && e == hipSuccess) e = hipMemcpyAsync(len, t.len, old, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      free_dev(beg);
+      free_dev(len);
+      return check_hip(ctx, e, "pas_names_resize: span copy");
+    }
+    free_dev(t.beg);
+    free_dev(t.len);
+    t.beg = beg;
+    t.len = len;
+    t.slot_cap = n_slots_new;
+  }
+  t.n_slots = n_slots_new;
+  if (2 * (int64_t)n_slots_new > t.buckets)  // the load factor would pass 1/2
+    if ((rc = rebuild_table(ctx, t, buckets_for(n_slots_new), s))) return rc;
+  if ((rc = derived_built(ctx, ctx->names_sync, s))) return rc;
+  PAS_HIP(ctx, hipStreamSynchronize(s));
+  return PAS_OK;
+}
+
+int pas_names_remap(pas_ctx* ctx, int32_t n_slots_new, const int32_t* src_slot,
+                    void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_names_remap";
+  NameTable& t = ctx->names;
+  if (!t.valid) return no_table(ctx, fn.c_str());
+  if (n_slots_new < 0 || (n_slots_new > 0 && !src_slot))
+    return set_error(ctx, PAS_EINVAL, fn + ": bad slot count or null map");
+  int32_t last = -1;
+  for (int32_t j = 0; j < n_slots_new; ++j) {
+    const int32_t v = src_slot[j];
+    if (v == -1) continue;
+    if (v < 0 || v >= t.n_slots || v <= last)
+      return set_error(ctx, PAS_EINVAL, fn + ": entry " + std::to_string(j) + " is neither -1 " +
+                                            "nor a slot above the entries before it");
+    last = v;
+  }
+  int rc = activate(ctx);
+  if (rc) return rc;
+  hipStream_t s = pick_stream(ctx, hip_stream);
+  const size_t n2 = (size_t)n_slots_new;
+  size_t scan_bytes = 0;
+  if ((rc = scan_size<int64_t>(ctx, n2 + 1, &scan_bytes))) return rc;
+  SlotScope scope(ctx, s, 0, &rc);
+  if (!scope.slot) return rc;
+  const size_t total = carve_size({sizeof(int32_t) * 2, sizeof(int32_t) * n2, scan_bytes});
+  char* base = static_cast<char*>(slot_buf(ctx, scope.slot, kBufNames, total, s, &rc));
+  if (!base) return rc;
+  Carve cv{base};
+  int32_t* d_ctr = cv.take<int32_t>(2);
+  int32_t* d_src = cv.take<int32_t>(n2);
+  void* d_scan = cv.take<char>(scan_bytes);
+  NameTable nt;
+  nt.n_slots = n_slots_new;
+  nt.slot_cap = std::max<int64_t>(n_slots_new, 1);
+  int32_t ctr[2] = {0, 0};
+  int64_t bytes_new = 0;
+  auto build = [&]() -> int {
+    int r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s);
+    if (r) return r;
+    PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(int32_t) * 2, s));
+    if (n2) {
+      PAS_HIP(ctx, hipMemcpyAsync(d_src, src_slot, sizeof(int32_t) * n2, hipMemcpyHostToDevice, s));
+      names_remap_lens<<<blocks_for(n_slots_new), kTpb, 0, s>>>(n_slots_new, d_src, t.len, nt.len,
+                                                                d_ctr);
+      PAS_HIP(ctx, hipGetLastError());
+    }
+    if ((r = scan_run<int64_t>(ctx, d_scan, scan_bytes, nt.len, nt.beg, n2 + 1, s))) return r;
+    PAS_HIP(ctx, hipMemcpyAsync(&bytes_new, nt.beg + n2, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    PAS_HIP(ctx, hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    PAS_HIP(ctx, hipStreamSynchronize(s));
+    nt.pool_cap = std::max<int64_t>(bytes_new, 1);
+    nt.pool_used = bytes_new;
+    nt.n_named = ctr[1];
+    PAS_HIP(ctx, hipMalloc(&nt.pool, (size_t)nt.pool_cap));
+    if (n2) {
+      names_gather<<<blocks_for(n_slots_new), kTpb, 0, s>>>(n_slots_new, d_src, t.beg, t.len,
+                                                            t.pool, nt.beg, nt.pool);
+      PAS_HIP(ctx, hipGetLastError());
+    }
+    if ((r = rebuild_table(ctx, nt, buckets_for(n_slots_new), s))) return r;
+    PAS_HIP(ctx, hipStreamSynchronize(s));
+    return PAS_OK;
+  };
+  rc = build();
+  if (rc) {  // the table stays as it was
+    (void)hipStreamSynchronize(s);
+    free_names(nt);
+    return rc;
+  }
+  nt.valid = true;
+  free_names(t);
+  ctx->names = nt;
+  return derived_built(ctx, ctx->names_sync, s);
+}
+
+}  // extern "C"

@@ -279,6 +279,8 @@ void pas_destroy(pas_ctx* ctx) {
   if (ctx->policies.dev) (void)hipFree(ctx->policies.dev);
   if (ctx->policies.viol) (void)hipFree(ctx->policies.viol);
   if (ctx->policies.viol_sync.ev) (void)hipEventDestroy(ctx->policies.viol_sync.ev);
+  free_names(ctx->names);
+  if (ctx->names_sync.ev) (void)hipEventDestroy(ctx->names_sync.ev);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->gas_sync_fault) (void)hipHostFree(ctx->gas_sync_fault);
   if (ctx->place_host) (void)hipHostFree(ctx->place_host);
@@ -601,6 +603,109 @@ int pas_tas_snapshot_update_quantities(pas_ctx* ctx, uint64_t gen_from, uint64_t
   if ((rc = st.upload())) return rc;
   rc = tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, n_bytes, d_node, d_off,
                                     d_bytes, kind_out, scale_out, bad_entry, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+// The refresh with each entry's node given by name (name_table.hip): the names are resolved,
+// lookup only, into a buffer of the stream's slot and the refresh above runs on it.  The count
+// of entries without a slot comes back on s before that launch's own synchronize.
+static int update_quantities_names_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
+                                          const int32_t* cols, const int64_t* col_off,
+                                          int64_t n_name_bytes, const int64_t* d_name_off,
+                                          const char* d_name_bytes, int64_t n_bytes,
+                                          const int64_t* d_lit_off, const char* d_bytes,
+                                          int32_t* kind_out, int32_t* scale_out,
+                                          int64_t* bad_entry, int64_t* n_unknown_out,
+                                          hipStream_t s) {
+  const int64_t T = n_cols > 0 ? col_off[n_cols] : 0;
+  if (n_unknown_out) *n_unknown_out = 0;
+  int rc = PAS_OK;
+  SlotScope scope(ctx, s, 0, &rc);
+  if (!scope.slot) return rc;
+  int32_t* d_node = nullptr;
+  uint32_t unknown = 0;
+  if (T > 0) {
+    const size_t total = carve_size({sizeof(uint32_t), sizeof(int32_t) * (size_t)T});
+    char* base = static_cast<char*>(slot_buf(ctx, scope.slot, kBufNames, total, s, &rc));
+    if (!base) return rc;
+    Carve cv{base};
+    uint32_t* d_ctr = cv.take<uint32_t>(1);
+    d_node = cv.take<int32_t>((size_t)T);
+    PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(uint32_t), s));
+    rc = names_resolve_launch(ctx, T, n_name_bytes, d_name_off, d_name_bytes, d_node, nullptr,
+                              d_ctr, true, s);
+    if (rc) return rc;
+    PAS_HIP(ctx, hipMemcpyAsync(&unknown, d_ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  }
+  rc = tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, n_bytes, d_node,
+                                    d_lit_off, d_bytes, kind_out, scale_out, bad_entry, s);
+  if (T > 0 && rc) (void)hipStreamSynchronize(s);  // (an early error: `unknown` is a local)
+  if (n_unknown_out) *n_unknown_out = unknown;
+  return rc;
+}
+
+int pas_tas_snapshot_update_quantities_names_device(
+    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_cols, const int32_t* cols,
+    const int64_t* col_off, int64_t n_name_bytes, const int64_t* d_name_off,
+    const char* d_name_bytes, int64_t n_bytes, const int64_t* d_lit_off, const char* d_bytes,
+    int32_t* kind_out, int32_t* scale_out, int64_t* bad_entry, int64_t* n_unknown_out,
+    void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities_names_device";
+  if (bad_entry) *bad_entry = -1;
+  if (n_unknown_out) *n_unknown_out = 0;
+  if (!ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
+  if (rc) return rc;
+  if (n_cols > 0 && col_off[n_cols] > 0 &&
+      (!d_name_off || !d_lit_off || n_bytes < 0 || n_name_bytes < 0 || (n_bytes > 0 && !d_bytes) ||
+       (n_name_bytes > 0 && !d_name_bytes)))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input or a byte count < 0");
+  if ((rc = activate(ctx))) return rc;
+  return update_quantities_names_launch(ctx, gen_to, n_cols, cols, col_off, n_name_bytes,
+                                        d_name_off, d_name_bytes, n_bytes, d_lit_off, d_bytes,
+                                        kind_out, scale_out, bad_entry, n_unknown_out,
+                                        pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_snapshot_update_quantities_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                             int32_t n_cols, const int32_t* cols,
+                                             const int64_t* col_off, const int64_t* name_off,
+                                             const char* name_bytes, const int64_t* lit_off,
+                                             const char* bytes, int32_t* kind_out,
+                                             int32_t* scale_out, int64_t* bad_entry,
+                                             int64_t* n_unknown_out) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities_names";
+  if (bad_entry) *bad_entry = -1;
+  if (n_unknown_out) *n_unknown_out = 0;
+  if (!ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
+  if (rc) return rc;
+  const int64_t T = n_cols > 0 ? col_off[n_cols] : 0;
+  int64_t n_bytes = 0, n_name_bytes = 0;
+  if (T > 0) {
+    if ((rc = check_offsets(ctx, T, lit_off, fn + ": lit_off"))) return rc;
+    if ((rc = check_offsets(ctx, T, name_off, fn + ": name_off"))) return rc;
+    n_bytes = lit_off[T];
+    n_name_bytes = name_off[T];
+    if ((n_bytes > 0 && !bytes) || (n_name_bytes > 0 && !name_bytes))
+      return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  }
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  int64_t *d_name_off, *d_off;
+  char *d_name_bytes, *d_bytes;
+  st.in(d_name_off, name_off, T > 0 ? (size_t)T + 1 : 0);
+  st.in(d_name_bytes, name_bytes, (size_t)n_name_bytes);
+  st.in(d_off, lit_off, T > 0 ? (size_t)T + 1 : 0);
+  st.in(d_bytes, bytes, (size_t)n_bytes);
+  if ((rc = st.upload())) return rc;
+  rc = update_quantities_names_launch(ctx, gen_to, n_cols, cols, col_off, n_name_bytes,
+                                      d_name_off, d_name_bytes, n_bytes, d_off, d_bytes, kind_out,
+                                      scale_out, bad_entry, n_unknown_out, ctx->stream);
   if (rc) return rc;
   PAS_HIP(ctx, st.fetch());
   return PAS_OK;

@@ -230,6 +230,28 @@ struct TasPolicies {
   DerivedSync viol_sync;
 };
 
+// The resident node-name table (name_table.hip): which name stands in which node slot, for
+// every snapshot of the context (combined contexts share one slot numbering, so it belongs to
+// neither).  A slot's name is pool[beg[s] .. beg[s] + len[s]); len 0 marks a spare slot, so
+// the empty name never has a slot.  The pool's order is the order of arrival, not of the
+// slots.  `table` is an open-addressing hash of the named slots, `buckets` a power of two >=
+// 2 * n_slots: word = tag << 32 | slot (name_hash.h), all ones = empty, linear probing with
+// wraparound; nothing is ever deleted in place (a remap rebuilds).  The span arrays hold
+// slot_cap + 1 entries and len is 0 from n_slots on.  Storage only grows.
+struct NameTable {
+  bool valid = false;
+  int32_t n_slots = 0;
+  int32_t n_named = 0;
+  int64_t slot_cap = 0;
+  int64_t* beg = nullptr;
+  int64_t* len = nullptr;
+  char* pool = nullptr;
+  int64_t pool_used = 0;  // = the sum of the lengths
+  int64_t pool_cap = 0;
+  unsigned long long* table = nullptr;
+  int64_t buckets = 0;
+};
+
 // slot_buf buffers
 enum SlotBuf {
   kBufGpass = 0,  // pass bitmaps of clusters past the LDS bitmap (tas_eval)
@@ -248,7 +270,10 @@ enum SlotBuf {
   // parsed entries, per-column summary and plan, and the column buffers of a refresh from
   // Quantity literals (tas_ingest.hip)
   kBufIngest = 8,
-  kSlotBufs = 9
+  // resolved slots, hashes, the first-seen scratch table, scan inputs and outputs of a name
+  // lookup or assignment (name_table.hip)
+  kBufNames = 9,
+  kSlotBufs = 10
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -322,6 +347,8 @@ struct pas_ctx {
   pas::TasSnapshot tas;
   pas::GasSnapshot gas;
   pas::TasPolicies policies;
+  pas::NameTable names;
+  pas::DerivedSync names_sync;  // the last change of `names`: lookups on other streams wait
   // counts the calls that can renumber or re-create the TAS snapshot's metric columns
   // (snapshot_set, reshape, drop): a policy table set at an older value is stale
   uint64_t tas_col_epoch = 1;
@@ -435,6 +462,15 @@ int tas_update_quantities_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
                                  const int32_t* d_entry_node, const int64_t* d_lit_off,
                                  const char* d_bytes, int32_t* kind_out, int32_t* scale_out,
                                  int64_t* bad_entry, hipStream_t s);
+// Name table (name_table.hip).  free_names: every array of the table (pas_destroy).
+// names_resolve_launch: d_slot[i] = the slot of name i = d_bytes[d_off[i] .. d_off[i + 1])
+// (offsets read clamped into [0, n_bytes]) or -1, enqueued on s after the last table change;
+// d_hash (the names' hashes) and d_unknown (a zeroed counter: + the entries without a slot,
+// the empty ones only when count_empty) may be null.  The caller has checked ctx->names.valid.
+void free_names(NameTable& t);
+int names_resolve_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
+                         const char* d_bytes, int32_t* d_slot, uint64_t* d_hash,
+                         uint32_t* d_unknown, bool count_empty, hipStream_t s);
 // The resident snapshot gathered into storage of n_nodes_new (>= the resident count) x
 // n_metrics_new (tas_reshape.hip): new column m is old column src_col[m] or, for -1, empty
 // (src_col: host [n_metrics_new], distinct old columns or -1; the caller has checked it and

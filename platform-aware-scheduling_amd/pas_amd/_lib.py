@@ -367,6 +367,24 @@ SIGNATURES = {
     "pas_decode_pod_requests": (
         c_int, [c_char_p, c_int64, c_int32, POINTER(c_char_p), c_int32, _P, _P,
                 POINTER(c_int32), POINTER(c_int32)]),
+    "pas_name_hash": (c_uint64, [c_char_p, c_int64]),
+    "pas_names_set": (c_int, [_P, c_int32, _P, _P]),
+    "pas_names_info": (c_int, [_P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]),
+    "pas_names_get": (c_int, [_P, _P, _P, c_int64]),
+    "pas_names_drop": (c_int, [_P]),
+    "pas_names_resolve": (c_int, [_P, c_int64, _P, _P, _P]),
+    "pas_names_resolve_device": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
+    "pas_names_assign": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, _P, POINTER(c_int64)]),
+    "pas_names_assign_device": (
+        c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, _P, _P, POINTER(c_int64), _P]),
+    "pas_names_resize": (c_int, [_P, c_int32, _P]),
+    "pas_names_remap": (c_int, [_P, c_int32, _P, _P]),
+    "pas_tas_snapshot_update_quantities_names": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
+                POINTER(c_int64), POINTER(c_int64)]),
+    "pas_tas_snapshot_update_quantities_names_device": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P,
+                POINTER(c_int64), POINTER(c_int64), _P]),
     "pas_decode_set_threads": (c_int, [c_int32]),
     "pas_decode_threads": (c_int32, [c_int64]),
     "pas_set_timing": (c_int, [_P, c_int]),

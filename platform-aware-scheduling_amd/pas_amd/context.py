@@ -118,6 +118,13 @@ def quantity_parse_fixed(q) -> Tuple[int, int, int, int, int]:
     return rc, whole.value, nano.value, dec.value, fit.value
 
 
+def name_hash(name) -> int:
+    """pas_name_hash of a node name (str or bytes): the name table's hash, whose low bits pick
+    the home bucket and whose high 32 bits are the tag (csrc/name_hash.h)."""
+    b = name.encode() if isinstance(name, str) else bytes(name)
+    return _lib.load().pas_name_hash(b, len(b))
+
+
 def quantity_as_int64(q: str) -> int:
     """resource.Quantity.AsInt64 with `ok` ignored (gpuscheduler/utils.go:23)."""
     out = c_int64()
@@ -372,6 +379,145 @@ class Context:
             _ptr(scale), byref(bad), _stream(stream))
         return self._update_quantities_result(rc, "pas_tas_snapshot_update_quantities_device",
                                               bad, kind[:len(cols)], scale[:len(cols)])
+
+    # ---- the resident node-name table (csrc/name_table.hip)
+    @staticmethod
+    def _csr(name_off):
+        off = np.ascontiguousarray(name_off, dtype=np.int64).reshape(-1)
+        assert len(off) >= 1, "offsets hold n + 1 entries"
+        return off, len(off) - 1
+
+    def names_set(self, name_off, blob):
+        """Install the name table (pas_names_set): slot s holds blob[name_off[s]:name_off[s + 1]],
+        an empty span is a spare slot (snapshot.pack_names).  A name in two slots is
+        PasError(PAS_EINVAL) and leaves the previous table valid."""
+        off, n = self._csr(name_off)
+        self._check(self._l.pas_names_set(self._h, n, _ptr(off), _ptr(self._blob(blob))),
+                    "pas_names_set")
+
+    def names_info(self):
+        """(n_slots, n_named, n_bytes) of the name table."""
+        n, k, b = c_int32(), c_int32(), c_int64()
+        self._check(self._l.pas_names_info(self._h, byref(n), byref(k), byref(b)),
+                    "pas_names_info")
+        return n.value, k.value, b.value
+
+    def names_get(self):
+        """(name_off int64 [n_slots + 1], blob bytes): the names packed in slot order."""
+        n, _, nb = self.names_info()
+        off = np.zeros(n + 1, np.int64)
+        buf = np.zeros(max(nb, 1), np.uint8)
+        self._check(self._l.pas_names_get(self._h, _ptr(off), _ptr(buf), nb), "pas_names_get")
+        return off, buf[:nb].tobytes()
+
+    def names_drop(self):
+        self._check(self._l.pas_names_drop(self._h), "pas_names_drop")
+
+    def names_resolve(self, name_off, blob) -> np.ndarray:
+        """slot int32 [n] of the names blob[name_off[i]:name_off[i + 1]], -1 for a name without
+        a slot (pas_names_resolve)."""
+        off, n = self._csr(name_off)
+        slot = np.full(max(n, 1), -1, np.int32)
+        self._check(self._l.pas_names_resolve(self._h, n, _ptr(off), _ptr(self._blob(blob)),
+                                              _ptr(slot)), "pas_names_resolve")
+        return slot[:n]
+
+    def names_resolve_device(self, n: int, n_bytes: int, name_off_t, bytes_t, slot_t,
+                             stream=None):
+        self._check(self._l.pas_names_resolve_device(
+            self._h, n, n_bytes, _dptr(name_off_t), _dptr(bytes_t), _dptr(slot_t),
+            _stream(stream)), "pas_names_resolve_device")
+
+    def _assign_result(self, rc: int, what: str, n_new, new_entry, new_slot):
+        if rc != _lib.PAS_OK:
+            msg = self._l.pas_last_error(self._h)
+            err = PasError(rc, f"{what}: {msg.decode() if msg else ''}")
+            err.n_new = n_new.value  # PAS_ECAPACITY: the distinct new names
+            raise err
+        return new_entry[:n_new.value], new_slot[:n_new.value]
+
+    def names_assign(self, name_off, blob, new_cap: Optional[int] = None, want_slots=True):
+        """Lookup plus first-seen assignment (pas_names_assign): (slot int32 [n] or None,
+        new_entry, new_slot), the latter two listing the first appearance of each new name and
+        the spare slot it took.  PasError(PAS_ECAPACITY) carries .n_new and changes nothing."""
+        off, n = self._csr(name_off)
+        cap = n if new_cap is None else int(new_cap)
+        slot = np.full(max(n, 1), -1, np.int32) if want_slots else None
+        new_entry = np.zeros(max(cap, 1), np.int32)
+        new_slot = np.zeros(max(cap, 1), np.int32)
+        n_new = c_int64(0)
+        try:
+            rc = self._l.pas_names_assign(self._h, n, _ptr(off), _ptr(self._blob(blob)),
+                                          _ptr(slot), cap, _ptr(new_entry), _ptr(new_slot),
+                                          byref(n_new))
+            new = self._assign_result(rc, "pas_names_assign", n_new, new_entry, new_slot)
+        except PasError as e:
+            e.slots = slot[:n] if slot is not None else None  # the plain lookups
+            raise
+        return (slot[:n] if slot is not None else None,) + new
+
+    def names_assign_device(self, n: int, n_bytes: int, name_off_t, bytes_t, slot_t,
+                            new_cap: Optional[int] = None, stream=None):
+        """The same with the names and the slots on the device: (new_entry, new_slot)."""
+        cap = n if new_cap is None else int(new_cap)
+        new_entry = np.zeros(max(cap, 1), np.int32)
+        new_slot = np.zeros(max(cap, 1), np.int32)
+        n_new = c_int64(0)
+        rc = self._l.pas_names_assign_device(
+            self._h, n, n_bytes, _dptr(name_off_t), _dptr(bytes_t), _dptr(slot_t), cap,
+            _ptr(new_entry), _ptr(new_slot), byref(n_new), _stream(stream))
+        return self._assign_result(rc, "pas_names_assign_device", n_new, new_entry, new_slot)
+
+    def names_resize(self, n_slots: int, stream=None):
+        self._check(self._l.pas_names_resize(self._h, n_slots, _stream(stream)),
+                    "pas_names_resize")
+
+    def names_remap(self, src_slot, stream=None):
+        """Renumber the table's slots with a compact map (pas_names_remap): new slot j holds
+        the name of old slot src_slot[j], or is spare for -1."""
+        src = np.ascontiguousarray(src_slot, dtype=np.int32).reshape(-1)
+        self._check(self._l.pas_names_remap(self._h, len(src), _ptr(src) if src.size else None,
+                                            _stream(stream)), "pas_names_remap")
+
+    def tas_snapshot_update_quantities_names(self, gen_from: int, gen_to: int, cols, col_off,
+                                             name_off, name_blob, lit_off, blob):
+        """tas_snapshot_update_quantities with each entry's node given by name
+        (snapshot.pack_names of the entries' node names): returns (kind, scale, n_unknown),
+        n_unknown the entries whose name has no slot."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        c_off = np.ascontiguousarray(col_off, dtype=np.int64).reshape(-1)
+        n_off = np.ascontiguousarray(name_off, dtype=np.int64).reshape(-1)
+        l_off = np.ascontiguousarray(lit_off, dtype=np.int64).reshape(-1)
+        assert len(c_off) == len(cols) + 1 and len(l_off) == len(n_off)
+        kind = np.zeros(max(len(cols), 1), np.int32)
+        scale = np.zeros(max(len(cols), 1), np.int32)
+        bad, unknown = c_int64(-1), c_int64(0)
+        rc = self._l.pas_tas_snapshot_update_quantities_names(
+            self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None, _ptr(c_off),
+            _ptr(n_off), _ptr(self._blob(name_blob)), _ptr(l_off), _ptr(self._blob(blob)),
+            _ptr(kind), _ptr(scale), byref(bad), byref(unknown))
+        return self._update_quantities_result(
+            rc, "pas_tas_snapshot_update_quantities_names", bad, kind[:len(cols)],
+            scale[:len(cols)]) + (unknown.value,)
+
+    def tas_snapshot_update_quantities_names_device(self, gen_from: int, gen_to: int, cols,
+                                                    col_off, n_name_bytes: int, name_off_t,
+                                                    name_bytes_t, n_bytes: int, lit_off_t,
+                                                    bytes_t, stream=None):
+        """The same with the name and literal arrays on the device.  Synchronous on the stream."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        c_off = np.ascontiguousarray(col_off, dtype=np.int64).reshape(-1)
+        assert len(c_off) == len(cols) + 1
+        kind = np.zeros(max(len(cols), 1), np.int32)
+        scale = np.zeros(max(len(cols), 1), np.int32)
+        bad, unknown = c_int64(-1), c_int64(0)
+        rc = self._l.pas_tas_snapshot_update_quantities_names_device(
+            self._h, gen_from, gen_to, len(cols), _ptr(cols) if cols.size else None, _ptr(c_off),
+            n_name_bytes, _dptr(name_off_t), _dptr(name_bytes_t), n_bytes, _dptr(lit_off_t),
+            _dptr(bytes_t), _ptr(kind), _ptr(scale), byref(bad), byref(unknown), _stream(stream))
+        return self._update_quantities_result(
+            rc, "pas_tas_snapshot_update_quantities_names_device", bad, kind[:len(cols)],
+            scale[:len(cols)]) + (unknown.value,)
 
     def tas_snapshot_wide_count(self) -> int:
         """Number of wide columns of the resident snapshot."""

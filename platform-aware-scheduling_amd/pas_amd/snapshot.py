@@ -135,6 +135,28 @@ def pack_quantities(metrics: Mapping[str, Mapping[str, str]], node_index: Mappin
     return col_off, entry_node, lit_off, blob
 
 
+def pack_names(nodes: Sequence):
+    """(name_off int64 [len(nodes) + 1], blob bytes) of node names end to end, for the name
+    table's calls (Context.names_set / names_resolve / names_assign /
+    tas_snapshot_update_quantities_names).  ASCII names, where the string length is the byte
+    length, take one join, one encode and one pass of len; anything else (non-ASCII str, bytes,
+    None for a spare slot = the empty name) is encoded name by name."""
+    n = len(nodes)
+    off = np.zeros(n + 1, np.int64)
+    try:
+        joined = "".join(nodes)
+        ascii_only = joined.isascii()
+    except TypeError:
+        ascii_only = False
+    if ascii_only:
+        blob = joined.encode()
+        np.cumsum(np.fromiter(map(len, nodes), np.int64, n), out=off[1:])
+        return off, blob
+    enc = [b"" if s is None else s.encode() if isinstance(s, str) else bytes(s) for s in nodes]
+    np.cumsum(np.fromiter(map(len, enc), np.int64, n), out=off[1:])
+    return off, b"".join(enc)
+
+
 def go_sort_strings(names):
     """sort.Strings: bytewise order of the UTF-8 encodings ("card10" < "card2")."""
     return sorted(names, key=lambda s: s.encode())

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from .context import quantity_to_wide, w64
-from .snapshot import pack_literals, tas_snapshot_from_metrics_wide
+from .snapshot import pack_literals, pack_names, tas_snapshot_from_metrics_wide
 
 METRIC_GROWTH = 8  # columns added when no free column is left
 
@@ -84,14 +84,28 @@ class TasCache:
     cache and snapshot as they were, as above), at most one reshape, and one
     pas_tas_snapshot_update_quantities for all its columns, in place of the narrow update, the
     wide update and the set_scale; `scale` and `wide` follow what that call reports.  The
-    snapshot it installs is the same."""
+    snapshot it installs is the same.
+
+    device_names=True (with device_ingest=True and slots=None, ValueError otherwise) also leaves
+    the node names to the device: the context's resident name table (pas_names_set, installed by
+    from_metrics; a cache built by hand expects the table to hold node_names) owns the slot
+    choice above.  After the literals are checked, one write or refresh issues one
+    pas_names_assign over its entries' names (first-seen names take the spare slots; when they
+    do not suffice the slot count grows by the rule above, pas_names_resize, and the assign is
+    repeated), updates node_names / node_index for the new names only, then at most one reshape
+    and one pas_tas_snapshot_update_quantities_names.  No dictionary is probed per entry.
+    compact() also applies its map to the table (pas_names_remap).  An empty node name in a
+    map raises ValueError before anything changes: the empty name marks a spare slot."""
 
     def __init__(self, ctx, gen: int, node_names: Sequence[Optional[str]],
                  metric_names: Sequence[Optional[str]], scale=None, wide=None, slots=None,
-                 device_ingest: bool = False):
+                 device_ingest: bool = False, device_names: bool = False):
+        if device_names and (not device_ingest or slots is not None):
+            raise ValueError("device_names needs device_ingest=True and slots=None")
         self.ctx, self.gen = ctx, gen
         self.slots = slots
         self.device_ingest = bool(device_ingest)
+        self.device_names = bool(device_names)
         self._undo: Dict[str, tuple] = {}  # device_ingest: data a pending write replaced
         self.node_names: List[Optional[str]] = list(node_names)
         self.node_index: Dict[str, int] = {n: i for i, n in enumerate(node_names)
@@ -110,18 +124,22 @@ class TasCache:
     def from_metrics(cls, ctx, gen: int, metrics: Mapping[str, Mapping[str, str]],
                      node_names: Optional[Sequence[str]] = None, spare_nodes: int = 0,
                      spare_metrics: int = 0, slots=None,
-                     device_ingest: bool = False) -> "TasCache":
+                     device_ingest: bool = False, device_names: bool = False) -> "TasCache":
         """A cache over a first snapshot, uploaded as generation gen: every entry of `metrics`
         as write_metric would take it (a non-empty map is data without a registration, an
         empty one a registration without data), over node_names (default: the maps' nodes in
         order of first appearance) plus spare_nodes spare slots and spare_metrics free
-        columns."""
+        columns.  device_names: the context's name table is installed over the same slots."""
+        if device_names and (not device_ingest or slots is not None):
+            raise ValueError("device_names needs device_ingest=True and slots=None")
         if slots is not None:
             names: List[Optional[str]] = list(slots.node_names)
         else:
             if node_names is None:
                 node_names = list(dict.fromkeys(n for mp in metrics.values() for n in (mp or {})))
             names = list(node_names) + [None] * int(spare_nodes)
+        if device_names and "" in names:
+            raise ValueError("device_names: the empty node name marks a spare slot")
         held = [name for name, mp in metrics.items() if mp]
         v, p, scale, wide = tas_snapshot_from_metrics_wide(metrics, names, held)
         extra = int(spare_metrics)
@@ -130,8 +148,10 @@ class TasCache:
         scale = np.concatenate([scale, np.full(extra, 3, np.int32)])
         ctx.tas_snapshot_set_wide(gen, v, p, scale, wide)
         cols = held + [None] * extra
+        if device_names:
+            ctx.names_set(*pack_names(names))
         self = cls(ctx, gen, names, cols, scale, [c in wide for c in range(len(cols))], slots,
-                   device_ingest)
+                   device_ingest, device_names)
         for name, mp in metrics.items():
             if mp:
                 self.data[name] = dict(mp)
@@ -208,6 +228,8 @@ class TasCache:
             src = [int(s) if s < n_old else -1 for s in src_node]
         self.ctx.tas_snapshot_compact(self.gen, self.gen + 1, src)
         self.gen += 1
+        if self.device_names:
+            self.ctx.names_remap(src)
         self.node_names = [self.node_names[s] if s >= 0 else None for s in src]
         self.node_index = {n: i for i, n in enumerate(self.node_names) if n is not None}
         if self.slots is not None:
@@ -238,11 +260,20 @@ class TasCache:
 
     def _flush(self, pending: Dict[str, Dict[str, str]]):
         """The device calls of one write or refresh: reshape, narrow update, wide update,
-        set_scale, each at most once (device_ingest: see _flush_literals)."""
+        set_scale, each at most once (device_ingest: see _flush_literals; device_names: the
+        node slots come from _assign_names, after the literals are checked)."""
+        if self.device_names and any("" in mp for mp in pending.values()):
+            self._restore_undo()
+            raise ValueError("device_names: the empty node name marks a spare slot")
         packed = self._check_literals(pending) if self.device_ingest and pending else None
         n_old, m_old = len(self.node_names), len(self.metric_names)
         # node slots
-        if self.slots is not None:
+        name_off = name_blob = None
+        if self.device_names:
+            if pending:
+                name_off, name_blob = pack_names(packed[2])
+                self._assign_names(packed[2], name_off, name_blob)
+        elif self.slots is not None:
             names = list(self.slots.node_names)
             names += [None] * (n_old - len(names))
             self.node_names = names
@@ -282,7 +313,7 @@ class TasCache:
         if not pending:
             return
         if packed is not None:
-            self._flush_literals(*packed)
+            self._flush_literals(*packed, name_off, name_blob)
             return
         # the columns, encoded as a from-scratch build encodes them
         order = sorted(pending, key=self.metric_index.__getitem__)
@@ -325,26 +356,61 @@ class TasCache:
         col_off, nodes, lit_off, blob = pack_literals(pending, order)
         status = self.ctx.quantities_to_wide(lit_off, blob)[3]
         bad = np.flatnonzero(status)
-        undo, self._undo = self._undo, {}
         if bad.size:
-            for name, (had, old) in undo.items():
-                if had:
-                    self.data[name] = old
-                else:
-                    self.data.pop(name, None)
+            self._restore_undo()
             at = int(bad[0])
             raise self._literal_error(int(status[at]), at, order, col_off, nodes, lit_off, blob)
+        self._undo = {}
         return order, col_off, nodes, lit_off, blob
 
-    def _flush_literals(self, order, col_off, nodes, lit_off, blob):
+    def _restore_undo(self):
+        """The maps the pending writes replaced, put back."""
+        undo, self._undo = self._undo, {}
+        for name, (had, old) in undo.items():
+            if had:
+                self.data[name] = old
+            else:
+                self.data.pop(name, None)
+
+    def _assign_names(self, nodes, name_off, name_blob):
+        """device_names: the slots of a flush's first-seen nodes, chosen by one pas_names_assign
+        over the entries' names (the table grows first when its spare slots do not suffice);
+        node_names / node_index follow for the new names only."""
+        n = len(self.node_names)
+        try:
+            _, new_entry, new_slot = self.ctx.names_assign(name_off, name_blob, len(nodes),
+                                                           want_slots=False)
+        except _lib.PasError as e:
+            if e.code != _lib.PAS_ECAPACITY:
+                raise
+            spare = n - len(self.node_index)
+            while spare < e.n_new:
+                grown = n + (max(64, n // 8) + 63) // 64 * 64
+                spare += grown - n
+                n = grown
+            self.ctx.names_resize(n)
+            _, new_entry, new_slot = self.ctx.names_assign(name_off, name_blob, len(nodes),
+                                                           want_slots=False)
+        self.node_names.extend([None] * (n - len(self.node_names)))
+        for entry, slot in zip(new_entry.tolist(), new_slot.tolist()):
+            self.node_names[slot] = nodes[entry]
+            self.node_index[nodes[entry]] = slot
+
+    def _flush_literals(self, order, col_off, nodes, lit_off, blob, name_off=None,
+                        name_blob=None):
         """One pas_tas_snapshot_update_quantities for the pending columns (slots and columns
-        are assigned, the snapshot has its new shape)."""
-        index = self.node_index
-        entry_node = np.fromiter((index.get(n, -1) for n in nodes), np.int32, len(nodes))
+        are assigned, the snapshot has its new shape); device_names: its _names form over the
+        packed node names, no lookup on the host."""
         cols = [self.metric_index[name] for name in order]
         try:
-            kind, scale = self.ctx.tas_snapshot_update_quantities(
-                self.gen, self.gen + 1, cols, col_off, entry_node, lit_off, blob)
+            if name_off is not None:
+                kind, scale, _ = self.ctx.tas_snapshot_update_quantities_names(
+                    self.gen, self.gen + 1, cols, col_off, name_off, name_blob, lit_off, blob)
+            else:
+                index = self.node_index
+                entry_node = np.fromiter((index.get(n, -1) for n in nodes), np.int32, len(nodes))
+                kind, scale = self.ctx.tas_snapshot_update_quantities(
+                    self.gen, self.gen + 1, cols, col_off, entry_node, lit_off, blob)
         except _lib.PasError as e:  # (_check_literals has parsed them all: not expected)
             at = getattr(e, "bad_entry", -1)
             if at < 0:
