@@ -1038,6 +1038,113 @@ int pas_gas_apply_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
                          const int32_t* d_cards_per_container, const int32_t* d_cards,
                          int32_t cards_ld, int32_t* d_status_out, void* hip_stream);
 
+/* Pod events from annotation strings.  Cache.handlePod gets a kind, the pod, the node's name
+ * and the pod's "gas-container-cards" annotation (node_resource_cache.go:493-538), and
+ * adjustPodResources checks its arguments (errBadArgs, :192-196), splits the annotation
+ * (strings.Split on "|" and ",", :241,253-256) and finds every listed card by name in the
+ * node's usage map.  The calls below take exactly that: per event the kind, the pod, the node
+ * (a slot, or its name) and the annotation's bytes; the device splits the annotation, resolves
+ * the card names against the resident card-name table (pas_gas_card_names_set below) and hands
+ * the ranks to the walker of pas_gas_apply, which runs unchanged.  Event e's annotation is
+ * ann_bytes[ann_off[e] .. ann_off[e + 1]) and, in the _names forms, its node's name
+ * node_name_bytes[node_name_off[e] .. node_name_off[e + 1]) (lookup only: the name table of
+ * pas_names_set does not change).  Host forms return PAS_EINVAL unless both offset arrays start
+ * at 0 and never decrease; _device forms read both ends of every span clamped into [0, n_bytes]
+ * and the end not before the begin, and n_containers clamped into [0, max_containers].
+ *
+ * The grammar (csrc/annotation_fixed.h, one routine for host and device): segments = 1 +
+ * count('|'), so the empty annotation is one empty segment, as Go's Split gives; an empty
+ * segment lists 0 cards; any other lists 1 + count(',') names, the empty names of "a,,b", "a,"
+ * and ",a" included.  Names are opaque bytes (byte 0 and bytes >= 0x80 are ordinary).
+ *
+ * Per event, in this order:
+ *   1. a kind outside {ADD, REMOVE} or a pod outside [0, n_pods): PAS_GAS_ERR_INPUT (the host
+ *      forms: PAS_EINVAL for the call, nothing changed);
+ *   2. segments != n_containers[pod], or (the _names forms) an empty node name:
+ *      PAS_GAS_ERR_BAD_ARGS, the reference's errBadArgs (:192-196); a pod without containers is
+ *      therefore always bad args;
+ *   3. node -1, or a name without a slot: PAS_GAS_OK and nothing changes (a node the snapshot
+ *      does not hold has no usage to adjust); any other slot outside [0, n_nodes):
+ *      PAS_GAS_ERR_INPUT (the host forms: PAS_EINVAL for the call);
+ *   4. no card listed at all: PAS_GAS_OK and nothing changes;
+ *   5. otherwise the event is pending (PAS_GAS_ANN_PENDING in verdict_out of the resolve form):
+ *      with L = n_cards[node] clamped into [0, k], every listed name gets the lowest rank r < L
+ *      whose name in the node's row of the card-name table has the same length and bytes, else
+ *      -1 (the names past L, parked cards, never match), and the event, with its counts and
+ *      ranks, is applied exactly as pas_gas_apply applies it: its status is that call's.
+ * Events are applied in call order, all or nothing per event, as in pas_gas_apply.
+ *
+ * PAS_ENOSNAP without a GAS snapshot, a card-name table or (the _names forms) a name table;
+ * PAS_EINVAL, the message naming the card-name table, unless that table has n_slots == n_nodes
+ * and k == max_cards of the resident snapshot.  gen_from is checked (PAS_ESTALE, nothing
+ * changed) and the snapshot moves to gen_to when the call returns PAS_OK, also when no event
+ * was pending.  The _device forms synchronize hip_stream once: the largest listed count of the
+ * pending events comes back to the host and sizes the rank rows (per-stream workspace; if it
+ * cannot be allocated: PAS_ENOMEM, nothing changed), as the refresh from Quantity literals
+ * reads its summary back.  They cannot validate the arrays: rules 1 and 3 give the statuses
+ * above, and nothing outside the call's arrays, the workspace and the resident arrays is read
+ * or written. */
+#define PAS_GAS_ERR_BAD_ARGS 4 /* node_resource_cache.go errBadArgs: nothing changes */
+#define PAS_GAS_ANN_PENDING (-1) /* verdict_out: rules 1-4 did not settle the event */
+int pas_gas_apply_annotations(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
+                              const int32_t* ev_kind, const int32_t* ev_pod,
+                              const int32_t* ev_node, int32_t n_pods, int32_t max_containers,
+                              const int64_t* req, const uint32_t* req_mask,
+                              const int32_t* n_containers, const int64_t* ann_off,
+                              const char* ann_bytes, int32_t* status_out /*[n_events]*/);
+int pas_gas_apply_annotations_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                     int32_t n_events, const int32_t* d_ev_kind,
+                                     const int32_t* d_ev_pod, const int32_t* d_ev_node,
+                                     int32_t n_pods, int32_t max_containers, const int64_t* d_req,
+                                     const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                     int64_t n_ann_bytes, const int64_t* d_ann_off,
+                                     const char* d_ann_bytes, int32_t* d_status_out,
+                                     void* hip_stream);
+int pas_gas_apply_annotations_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                    int32_t n_events, const int32_t* ev_kind,
+                                    const int32_t* ev_pod, const int64_t* node_name_off,
+                                    const char* node_name_bytes, int32_t n_pods,
+                                    int32_t max_containers, const int64_t* req,
+                                    const uint32_t* req_mask, const int32_t* n_containers,
+                                    const int64_t* ann_off, const char* ann_bytes,
+                                    int32_t* status_out /*[n_events]*/);
+int pas_gas_apply_annotations_names_device(
+    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events, const int32_t* d_ev_kind,
+    const int32_t* d_ev_pod, int64_t n_name_bytes, const int64_t* d_node_name_off,
+    const char* d_node_name_bytes, int32_t n_pods, int32_t max_containers, const int64_t* d_req,
+    const uint32_t* d_req_mask, const int32_t* d_n_containers, int64_t n_ann_bytes,
+    const int64_t* d_ann_off, const char* d_ann_bytes, int32_t* d_status_out, void* hip_stream);
+
+/* The parse alone, as pas_quantities_to_wide is for the refresh: reads the resident n_cards and
+ * the card-name table, writes nothing resident and has no kinds (rule 1 is the pod's range).
+ * verdict_out [E] is the status rules 1-4 give or PAS_GAS_ANN_PENDING, n_listed_out [E] the
+ * full listed count; cards_per_container_out [E][max_containers] holds the counts of the first
+ * max_containers segments (0 past the annotation's segments) and cards_out [E][cards_ld] the
+ * ranks of the first cards_ld listed cards (-1 past them), for every event: a node outside
+ * [0, n_nodes) has no label card, so all its ranks are -1.  cards_ld >= 1.  The _device form is
+ * asynchronous on hip_stream. */
+int pas_gas_annotations_resolve(pas_ctx* ctx, int32_t n_events, const int32_t* ev_pod,
+                                const int32_t* ev_node, int32_t n_pods,
+                                const int32_t* n_containers, int32_t max_containers,
+                                const int64_t* ann_off, const char* ann_bytes, int32_t cards_ld,
+                                int32_t* verdict_out, int32_t* n_listed_out,
+                                int32_t* cards_per_container_out, int32_t* cards_out);
+int pas_gas_annotations_resolve_device(pas_ctx* ctx, int32_t n_events, const int32_t* d_ev_pod,
+                                       const int32_t* d_ev_node, int32_t n_pods,
+                                       const int32_t* d_n_containers, int32_t max_containers,
+                                       int64_t n_ann_bytes, const int64_t* d_ann_off,
+                                       const char* d_ann_bytes, int32_t cards_ld,
+                                       int32_t* d_verdict_out, int32_t* d_n_listed_out,
+                                       int32_t* d_cards_per_container_out, int32_t* d_cards_out,
+                                       void* hip_stream);
+/* One annotation on the host, the same routine: *n_segments and *n_listed are always the full
+ * counts, cards_per_container [max_containers] is filled for the first max_containers segments
+ * and name_span [cap][2] = (begin, length) for the first cap names.  No context; PAS_EINVAL for
+ * a negative size or a missing array. */
+int pas_gas_annotation_parse(const char* bytes, int64_t len, int32_t max_containers,
+                             int64_t* n_segments, int32_t* cards_per_container,
+                             int64_t* n_listed, int64_t* name_span /*[cap][2]*/, int64_t cap);
+
 /* Read back the resident usage used[N][K][Q] and its generation. */
 int pas_gas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* used_out);
 /* Read back the resident n_cards [N] and cap_per_gpu [N][Q] and the generation. */
@@ -1539,6 +1646,53 @@ int pas_tas_snapshot_update_quantities_names_device(
     const char* d_name_bytes, int64_t n_bytes, const int64_t* d_lit_off, const char* d_bytes,
     int32_t* kind_out, int32_t* scale_out, int64_t* bad_entry, int64_t* n_unknown_out,
     void* hip_stream);
+
+/* ------------------------------------------------------------------------- */
+/* Resident card-name table: the names of the GAS snapshot's card slots      */
+/* ------------------------------------------------------------------------- */
+
+/* The reference keeps a node's usage by card name (nodeStatuses, node_resource_cache.go:64,
+ * 259-272) and reads a pod's cards as names (:253-256); card slots exist only here.  The table
+ * names them for pas_gas_apply_annotations: n_slots rows (node slots) of k card slots, row s in
+ * the order of used[s][.]: the label cards in sort.Strings order, then whatever the caller
+ * keeps behind them (parked cards, which a lookup never matches).  Names are opaque bytes of
+ * any length, byte 0 and bytes >= 0x80 included, and the empty name is a name like any other (a
+ * label "card0..card1" lists a card ""); an unused slot is an empty name past the node's
+ * n_cards.  The table belongs to the context, beside the GAS snapshot (pas_gas_snapshot_resize
+ * and _compact do not touch it: the caller resizes and remaps it with the same arguments).
+ * Every entry point answers PAS_ENOSNAP without a table and every change is synchronous.
+ * Storage is freed with the context.  PAS_ABI_VERSION is unchanged: additions only.
+ *
+ * set: name (s, c) is bytes[name_off[s * k + c] .. name_off[s * k + c + 1]); 1 <= k <=
+ * PAS_GAS_MAX_CARDS, name_off [n_slots * k + 1] starts at 0 and never decreases (PAS_EINVAL
+ * otherwise).  Built in fresh storage and swapped in: after any error the previous table, if
+ * any, is still valid. */
+int pas_gas_card_names_set(pas_ctx* ctx, int32_t n_slots, int32_t k, const int64_t* name_off,
+                           const char* bytes);
+/* Rewrite whole rows, in call order: row r of the call (name_off [n_rows * k + 1]) replaces slot
+ * row_slot[r]; a slot given twice keeps the later row.  A slot outside [0, n_slots) or a bad
+ * name_off is PAS_EINVAL, nothing changed.  The new bytes are appended to the table's byte
+ * pool and the old ones are dead; when the dead bytes pass the live ones the call gathers the
+ * pool on the device, so rows rewritten many times do not grow it without bound. */
+int pas_gas_card_names_update(pas_ctx* ctx, int32_t n_rows, const int32_t* row_slot,
+                              const int64_t* name_off, const char* bytes);
+/* Both sizes may only grow (PAS_EINVAL otherwise, or for k_new > PAS_GAS_MAX_CARDS); the spans
+ * are re-pitched on the device and the new entries are empty names. */
+int pas_gas_card_names_resize(pas_ctx* ctx, int32_t n_slots_new, int32_t k_new,
+                              void* hip_stream);
+/* Renumber the rows with the map of pas_gas_snapshot_compact / pas_names_remap: new row j is old
+ * row src_slot[j], or k empty names for -1; the entries >= 0 are strictly increasing and below
+ * n_slots, anything else is PAS_EINVAL.  The pool is gathered. */
+int pas_gas_card_names_remap(pas_ctx* ctx, int32_t n_slots_new, const int32_t* src_slot,
+                             void* hip_stream);
+/* Rows, card slots per row and the bytes the pool holds, dead ones included (each output may be
+ * NULL). */
+int pas_gas_card_names_info(const pas_ctx* ctx, int32_t* n_slots, int32_t* k, int64_t* n_bytes);
+/* The names packed in (slot, card) order: name_off_out [n_slots * k + 1] always, bytes_out [cap]
+ * when cap >= the live bytes, else PAS_ECAPACITY (the size needed is name_off_out[n_slots * k],
+ * and in the message; n_bytes of _info is always enough). */
+int pas_gas_card_names_get(pas_ctx* ctx, int64_t* name_off_out, char* bytes_out, int64_t cap);
+int pas_gas_card_names_drop(pas_ctx* ctx);
 
 /* ------------------------------------------------------------------------- */
 /* Instrumentation                                                           */

@@ -19,8 +19,6 @@
 // parse_literals does.  The table's layout may depend on arrival order; no output does.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -28,6 +26,7 @@
 #include "host_staging.h"
 #include "name_hash.h"
 #include "pas_internal.h"
+#include "span_pool.h"
 
 namespace pas {
 namespace {
@@ -304,42 +303,6 @@ __global__ void assign_repeats(int64_t n, const int32_t* __restrict__ first_of,
   slot[i] = slot[first_of[i]];  // (a first's entry: written by assign_commit, not here)
 }
 
-template <typename T>
-int scan_size(pas_ctx* ctx, size_t n, size_t* bytes) {
-  *bytes = 0;
-  PAS_HIP(ctx, rocprim::exclusive_scan(nullptr, *bytes, (const T*)nullptr, (T*)nullptr, T(0), n,
-                                       rocprim::plus<T>(), (hipStream_t) nullptr));
-  return PAS_OK;
-}
-
-template <typename T>
-int scan_run(pas_ctx* ctx, void* tmp, size_t bytes, const T* in, T* out, size_t n,
-             hipStream_t s) {
-  PAS_HIP(ctx, rocprim::exclusive_scan(tmp, bytes, in, out, T(0), n, rocprim::plus<T>(), s));
-  return PAS_OK;
-}
-
-void free_dev(void* p) {
-  if (p) (void)hipFree(p);
-}
-
-// Span arrays of `cap` slots (+ 1: the scans' last element), len all zero.
-int alloc_spans(pas_ctx* ctx, int64_t cap, int64_t** beg, int64_t** len, hipStream_t s) {
-  *beg = *len = nullptr;
-  const size_t bytes = sizeof(int64_t) * ((size_t)cap + 1);
-  hipError_t e = hipMalloc(beg, bytes);
-  if (e == hipSuccess) e = hipMalloc(len, bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(*len, 0, bytes, s);
-  if (e == hipSuccess) e = hipMemsetAsync(*beg, 0, bytes, s);
-  if (e != hipSuccess) {
-    free_dev(*beg);
-    free_dev(*len);
-    *beg = *len = nullptr;
-    return check_hip(ctx, e, "name table: span arrays");
-  }
-  return PAS_OK;
-}
-
 // A hash of `buckets` buckets over the named slots of t (its spans and pool in place),
 // replacing t.table; synchronous on s when the bucket count changes (the old table is freed).
 int rebuild_table(pas_ctx* ctx, NameTable& t, int64_t buckets, hipStream_t s) {
@@ -365,39 +328,8 @@ int rebuild_table(pas_ctx* ctx, NameTable& t, int64_t buckets, hipStream_t s) {
   return PAS_OK;
 }
 
-// Room for pool_used + more bytes; synchronous on s when the pool moves.
-int grow_pool(pas_ctx* ctx, NameTable& t, int64_t more, hipStream_t s) {
-  const int64_t need = t.pool_used + more;
-  if (need <= t.pool_cap) return PAS_OK;
-  const int64_t cap = std::max(need, 2 * t.pool_cap);
-  char* np = nullptr;
-  PAS_HIP(ctx, hipMalloc(&np, (size_t)cap));
-  hipError_t e = hipSuccess;
-  if (t.pool_used > 0)
-    e = hipMemcpyAsync(np, t.pool, (size_t)t.pool_used, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    free_dev(np);
-    return check_hip(ctx, e, "name table: pool copy");
-  }
-  free_dev(t.pool);
-  t.pool = np;
-  t.pool_cap = cap;
-  return PAS_OK;
-}
-
 int no_table(pas_ctx* ctx, const char* fn) {
   return set_error(ctx, PAS_ENOSNAP, std::string(fn) + ": no name table");
-}
-
-// offsets [n + 1] of a host form: from 0 and non-decreasing
-int check_csr(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
-              const std::string& fn) {
-  if (!off || off[0] != 0) return set_error(ctx, PAS_EINVAL, fn + ": offsets must start at 0");
-  for (int64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return set_error(ctx, PAS_EINVAL, fn + ": offsets decrease");
-  if (off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  return PAS_OK;
 }
 
 // pas_names_assign[_device] on device arrays (d_slot may be null), synchronous on s.
@@ -483,7 +415,7 @@ int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t*
     return set_error(ctx, PAS_EINVAL, "pas_names_assign: new names and null output arrays");
 
   // (d), (e): nothing has changed so far; from here the table does
-  if ((rc = grow_pool(ctx, t, new_bytes, s))) return rc;
+  if ((rc = grow_pool(ctx, t, new_bytes, s, "name table: pool copy"))) return rc;
   assign_spares<<<blocks_for(t.n_slots), kTpb, 0, s>>>(t.n_slots, n_new, d_sflag, d_srank,
                                                        d_spare);
   PAS_HIP(ctx, hipGetLastError());
@@ -562,7 +494,8 @@ int pas_names_set(pas_ctx* ctx, int32_t n_slots, const int64_t* name_off, const 
   auto build = [&]() -> int {
     int r = st.upload();
     if (r) return r;
-    if ((r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s))) return r;
+    if ((r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s, "name table: span arrays")))
+      return r;
     PAS_HIP(ctx, hipMalloc(&nt.pool, (size_t)nt.pool_cap));
     if (total > 0)
       PAS_HIP(ctx, hipMemcpyAsync(nt.pool, bytes, (size_t)total, hipMemcpyHostToDevice, s));
@@ -751,7 +684,8 @@ int pas_names_resize(pas_ctx* ctx, int32_t n_slots_new, void* hip_stream) {
   hipStream_t s = pick_stream(ctx, hip_stream);
   if (n_slots_new > t.slot_cap) {
     int64_t *beg, *len;
-    if ((rc = alloc_spans(ctx, n_slots_new, &beg, &len, s))) return rc;
+    if ((rc = alloc_spans(ctx, n_slots_new, &beg, &len, s, "name table: span arrays")))
+      return rc;
     const size_t old = sizeof(int64_t) * (size_t)t.n_slots;
     hipError_t e = hipSuccess;
     if (old) e = hipMemcpyAsync(beg, t.beg, old, hipMemcpyDeviceToDevice, s);
@@ -814,7 +748,7 @@ int pas_names_remap(pas_ctx* ctx, int32_t n_slots_new, const int32_t* src_slot,
   int32_t ctr[2] = {0, 0};
   int64_t bytes_new = 0;
   auto build = [&]() -> int {
-    int r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s);
+    int r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s, "name table: span arrays");
     if (r) return r;
     PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(int32_t) * 2, s));
     if (n2) {

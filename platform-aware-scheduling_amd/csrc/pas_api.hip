@@ -280,6 +280,7 @@ void pas_destroy(pas_ctx* ctx) {
   if (ctx->policies.viol) (void)hipFree(ctx->policies.viol);
   if (ctx->policies.viol_sync.ev) (void)hipEventDestroy(ctx->policies.viol_sync.ev);
   free_names(ctx->names);
+  free_gas_cards(ctx->gas_cards);
   if (ctx->names_sync.ev) (void)hipEventDestroy(ctx->names_sync.ev);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->gas_sync_fault) (void)hipHostFree(ctx->gas_sync_fault);
@@ -1943,6 +1944,273 @@ int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_ev
       return rc;
   }
   return gas_write_finish(ctx, gen_to, n_events > 0, st, fn);
+}
+
+// What the annotation forms share (pas_gas_annotations_resolve*, pas_gas_apply_annotations*):
+// the card-name table is there and has the resident snapshot's shape, and the name table is
+// there when the nodes come by name.  The caller has checked the snapshot.
+static int gas_annotations_tables(pas_ctx* ctx, bool by_name, const std::string& fn) {
+  const GasCardNames& t = ctx->gas_cards;
+  if (!t.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no card-name table");
+  if (by_name && !ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
+  if (t.n_slots != ctx->gas.n_nodes || t.k != ctx->gas.max_cards)
+    return set_error(ctx, PAS_EINVAL,
+                     fn + ": the card-name table is " + std::to_string(t.n_slots) + " x " +
+                         std::to_string(t.k) + ", the GAS snapshot " +
+                         std::to_string(ctx->gas.n_nodes) + " x " +
+                         std::to_string(ctx->gas.max_cards));
+  return PAS_OK;
+}
+
+// offsets [n + 1] of a host form's byte spans: from 0, non-decreasing, bytes when any
+static int check_spans(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
+                       const std::string& what) {
+  int rc = check_offsets(ctx, n, off, what);
+  if (rc) return rc;
+  if (off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, what + ": null bytes");
+  return PAS_OK;
+}
+
+int pas_gas_annotations_resolve_device(pas_ctx* ctx, int32_t n_events, const int32_t* d_ev_pod,
+                                       const int32_t* d_ev_node, int32_t n_pods,
+                                       const int32_t* d_n_containers, int32_t max_containers,
+                                       int64_t n_ann_bytes, const int64_t* d_ann_off,
+                                       const char* d_ann_bytes, int32_t cards_ld,
+                                       int32_t* d_verdict_out, int32_t* d_n_listed_out,
+                                       int32_t* d_cards_per_container_out, int32_t* d_cards_out,
+                                       void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_gas_annotations_resolve_device";
+  if (!ctx->gas.valid) return set_error(ctx, PAS_ENOSNAP, "no GAS snapshot uploaded");
+  int rc = gas_annotations_tables(ctx, false, fn);
+  if (rc) return rc;
+  if (n_events < 0 || n_pods < 0 || max_containers < 0 || cards_ld < 1 || n_ann_bytes < 0)
+    return set_error(ctx, PAS_EINVAL, fn + ": bad shape");
+  if (n_events > 0 &&
+      (!d_ev_pod || !d_ev_node || !d_ann_off || (n_ann_bytes > 0 && !d_ann_bytes) ||
+       (n_pods > 0 && !d_n_containers) || !d_verdict_out || !d_n_listed_out || !d_cards_out ||
+       (max_containers > 0 && !d_cards_per_container_out)))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  if ((rc = activate(ctx))) return rc;
+  return annotations_resolve_launch(ctx, n_events, nullptr, d_ev_pod, d_ev_node, 0, nullptr, n_pods,
+                                    d_n_containers, max_containers, n_ann_bytes, d_ann_off,
+                                    d_ann_bytes, cards_ld, d_verdict_out, d_n_listed_out,
+                                    d_cards_per_container_out, d_cards_out,
+                                    pick_stream(ctx, hip_stream));
+}
+
+int pas_gas_annotations_resolve(pas_ctx* ctx, int32_t n_events, const int32_t* ev_pod,
+                                const int32_t* ev_node, int32_t n_pods,
+                                const int32_t* n_containers, int32_t max_containers,
+                                const int64_t* ann_off, const char* ann_bytes, int32_t cards_ld,
+                                int32_t* verdict_out, int32_t* n_listed_out,
+                                int32_t* cards_per_container_out, int32_t* cards_out) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_gas_annotations_resolve";
+  if (!ctx->gas.valid) return set_error(ctx, PAS_ENOSNAP, "no GAS snapshot uploaded");
+  int rc = gas_annotations_tables(ctx, false, fn);
+  if (rc) return rc;
+  if (n_events < 0 || n_pods < 0 || max_containers < 0 || cards_ld < 1)
+    return set_error(ctx, PAS_EINVAL, fn + ": bad shape");
+  if (n_events == 0) return PAS_OK;
+  if (!ev_pod || !ev_node || (n_pods > 0 && !n_containers) || !verdict_out || !n_listed_out ||
+      !cards_out || (max_containers > 0 && !cards_per_container_out))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  if ((rc = check_spans(ctx, n_events, ann_off, ann_bytes, fn + ": ann_off"))) return rc;
+  if ((rc = activate(ctx))) return rc;
+  const size_t E = (size_t)n_events;
+  Staging st(ctx);
+  int32_t *d_pod, *d_node, *d_nc, *d_verdict, *d_listed, *d_cpc, *d_cards;
+  int64_t* d_off;
+  char* d_bytes;
+  st.in(d_pod, ev_pod, E);
+  st.in(d_node, ev_node, E);
+  st.in(d_nc, n_containers, (size_t)n_pods);
+  st.in(d_off, ann_off, E + 1);
+  st.in(d_bytes, ann_bytes, (size_t)ann_off[E]);
+  st.out(d_verdict, verdict_out, E);
+  st.out(d_listed, n_listed_out, E);
+  st.out(d_cpc, cards_per_container_out, E * (size_t)max_containers);
+  st.out(d_cards, cards_out, E * (size_t)cards_ld);
+  if ((rc = st.upload())) return rc;
+  rc = annotations_resolve_launch(ctx, n_events, nullptr, d_pod, d_node, 0, nullptr, n_pods, d_nc,
+                                  max_containers, ann_off[E], d_off, d_bytes, cards_ld, d_verdict,
+                                  d_listed, d_cpc, d_cards, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+// What the four apply forms share: the snapshot, its generation and the tables, then the checks
+// a host can make on either form's scalars and pointers (by_name: the nodes by name).
+static int gas_apply_annotations_check(pas_ctx* ctx, bool by_name, uint64_t gen_from,
+                                       int32_t n_events, const void* ev_kind, const void* ev_pod,
+                                       const void* ev_node, const void* node_name_off,
+                                       int32_t n_pods, int32_t max_containers, const void* req,
+                                       const void* req_mask, const void* n_containers,
+                                       const void* ann_off, const void* status_out,
+                                       const std::string& fn) {
+  int rc = check_gas_gen(ctx, gen_from);
+  if (rc) return rc;
+  if ((rc = gas_annotations_tables(ctx, by_name, fn))) return rc;
+  if (n_events < 0 || n_pods < 0 || max_containers < 0)
+    return set_error(ctx, PAS_EINVAL, fn + ": bad shape");
+  if (n_events > 0 && (!ev_kind || !ev_pod || !(by_name ? node_name_off : ev_node) || !ann_off ||
+                       !status_out || (n_pods > 0 && !n_containers) ||
+                       (max_containers > 0 && n_pods > 0 && (!req || !req_mask))))
+    return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  return PAS_OK;
+}
+
+static int gas_apply_annotations_device(pas_ctx* ctx, bool by_name, uint64_t gen_from,
+                                        uint64_t gen_to, int32_t n_events,
+                                        const int32_t* d_ev_kind,
+                                        const int32_t* d_ev_pod, const int32_t* d_ev_node,
+                                        int64_t n_name_bytes, const int64_t* d_node_name_off,
+                                        const char* d_node_name_bytes, int32_t n_pods,
+                                        int32_t max_containers, const int64_t* d_req,
+                                        const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                        int64_t n_ann_bytes, const int64_t* d_ann_off,
+                                        const char* d_ann_bytes, int32_t* d_status_out,
+                                        void* hip_stream, const std::string& fn) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = gas_apply_annotations_check(ctx, by_name, gen_from, n_events, d_ev_kind, d_ev_pod,
+                                       d_ev_node, d_node_name_off, n_pods, max_containers, d_req, d_req_mask,
+                                       d_n_containers, d_ann_off, d_status_out, fn);
+  if (rc) return rc;
+  if (n_ann_bytes < 0 || n_name_bytes < 0 || (n_events > 0 && n_ann_bytes > 0 && !d_ann_bytes) ||
+      (n_events > 0 && by_name && n_name_bytes > 0 && !d_node_name_bytes))
+    return set_error(ctx, PAS_EINVAL, fn + ": null bytes or a byte count < 0");
+  if ((rc = activate(ctx))) return rc;
+  if ((rc = gas_apply_annotations_launch(ctx, n_events, d_ev_kind, d_ev_pod,
+                                         by_name ? nullptr : d_ev_node, n_name_bytes, d_node_name_off, d_node_name_bytes, n_pods,
+                                         max_containers, d_req, d_req_mask, d_n_containers,
+                                         n_ann_bytes, d_ann_off, d_ann_bytes, d_status_out,
+                                         pick_stream(ctx, hip_stream))))
+    return rc;
+  return gas_stepped(ctx, gen_to);
+}
+
+int pas_gas_apply_annotations_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                     int32_t n_events, const int32_t* d_ev_kind,
+                                     const int32_t* d_ev_pod, const int32_t* d_ev_node,
+                                     int32_t n_pods, int32_t max_containers, const int64_t* d_req,
+                                     const uint32_t* d_req_mask, const int32_t* d_n_containers,
+                                     int64_t n_ann_bytes, const int64_t* d_ann_off,
+                                     const char* d_ann_bytes, int32_t* d_status_out,
+                                     void* hip_stream) {
+  return gas_apply_annotations_device(ctx, false, gen_from, gen_to, n_events, d_ev_kind, d_ev_pod,
+                                      d_ev_node, 0, nullptr, nullptr, n_pods, max_containers,
+                                      d_req, d_req_mask, d_n_containers, n_ann_bytes, d_ann_off,
+                                      d_ann_bytes, d_status_out, hip_stream,
+                                      "pas_gas_apply_annotations_device");
+}
+
+int pas_gas_apply_annotations_names_device(
+    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events, const int32_t* d_ev_kind,
+    const int32_t* d_ev_pod, int64_t n_name_bytes, const int64_t* d_node_name_off,
+    const char* d_node_name_bytes, int32_t n_pods, int32_t max_containers, const int64_t* d_req,
+    const uint32_t* d_req_mask, const int32_t* d_n_containers, int64_t n_ann_bytes,
+    const int64_t* d_ann_off, const char* d_ann_bytes, int32_t* d_status_out, void* hip_stream) {
+  return gas_apply_annotations_device(ctx, true, gen_from, gen_to, n_events, d_ev_kind, d_ev_pod,
+                                      nullptr, n_name_bytes, d_node_name_off, d_node_name_bytes,
+                                      n_pods, max_containers, d_req, d_req_mask, d_n_containers,
+                                      n_ann_bytes, d_ann_off, d_ann_bytes, d_status_out,
+                                      hip_stream, "pas_gas_apply_annotations_names_device");
+}
+
+// The host forms: validate (rules 1 and 3 are PAS_EINVAL for the call), upload, run the
+// _device forms' path, wait and copy status_out back.
+static int gas_apply_annotations_host(pas_ctx* ctx, bool by_name, uint64_t gen_from,
+                                      uint64_t gen_to, int32_t n_events, const int32_t* ev_kind,
+                                      const int32_t* ev_pod, const int32_t* ev_node,
+                                      const int64_t* node_name_off, const char* node_name_bytes,
+                                      int32_t n_pods, int32_t max_containers, const int64_t* req,
+                                      const uint32_t* req_mask, const int32_t* n_containers,
+                                      const int64_t* ann_off, const char* ann_bytes,
+                                      int32_t* status_out, const std::string& fn) {
+  if (!ctx) return PAS_EINVAL;
+  int rc = gas_apply_annotations_check(ctx, by_name, gen_from, n_events, ev_kind, ev_pod, ev_node,
+                                       node_name_off, n_pods, max_containers, req, req_mask,
+                                       n_containers, ann_off, status_out, fn);
+  if (rc) return rc;
+  const int32_t N = ctx->gas.n_nodes;
+  const size_t E = (size_t)n_events;
+  int64_t n_ann_bytes = 0, n_name_bytes = 0;
+  if (n_events > 0) {
+    if ((rc = check_spans(ctx, n_events, ann_off, ann_bytes, fn + ": ann_off"))) return rc;
+    n_ann_bytes = ann_off[E];
+    if (by_name) {
+      if ((rc = check_spans(ctx, n_events, node_name_off, node_name_bytes,
+                            fn + ": node_name_off")))
+        return rc;
+      n_name_bytes = node_name_off[E];
+    }
+  }
+  for (int32_t e = 0; e < n_events; ++e) {
+    if (ev_kind[e] != PAS_GAS_EV_ADD && ev_kind[e] != PAS_GAS_EV_REMOVE)
+      return set_error(ctx, PAS_EINVAL, fn + ": event kind out of range");
+    if (ev_pod[e] < 0 || ev_pod[e] >= n_pods)
+      return set_error(ctx, PAS_EINVAL, fn + ": pod index out of range");
+    if (!by_name && ev_node[e] != -1 && (ev_node[e] < 0 || ev_node[e] >= N))
+      return set_error(ctx, PAS_EINVAL, fn + ": node neither -1 nor a slot of the snapshot");
+    if ((rc = gas_pod_check(ctx, ev_pod[e], max_containers, req_mask, n_containers, fn.c_str())))
+      return rc;
+  }
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  PodBatch d;
+  int32_t *d_kind, *d_pod, *d_node, *d_status;
+  int64_t *d_name_off, *d_ann_off;
+  char *d_name_bytes, *d_ann_bytes;
+  stage_pods(st, d, n_pods, max_containers, req, req_mask, n_containers);
+  st.in(d_kind, ev_kind, E);
+  st.in(d_pod, ev_pod, E);
+  d_node = nullptr, d_name_off = nullptr, d_name_bytes = nullptr;
+  if (by_name) {
+    st.in(d_name_off, node_name_off, E + 1);
+    st.in(d_name_bytes, node_name_bytes, (size_t)n_name_bytes);
+  } else {
+    st.in(d_node, ev_node, E);
+  }
+  st.in(d_ann_off, ann_off, n_events > 0 ? E + 1 : 0);
+  st.in(d_ann_bytes, ann_bytes, (size_t)n_ann_bytes);
+  st.out(d_status, status_out, E);
+  if (n_events > 0) {
+    if ((rc = st.upload())) return rc;
+    if ((rc = gas_apply_annotations_launch(ctx, n_events, d_kind, d_pod, d_node, n_name_bytes,
+                                           d_name_off, d_name_bytes, n_pods, max_containers, d.req,
+                                           d.mask, d.nc, n_ann_bytes, d_ann_off, d_ann_bytes,
+                                           d_status, ctx->stream)))
+      return rc;
+  }
+  return gas_write_finish(ctx, gen_to, n_events > 0, st, fn);
+}
+
+int pas_gas_apply_annotations(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
+                              const int32_t* ev_kind, const int32_t* ev_pod,
+                              const int32_t* ev_node, int32_t n_pods, int32_t max_containers,
+                              const int64_t* req, const uint32_t* req_mask,
+                              const int32_t* n_containers, const int64_t* ann_off,
+                              const char* ann_bytes, int32_t* status_out) {
+  return gas_apply_annotations_host(ctx, false, gen_from, gen_to, n_events, ev_kind, ev_pod,
+                                    ev_node, nullptr, nullptr, n_pods, max_containers, req,
+                                    req_mask, n_containers, ann_off, ann_bytes, status_out,
+                                    "pas_gas_apply_annotations");
+}
+
+int pas_gas_apply_annotations_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                    int32_t n_events, const int32_t* ev_kind,
+                                    const int32_t* ev_pod, const int64_t* node_name_off,
+                                    const char* node_name_bytes, int32_t n_pods,
+                                    int32_t max_containers, const int64_t* req,
+                                    const uint32_t* req_mask, const int32_t* n_containers,
+                                    const int64_t* ann_off, const char* ann_bytes,
+                                    int32_t* status_out) {
+  return gas_apply_annotations_host(ctx, true, gen_from, gen_to, n_events, ev_kind, ev_pod,
+                                    nullptr, node_name_off, node_name_bytes, n_pods, max_containers, req,
+                                    req_mask, n_containers, ann_off, ann_bytes, status_out,
+                                    "pas_gas_apply_annotations_names");
 }
 
 // What pas_gas_place and pas_gas_place_device share: the checks a host can make on either

@@ -252,6 +252,30 @@ struct NameTable {
   int64_t buckets = 0;
 };
 
+// The resident card-name table (gas_cards.hip): the names of the card slots of every node slot,
+// beside the GAS snapshot struct and not in it (resize and compact replace that struct).  Row s
+// holds k entries in the order of used[s][.]: the label cards in sort.Strings order, then what
+// the caller keeps behind them (parked cards).  Entry (s, c) is pool[beg[s * k + c] ..
+// + len[s * k + c]); names are opaque bytes and the empty name is a name like any other.  The
+// span arrays hold n_slots * k + 1 entries (the scans' last element; len is 0 there).  A row
+// rewrite appends the new bytes to the pool and leaves the old ones dead: pool_used counts
+// both, live_bytes (the sum of row_bytes, the rows' byte totals kept on the host) the bytes
+// the spans still name.  When the dead bytes pass the live ones the pool is gathered.
+struct GasCardNames {
+  bool valid = false;
+  int32_t n_slots = 0;
+  int32_t k = 0;
+  int64_t* beg = nullptr;
+  int64_t* len = nullptr;
+  char* pool = nullptr;
+  int64_t pool_used = 0;
+  int64_t pool_cap = 0;
+  int64_t live_bytes = 0;
+  std::vector<int64_t> row_bytes;  // [n_slots]
+  std::vector<uint32_t> stamp;     // [n_slots] the last update call that named the slot
+  uint32_t stamp_clock = 0;
+};
+
 // slot_buf buffers
 enum SlotBuf {
   kBufGpass = 0,  // pass bitmaps of clusters past the LDS bitmap (tas_eval)
@@ -273,7 +297,13 @@ enum SlotBuf {
   // resolved slots, hashes, the first-seen scratch table, scan inputs and outputs of a name
   // lookup or assignment (name_table.hip)
   kBufNames = 9,
-  kSlotBufs = 10
+  // the parsed annotations of a pod-event batch (gas_annotations.hip): cards per container
+  // [E][max_containers] and card ranks [E][cards_ld], sized after the call's read-back
+  kBufAnnot = 10,
+  // the same batch's per-event words, sized before it: the largest pending list, verdicts,
+  // listed counts, the nodes handed to the walker and the slots of the nodes given by name
+  kBufAnnotEvents = 11,
+  kSlotBufs = 12
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -349,6 +379,7 @@ struct pas_ctx {
   pas::TasPolicies policies;
   pas::NameTable names;
   pas::DerivedSync names_sync;  // the last change of `names`: lookups on other streams wait
+  pas::GasCardNames gas_cards;  // (every change is synchronous: no event is needed)
   // counts the calls that can renumber or re-create the TAS snapshot's metric columns
   // (snapshot_set, reshape, drop): a policy table set at an older value is stale
   uint64_t tas_col_epoch = 1;
@@ -471,6 +502,35 @@ void free_names(NameTable& t);
 int names_resolve_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
                          const char* d_bytes, int32_t* d_slot, uint64_t* d_hash,
                          uint32_t* d_unknown, bool count_empty, hipStream_t s);
+// Card-name table (gas_cards.hip): every array of the table (pas_destroy).
+void free_gas_cards(GasCardNames& t);
+// Pod events from annotation strings (gas_annotations.hip).  annotations_resolve_launch: the
+// parse-alone form on device arrays, enqueued on s: per event the verdict of the rules of
+// pas_gas_apply_annotations (d_kind null: no kind is checked; d_name_off non-null: d_node holds
+// the slots of the nodes given by those names, and an empty name is bad args), the listed count,
+// the cards per container and the ranks of the first cards_ld listed cards of every event.
+// The caller has checked the snapshot and the card-name table.
+int annotations_resolve_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
+                               const int32_t* d_pod, const int32_t* d_node, int64_t n_name_bytes,
+                               const int64_t* d_name_off, int32_t n_pods, const int32_t* d_ncont,
+                               int32_t max_containers, int64_t n_ann_bytes,
+                               const int64_t* d_ann_off, const char* d_ann_bytes, int32_t cards_ld,
+                               int32_t* d_verdict, int32_t* d_n_listed, int32_t* d_cpc,
+                               int32_t* d_cards, hipStream_t s);
+// pas_gas_apply_annotations[_names][_device] on device arrays: the count pass, the call's one
+// read-back (s is synchronized), the rank pass into the slot's workspace, gas_apply_launch and
+// the status fix-up.  d_node: the events' slots, or null with the nodes given by name (d_name_off
+// / d_name_bytes, resolved through the name table, which the caller has checked like the
+// snapshot and the card-name table).  Nothing of the snapshot has changed when it returns an
+// error.
+int gas_apply_annotations_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
+                                 const int32_t* d_pod, const int32_t* d_node,
+                                 int64_t n_name_bytes, const int64_t* d_name_off,
+                                 const char* d_name_bytes, int32_t n_pods, int32_t max_containers,
+                                 const int64_t* d_req, const uint32_t* d_mask,
+                                 const int32_t* d_ncont, int64_t n_ann_bytes,
+                                 const int64_t* d_ann_off, const char* d_ann_bytes,
+                                 int32_t* d_status, hipStream_t s);
 // The resident snapshot gathered into storage of n_nodes_new (>= the resident count) x
 // n_metrics_new (tas_reshape.hip): new column m is old column src_col[m] or, for -1, empty
 // (src_col: host [n_metrics_new], distinct old columns or -1; the caller has checked it and

@@ -59,6 +59,8 @@ PAS_GAS_OK = 0
 PAS_GAS_WONT_FIT = 1
 PAS_GAS_ERR_INPUT = 2
 PAS_GAS_ERR_OVERFLOW = 3
+PAS_GAS_ERR_BAD_ARGS = 4
+PAS_GAS_ANN_PENDING = -1
 PAS_GAS_EV_ADD = 0
 PAS_GAS_EV_REMOVE = 1
 
@@ -275,6 +277,42 @@ SIGNATURES = {
         [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P,
          c_int32, _P, _P],
     ),
+    # pod events from annotation strings (csrc/gas_annotations.hip)
+    "pas_gas_apply_annotations": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P],
+    ),
+    "pas_gas_apply_annotations_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int64, _P,
+         _P, _P, _P],
+    ),
+    "pas_gas_apply_annotations_names": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P,
+         _P],
+    ),
+    "pas_gas_apply_annotations_names_device": (
+        c_int,
+        [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int64, _P, _P, c_int32, c_int32, _P, _P, _P,
+         c_int64, _P, _P, _P, _P],
+    ),
+    "pas_gas_annotations_resolve": (
+        c_int, [_P, c_int32, _P, _P, c_int32, _P, c_int32, _P, _P, c_int32, _P, _P, _P, _P]),
+    "pas_gas_annotations_resolve_device": (
+        c_int, [_P, c_int32, _P, _P, c_int32, _P, c_int32, c_int64, _P, _P, c_int32, _P, _P, _P,
+                _P, _P]),
+    "pas_gas_annotation_parse": (
+        c_int, [c_char_p, c_int64, c_int32, POINTER(c_int64), _P, POINTER(c_int64), _P, c_int64]),
+    # the resident card-name table (csrc/gas_cards.hip)
+    "pas_gas_card_names_set": (c_int, [_P, c_int32, c_int32, _P, _P]),
+    "pas_gas_card_names_update": (c_int, [_P, c_int32, _P, _P, _P]),
+    "pas_gas_card_names_resize": (c_int, [_P, c_int32, c_int32, _P]),
+    "pas_gas_card_names_remap": (c_int, [_P, c_int32, _P, _P]),
+    "pas_gas_card_names_info": (c_int, [_P, POINTER(c_int32), POINTER(c_int32),
+                                        POINTER(c_int64)]),
+    "pas_gas_card_names_get": (c_int, [_P, _P, _P, c_int64]),
+    "pas_gas_card_names_drop": (c_int, [_P]),
     "pas_gas_snapshot_get": (c_int, [_P, POINTER(c_uint64), _P]),
     "pas_gas_snapshot_get_nodes": (c_int, [_P, POINTER(c_uint64), _P, _P]),
     "pas_gas_snapshot_info": (c_int, [_P, POINTER(c_uint64), POINTER(c_int32), POINTER(c_int32),

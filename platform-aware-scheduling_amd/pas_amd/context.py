@@ -125,6 +125,27 @@ def name_hash(name) -> int:
     return _lib.load().pas_name_hash(b, len(b))
 
 
+def gas_annotation_parse(annotation, max_containers: Optional[int] = None,
+                         cap: Optional[int] = None):
+    """(n_segments, cards_per_container, n_listed, spans) of one "gas-container-cards" value
+    (str or bytes, no terminator needed) from the routine the device runs
+    (pas_gas_annotation_parse, csrc/annotation_fixed.h): the full segment and name counts, the
+    counts of the first max_containers segments (default: all) and the (begin, length) spans
+    of the first cap names (default: all)."""
+    b = annotation.encode() if isinstance(annotation, str) else bytes(annotation)
+    c = b.count(b"|") + 1 if max_containers is None else int(max_containers)
+    n = len(b) + 1 if cap is None else int(cap)
+    cpc = np.full(max(c, 1), -7, np.int32)
+    spans = np.full((max(n, 1), 2), -7, np.int64)
+    segs, listed = c_int64(), c_int64()
+    rc = _lib.load().pas_gas_annotation_parse(b, len(b), c, byref(segs), _ptr(cpc), byref(listed),
+                                              _ptr(spans), n)
+    if rc != _lib.PAS_OK:
+        raise PasError(rc, "pas_gas_annotation_parse")
+    return (segs.value, cpc[:min(c, segs.value)].tolist(), listed.value,
+            [tuple(x) for x in spans[:min(n, listed.value)].tolist()])
+
+
 def quantity_as_int64(q: str) -> int:
     """resource.Quantity.AsInt64 with `ok` ignored (gpuscheduler/utils.go:23)."""
     out = c_int64()
@@ -1238,6 +1259,164 @@ class Context:
             n_pods, max_containers, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), _dptr(cpc_t),
             _dptr(cards_t), cards_ld, _dptr(status_t), _stream(stream))
         self._check(rc, "pas_gas_apply_device")
+
+    # ---- pod events from annotation strings (csrc/gas_annotations.hip)
+    def _pod_batch(self, req, req_mask, n_containers):
+        req = np.ascontiguousarray(req, dtype=np.int64)
+        assert req.ndim == 3, "req is [P][C][Q]"
+        return (req, np.ascontiguousarray(req_mask, dtype=np.uint32),
+                np.ascontiguousarray(n_containers, dtype=np.int32))
+
+    def gas_apply_annotations(self, gen_from: int, gen_to: int, kinds, pods, nodes,
+                              req: np.ndarray, req_mask: np.ndarray, n_containers: np.ndarray,
+                              ann_off, ann_blob) -> np.ndarray:
+        """Pod events in order with the annotations as strings (pas_gas_apply_annotations):
+        event e is kinds[e] of pod pods[e] on node slot nodes[e] (-1: a node the snapshot does
+        not hold) with the annotation ann_blob[ann_off[e]:ann_off[e + 1]] (snapshot.pack_names
+        packs them); the cards are resolved against the card-name table on the device.
+        Returns statuses [E], PAS_GAS_ERR_BAD_ARGS included."""
+        req, req_mask, n_containers = self._pod_batch(req, req_mask, n_containers)
+        p, c, _ = req.shape
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        pods = np.ascontiguousarray(pods, dtype=np.int32)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        off, e = self._csr(ann_off)
+        assert kinds.shape == (e,) and pods.shape == (e,) and nodes.shape == (e,)
+        st = np.zeros(max(e, 1), np.int32)
+        rc = self._l.pas_gas_apply_annotations(
+            self._h, gen_from, gen_to, e, _ptr(kinds), _ptr(pods), _ptr(nodes), p, c, _ptr(req),
+            _ptr(req_mask), _ptr(n_containers), _ptr(off), _ptr(self._blob(ann_blob)), _ptr(st))
+        self._check(rc, "pas_gas_apply_annotations")
+        return st[:e]
+
+    def gas_apply_annotations_names(self, gen_from: int, gen_to: int, kinds, pods, node_name_off,
+                                    node_name_blob, req: np.ndarray, req_mask: np.ndarray,
+                                    n_containers: np.ndarray, ann_off, ann_blob) -> np.ndarray:
+        """The same with each event's node given by name, resolved through the name table
+        (pas_gas_apply_annotations_names): a name without a slot is an event that succeeds and
+        changes nothing, an empty name PAS_GAS_ERR_BAD_ARGS."""
+        req, req_mask, n_containers = self._pod_batch(req, req_mask, n_containers)
+        p, c, _ = req.shape
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        pods = np.ascontiguousarray(pods, dtype=np.int32)
+        off, e = self._csr(ann_off)
+        n_off, e2 = self._csr(node_name_off)
+        assert kinds.shape == (e,) and pods.shape == (e,) and e2 == e
+        st = np.zeros(max(e, 1), np.int32)
+        rc = self._l.pas_gas_apply_annotations_names(
+            self._h, gen_from, gen_to, e, _ptr(kinds), _ptr(pods), _ptr(n_off),
+            _ptr(self._blob(node_name_blob)), p, c, _ptr(req), _ptr(req_mask), _ptr(n_containers),
+            _ptr(off), _ptr(self._blob(ann_blob)), _ptr(st))
+        self._check(rc, "pas_gas_apply_annotations_names")
+        return st[:e]
+
+    def gas_apply_annotations_device(self, gen_from: int, gen_to: int, n_events: int, kinds_t,
+                                     pods_t, nodes_t, n_pods: int, max_containers: int, req_t,
+                                     mask_t, ncont_t, n_ann_bytes: int, ann_off_t, ann_bytes_t,
+                                     status_t, stream=None):
+        """pas_gas_apply_annotations_device on device tensors: synchronizes the stream once (the
+        rank rows' length comes back), the statuses are in status_t once the stream has run."""
+        rc = self._l.pas_gas_apply_annotations_device(
+            self._h, gen_from, gen_to, n_events, _dptr(kinds_t), _dptr(pods_t), _dptr(nodes_t),
+            n_pods, max_containers, _dptr(req_t), _dptr(mask_t), _dptr(ncont_t), n_ann_bytes,
+            _dptr(ann_off_t), _dptr(ann_bytes_t), _dptr(status_t), _stream(stream))
+        self._check(rc, "pas_gas_apply_annotations_device")
+
+    def gas_apply_annotations_names_device(self, gen_from: int, gen_to: int, n_events: int,
+                                           kinds_t, pods_t, n_name_bytes: int, name_off_t,
+                                           name_bytes_t, n_pods: int, max_containers: int, req_t,
+                                           mask_t, ncont_t, n_ann_bytes: int, ann_off_t,
+                                           ann_bytes_t, status_t, stream=None):
+        rc = self._l.pas_gas_apply_annotations_names_device(
+            self._h, gen_from, gen_to, n_events, _dptr(kinds_t), _dptr(pods_t), n_name_bytes,
+            _dptr(name_off_t), _dptr(name_bytes_t), n_pods, max_containers, _dptr(req_t),
+            _dptr(mask_t), _dptr(ncont_t), n_ann_bytes, _dptr(ann_off_t), _dptr(ann_bytes_t),
+            _dptr(status_t), _stream(stream))
+        self._check(rc, "pas_gas_apply_annotations_names_device")
+
+    def gas_annotations_resolve(self, pods, nodes, n_containers, max_containers: int, ann_off,
+                                ann_blob, cards_ld: int):
+        """The parse alone (pas_gas_annotations_resolve): (verdict [E], n_listed [E],
+        cards_per_container [E][max_containers], cards [E][cards_ld]); verdict is the status of
+        the rules that need no card name or PAS_GAS_ANN_PENDING."""
+        pods = np.ascontiguousarray(pods, dtype=np.int32)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        ncont = np.ascontiguousarray(n_containers, dtype=np.int32)
+        off, e = self._csr(ann_off)
+        assert pods.shape == (e,) and nodes.shape == (e,)
+        c, ld = int(max_containers), int(cards_ld)
+        verdict = np.zeros(max(e, 1), np.int32)
+        listed = np.zeros(max(e, 1), np.int32)
+        cpc = np.zeros((max(e, 1), max(c, 1)), np.int32)
+        cards = np.zeros((max(e, 1), max(ld, 1)), np.int32)
+        rc = self._l.pas_gas_annotations_resolve(
+            self._h, e, _ptr(pods), _ptr(nodes), len(ncont), _ptr(ncont), c, _ptr(off),
+            _ptr(self._blob(ann_blob)), ld, _ptr(verdict), _ptr(listed),
+            _ptr(cpc.reshape(-1)[:max(e * c, 1)]), _ptr(cards))
+        self._check(rc, "pas_gas_annotations_resolve")
+        flat = cpc.reshape(-1)[:e * c].reshape(e, c)
+        return verdict[:e], listed[:e], flat, cards[:e]
+
+    def gas_annotations_resolve_device(self, n_events: int, pods_t, nodes_t, n_pods: int, ncont_t,
+                                       max_containers: int, n_ann_bytes: int, ann_off_t,
+                                       ann_bytes_t, cards_ld: int, verdict_t, listed_t, cpc_t,
+                                       cards_t, stream=None):
+        rc = self._l.pas_gas_annotations_resolve_device(
+            self._h, n_events, _dptr(pods_t), _dptr(nodes_t), n_pods, _dptr(ncont_t),
+            max_containers, n_ann_bytes, _dptr(ann_off_t), _dptr(ann_bytes_t), cards_ld,
+            _dptr(verdict_t), _dptr(listed_t), _dptr(cpc_t), _dptr(cards_t), _stream(stream))
+        self._check(rc, "pas_gas_annotations_resolve_device")
+
+    # ---- the resident card-name table (csrc/gas_cards.hip)
+    def gas_card_names_set(self, n_slots: int, k: int, name_off, blob):
+        """Install the card-name table (pas_gas_card_names_set): n_slots rows of k names, name
+        (s, c) = blob[name_off[s * k + c]:name_off[s * k + c + 1]] (snapshot.pack_card_names)."""
+        off, n = self._csr(name_off)
+        assert n == n_slots * k, "name_off holds n_slots * k + 1 entries"
+        self._check(self._l.pas_gas_card_names_set(self._h, n_slots, k, _ptr(off),
+                                                   _ptr(self._blob(blob))),
+                    "pas_gas_card_names_set")
+
+    def gas_card_names_update(self, row_slot, name_off, blob):
+        """Rewrite whole rows in call order (pas_gas_card_names_update): row r of name_off /
+        blob replaces slot row_slot[r]; a slot given twice keeps the later row."""
+        rows = np.ascontiguousarray(row_slot, dtype=np.int32).reshape(-1)
+        off, _ = self._csr(name_off)
+        self._check(self._l.pas_gas_card_names_update(
+            self._h, len(rows), _ptr(rows) if rows.size else None, _ptr(off),
+            _ptr(self._blob(blob))), "pas_gas_card_names_update")
+
+    def gas_card_names_resize(self, n_slots: int, k: int, stream=None):
+        self._check(self._l.pas_gas_card_names_resize(self._h, n_slots, k, _stream(stream)),
+                    "pas_gas_card_names_resize")
+
+    def gas_card_names_remap(self, src_slot, stream=None):
+        """Renumber the table's rows with a compact map (pas_gas_card_names_remap)."""
+        src = np.ascontiguousarray(src_slot, dtype=np.int32).reshape(-1)
+        self._check(self._l.pas_gas_card_names_remap(
+            self._h, len(src), _ptr(src) if src.size else None, _stream(stream)),
+            "pas_gas_card_names_remap")
+
+    def gas_card_names_info(self):
+        """(n_slots, k, n_bytes) of the card-name table; n_bytes counts the pool's dead bytes
+        too."""
+        n, k, b = c_int32(), c_int32(), c_int64()
+        self._check(self._l.pas_gas_card_names_info(self._h, byref(n), byref(k), byref(b)),
+                    "pas_gas_card_names_info")
+        return n.value, k.value, b.value
+
+    def gas_card_names_get(self):
+        """(name_off int64 [n_slots * k + 1], blob bytes): the names packed in (slot, card)
+        order."""
+        n, k, nb = self.gas_card_names_info()
+        off = np.zeros(n * k + 1, np.int64)
+        buf = np.zeros(max(nb, 1), np.uint8)
+        self._check(self._l.pas_gas_card_names_get(self._h, _ptr(off), _ptr(buf), nb),
+                    "pas_gas_card_names_get")
+        return off, buf[:int(off[-1])].tobytes()
+
+    def gas_card_names_drop(self):
+        self._check(self._l.pas_gas_card_names_drop(self._h), "pas_gas_card_names_drop")
 
     def gas_snapshot_get(self):
         """(generation, used [N][K][Q]) of the resident GAS snapshot."""

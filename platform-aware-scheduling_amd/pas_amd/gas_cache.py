@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .snapshot import card_remap, gas_node_row, parse_annotation
+from .snapshot import card_remap, gas_node_row, pack_card_names, pack_names, parse_annotation
 
 CARD_ANNOTATION = "gas-container-cards"  # cardAnnotationName (scheduler.go)
 
@@ -31,7 +31,7 @@ BAD_ARGS = "bad_args"    # errBadArgs: segment count != container count, or no n
 ERR_INPUT = "input"      # errInput (PAS_GAS_ERR_INPUT)
 ERR_OVERFLOW = "overflow"  # errOverflow (PAS_GAS_ERR_OVERFLOW)
 _STATUS = {_lib.PAS_GAS_OK: OK, _lib.PAS_GAS_ERR_INPUT: ERR_INPUT,
-           _lib.PAS_GAS_ERR_OVERFLOW: ERR_OVERFLOW}
+           _lib.PAS_GAS_ERR_OVERFLOW: ERR_OVERFLOW, _lib.PAS_GAS_ERR_BAD_ARGS: BAD_ARGS}
 
 
 def pod_key(pod: dict) -> str:
@@ -122,24 +122,48 @@ class GasCache:
     is left, by max(64, N / 8) slots rounded up to 64, and when a label lists more cards than
     max_cards, to the next of 8 / 16 / 64; parking never grows it.  card_names is changed in
     place (a GASExtender sharing the list sees the changes; GASExtender.nodes_changed takes
-    the new node_names)."""
+    the new node_names).
+
+    device_events=True leaves the string work of a pod event to the device, as handlePod gets
+    it: construction installs the context's card-name table (pas_gas_card_names_set: row slot =
+    card_names[slot] + parked[slot]) and its node-name table (pas_names_set, spare slots as
+    empty names; a node named "" is a ValueError, as in TasCache), and a pod batch is one
+    pas_gas_apply_annotations_names call over the events' node names and annotation strings.
+    The host keeps the annotatedPods decision and requests(pod) and nothing else: no split, no
+    node lookup, no card lookup, and errBadArgs, the unknown node and the annotation without
+    cards are answered by the device in the same batch (so every item that is not skipped
+    takes part in the one-event-per-key rule).  Node items send their rows to the card-name
+    table beside pas_gas_nodes_update, a first-seen node takes its slot through
+    pas_names_assign (the lowest spare slot, which is the slot chosen here), and growth,
+    compact and rebuild keep both tables in step.  Outcomes, annotated, card_names, parked and
+    the resident usage are those of the default mode.  max_cards names the snapshot's card
+    slots per node when the context cannot tell (from_nodes passes it)."""
 
     def __init__(self, ctx, gen: int, node_names: Sequence[str],
                  card_names: Sequence[Sequence[str]], kinds: Sequence[str],
                  n_cards=None, cap=None,
-                 requests: Optional[Callable[[dict], Tuple[np.ndarray, np.ndarray, int]]] = None):
+                 requests: Optional[Callable[[dict], Tuple[np.ndarray, np.ndarray, int]]] = None,
+                 device_events: bool = False, max_cards: Optional[int] = None):
+        if device_events and "" in node_names:
+            raise ValueError("device_events: the empty node name marks a spare slot")
         self.ctx, self.gen = ctx, gen
         self.node_names: List[Optional[str]] = list(node_names)
         self.node_index = {n: i for i, n in enumerate(node_names) if n is not None}
         self.card_names = card_names
         self.parked: List[List[str]] = [[] for _ in self.node_names]
-        self.max_cards: Optional[int] = None  # resolved by the first node event (_k)
+        self.max_cards: Optional[int] = max_cards  # None: resolved by the first use (_k)
         self.kinds = list(kinds)
         self.n_cards, self.cap = n_cards, cap
         self._rows_owned = False  # n_cards / cap are copies this cache may write
         self._requests = requests if requests is not None else self._decode_requests
         self.annotated: Dict[str, str] = {}  # annotatedPods
         self._queue: List[Tuple[str, dict, str]] = []  # (action, pod or node, annotation)
+        self.device_events = bool(device_events)
+        if self.device_events:
+            k = self._k()
+            ctx.gas_card_names_set(len(self.node_names), k,
+                                   *pack_card_names(self.card_names, self.parked, k))
+            ctx.names_set(*pack_names(self.node_names))
 
     @classmethod
     def from_nodes(cls, ctx, gen: int, nodes: Sequence[dict], kinds: Sequence[str],
@@ -157,10 +181,8 @@ class GasCache:
             n_cards[i], cap[i] = nc, c
         card_names = [cards for _, _, cards in rows] + [[] for _ in range(int(spare_nodes))]
         ctx.gas_snapshot_set(gen, n_cards, cap, np.zeros((n, k, q), np.int64))
-        self = cls(ctx, gen, names + [None] * int(spare_nodes), card_names, kinds,
-                   n_cards=n_cards, cap=cap, **kw)
-        self.max_cards = k
-        return self
+        return cls(ctx, gen, names + [None] * int(spare_nodes), card_names, kinds,
+                   n_cards=n_cards, cap=cap, max_cards=k, **kw)
 
     def _decode_requests(self, pod: dict):
         from . import wire
@@ -190,17 +212,22 @@ class GasCache:
         pod's usage: adjustPodResources(add) in bindNode sets annotatedPods[key]."""
         self.annotated[pod_key(pod)] = annotation
 
+    def _queue_node(self, action: str, node: dict):
+        if self.device_events and _node_name(node) == "":
+            raise ValueError("device_events: the empty node name marks a spare slot")
+        self._queue.append((action, node, ""))
+
     def add_node(self, node: dict):
         """A node the lister now knows (or knows again)."""
-        self._queue.append((NODE_ADDED, node, ""))
+        self._queue_node(NODE_ADDED, node)
 
     def update_node(self, old_node: Optional[dict], new_node: dict):
         """A changed node: its cards label or its allocatable."""
-        self._queue.append((NODE_UPDATED, new_node, ""))
+        self._queue_node(NODE_UPDATED, new_node)
 
     def delete_node(self, node: dict):
         """A node the lister no longer knows: every fit on it is the FetchNode error."""
-        self._queue.append((NODE_DELETED, node, ""))
+        self._queue_node(NODE_DELETED, node)
 
     # ------------------------------------------------------------ node items
     def _k(self) -> int:
@@ -215,6 +242,9 @@ class GasCache:
         """pas_gas_snapshot_resize, and the host tables with it."""
         self.ctx.gas_snapshot_resize(self.gen, self.gen + 1, n_nodes, max_cards)
         self.gen += 1
+        if self.device_events:
+            self.ctx.gas_card_names_resize(n_nodes, max_cards)
+            self.ctx.names_resize(n_nodes)
         extra = n_nodes - len(self.node_names)
         self.node_names.extend([None] * extra)
         self.card_names.extend([] for _ in range(extra))  # in place: the extender shares it
@@ -229,8 +259,9 @@ class GasCache:
 
     def _plan_node(self, action: str, node: dict, send_pending):
         """One node item on the host tables: (outcome, update) with update = (slot, n_cards,
-        cap [Q], src [max_cards]) or None when nothing is sent.  send_pending() sends the node
-        updates planned so far; it runs before the snapshot has to grow."""
+        cap [Q], src [max_cards], the row's card names) or None when nothing is sent.
+        send_pending() sends the node updates planned so far; it runs before the snapshot has
+        to grow."""
         name = _node_name(node)
         slot = self.node_index.get(name)
         if action == NODE_DELETED:
@@ -255,6 +286,9 @@ class GasCache:
             slot = spare
             self.node_names[slot] = name
             self.node_index[name] = slot
+            if self.device_events:  # the name table's rule is this one: the lowest spare slot
+                _, _, new_slot = self.ctx.names_assign(*pack_names([name]), 1, want_slots=False)
+                assert list(new_slot) == [slot], (name, slot, list(new_slot))
         old_slots = list(self.card_names[slot]) + self.parked[slot]
         if action == NODE_DELETED:  # the row stays where it is, every card parked
             src, slots, dropped = list(range(k)), old_slots, []
@@ -269,15 +303,20 @@ class GasCache:
                 self._rows_owned = True
             self.n_cards[slot], self.cap[slot] = n_cards, cap
         outcome = OK if not dropped else "dropped: " + ", ".join(dropped)
-        return outcome, (slot, n_cards, cap, src)
+        return outcome, (slot, n_cards, cap, src, list(slots))
 
     def _send_nodes(self, updates) -> List[int]:
-        """One pas_gas_nodes_update call for the planned updates, in order."""
+        """One pas_gas_nodes_update call for the planned updates, in order (device_events: and
+        one pas_gas_card_names_update with the rows' names as each update left them)."""
         st = self.ctx.gas_nodes_update(self.gen, self.gen + 1, [u[0] for u in updates],
                                        [u[1] for u in updates],
                                        np.array([u[2] for u in updates], np.int64),
                                        np.array([u[3] for u in updates], np.int32))
         self.gen += 1
+        if self.device_events:
+            self.ctx.gas_card_names_update(
+                [u[0] for u in updates],
+                *pack_card_names([u[4] for u in updates], None, self._k()))
         return [int(s) for s in st]
 
     # ------------------------------------------------------------ the worker
@@ -289,6 +328,9 @@ class GasCache:
         if add == (key in self.annotated):  # already present / already gone
             return SKIPPED
         req, mask, ncont = self._requests(pod)
+        if self.device_events:  # handlePod's arguments as they are: the device does the rest
+            kind = _lib.PAS_GAS_EV_ADD if add else _lib.PAS_GAS_EV_REMOVE
+            return kind, (pod.get("spec") or {}).get("nodeName") or "", req, mask, ncont, annotation
         segments = annotation.split("|")
         node_name = (pod.get("spec") or {}).get("nodeName") or ""
         if len(segments) != ncont or node_name == "":
@@ -309,14 +351,26 @@ class GasCache:
                 self.annotated.pop(key, None)
 
     def _send(self, batch) -> List[int]:
-        """One pas_gas_apply call for the batch's events, pod e = event e."""
+        """One pas_gas_apply call for the batch's events, pod e = event e (device_events: one
+        pas_gas_apply_annotations_names call over the node names and annotation strings)."""
         e = len(batch)
         q = len(self.kinds)
         c = max(1, max(ev[4] for ev in batch))
-        ld = max(1, max(len(ev[6]) for ev in batch))
         req = np.zeros((e, c, q), np.int64)
         mask = np.zeros((e, c), np.uint32)
         ncont = np.zeros(e, np.int32)
+        if self.device_events:
+            for i, (_, _, r, m, nc, _) in enumerate(batch):
+                ncont[i] = nc
+                req[i, :nc] = np.asarray(r, np.int64).reshape(-1, q)[:nc]
+                mask[i, :nc] = np.asarray(m, np.uint32)[:nc]
+            st = self.ctx.gas_apply_annotations_names(
+                self.gen, self.gen + 1, np.fromiter((ev[0] for ev in batch), np.int32, e),
+                np.arange(e, dtype=np.int32), *pack_names([ev[1] for ev in batch]), req, mask,
+                ncont, *pack_names([ev[5] for ev in batch]))
+            self.gen += 1
+            return [int(s) for s in st]
+        ld = max(1, max(len(ev[6]) for ev in batch))
         cpc = np.zeros((e, c), np.int32)
         cards = np.full((e, ld), -1, np.int32)
         kinds = np.zeros(e, np.int32)
@@ -406,6 +460,9 @@ class GasCache:
         src += [-1] * int(spare_nodes)
         self.ctx.gas_snapshot_compact(self.gen, self.gen + 1, src)
         self.gen += 1
+        if self.device_events:
+            self.ctx.gas_card_names_remap(src)
+            self.ctx.names_remap(src)
         self.node_names = [self.node_names[s] if s >= 0 else None for s in src]
         self.node_index = {n: i for i, n in enumerate(self.node_names) if n is not None}
         self.card_names[:] = [self.card_names[s] if s >= 0 else [] for s in src]
@@ -430,6 +487,11 @@ class GasCache:
         self.gen += 1
         self.ctx.gas_snapshot_set(self.gen, n_cards, cap,
                                   np.zeros((len(n_cards), k, len(self.kinds)), np.int64))
+        if self.device_events:  # the rows whose parked names go
+            rows = [s for s, p in enumerate(self.parked) if p]
+            if rows:
+                self.ctx.gas_card_names_update(
+                    rows, *pack_card_names([self.card_names[s] for s in rows], None, k))
         self.parked = [[] for _ in self.node_names]
         self.annotated.clear()
         self._queue = []

@@ -157,6 +157,22 @@ def pack_names(nodes: Sequence):
     return off, b"".join(enc)
 
 
+def pack_card_names(card_names: Sequence[Sequence], parked: Optional[Sequence[Sequence]],
+                    k: int):
+    """(name_off int64 [len(card_names) * k + 1], blob bytes) for the card-name table's calls
+    (Context.gas_card_names_set / gas_card_names_update): row s is card_names[s] followed by
+    parked[s] (parked may be None), padded with empty names to k entries.  A row of more than k
+    names is a ValueError."""
+    flat: List = []
+    for s, cards in enumerate(card_names):
+        row = list(cards) + (list(parked[s]) if parked is not None else [])
+        if len(row) > k:
+            raise ValueError(f"row {s}: {len(row)} card names > k = {k}")
+        flat.extend(row)
+        flat.extend([""] * (k - len(row)))
+    return pack_names(flat)
+
+
 def go_sort_strings(names):
     """sort.Strings: bytewise order of the UTF-8 encodings ("card10" < "card2")."""
     return sorted(names, key=lambda s: s.encode())
