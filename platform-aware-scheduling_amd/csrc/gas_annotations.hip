@@ -27,6 +27,7 @@
 #include <string>
 
 #include "annotation_fixed.h"
+#include "csr_entry.h"
 #include "pas_internal.h"
 
 namespace pas {
@@ -35,19 +36,6 @@ namespace {
 constexpr int kTpb = 256;
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTpb - 1) / kTpb); }
-
-__device__ __forceinline__ int64_t clamp_off(int64_t v, int64_t n) {
-  return v < 0 ? 0 : v > n ? n : v;
-}
-
-// Entry i of a CSR batch: bytes[*b .. *b + return), both ends clamped into [0, n_bytes] and
-// the end not before the begin (tas_ingest.hip reads its literals so).
-__device__ __forceinline__ int64_t entry_span(const int64_t* __restrict__ off, int64_t n_bytes,
-                                              int64_t i, int64_t* b) {
-  *b = clamp_off(off[i], n_bytes);
-  const int64_t e = clamp_off(off[i + 1], n_bytes);
-  return e < *b ? 0 : e - *b;
-}
 
 __device__ __forceinline__ int32_t sat32(int64_t v) {
   return v > INT32_MAX ? INT32_MAX : (int32_t)v;
@@ -112,7 +100,7 @@ __device__ __forceinline__ int32_t card_rank(const CardView& t, int64_t row, int
   for (int32_t r = 0; r < L; ++r) {
     if (t.len[row + r] != n) continue;
     const char* q = t.pool + t.beg[row + r];
-    int64_t i = 0;
+    int64_t i = 0;  // (not bytes_equal: its early return compiles to another annotation_ranks)
     while (i < n && q[i] == p[i]) ++i;
     if (i == n) return r;
   }
@@ -168,7 +156,7 @@ __global__ __launch_bounds__(kTpb) void annotation_verdicts(int32_t E,
   if (e < E && verdict[e] != PAS_GAS_ANN_PENDING) status[e] = verdict[e];
 }
 
-CardView view_of(const GasCardNames& t) { return CardView{t.k, t.beg, t.len, t.pool}; }
+CardView view_of(const GasCardNames& t) { return CardView{t.k, t.sp.beg, t.sp.len, t.sp.pool}; }
 
 }  // namespace
 

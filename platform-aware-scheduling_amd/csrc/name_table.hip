@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "csr_entry.h"
 #include "host_staging.h"
 #include "name_hash.h"
 #include "pas_internal.h"
@@ -33,6 +34,7 @@ namespace {
 
 constexpr int kTpb = 256;
 constexpr unsigned long long kEmpty = ~0ull;
+constexpr const char* kTable = "name table";
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTpb - 1) / kTpb); }
 
@@ -45,33 +47,13 @@ struct NameView {
 };
 
 inline NameView view_of(const NameTable& t) {
-  return NameView{t.buckets - 1, t.table, t.beg, t.len, t.pool};
+  return NameView{t.buckets - 1, t.table, t.sp.beg, t.sp.len, t.sp.pool};
 }
 
 inline int64_t buckets_for(int64_t n_slots) {
   int64_t b = 2;
   while (b < 2 * n_slots) b <<= 1;
   return b;
-}
-
-__device__ __forceinline__ int64_t clamp_off(int64_t v, int64_t n) {
-  return v < 0 ? 0 : v > n ? n : v;
-}
-
-// Entry i of a batch: bytes[*b .. *b + return), both ends clamped into [0, n_bytes] and the
-// end not before the begin, as parse_literals reads its literals.
-__device__ __forceinline__ int64_t entry_span(const int64_t* __restrict__ off, int64_t n_bytes,
-                                              int64_t i, int64_t* b) {
-  *b = clamp_off(off[i], n_bytes);
-  const int64_t e = clamp_off(off[i + 1], n_bytes);
-  return e < *b ? 0 : e - *b;
-}
-
-__device__ __forceinline__ bool bytes_equal(const char* __restrict__ a,
-                                            const char* __restrict__ b, int64_t n) {
-  for (int64_t i = 0; i < n; ++i)
-    if (a[i] != b[i]) return false;
-  return true;
 }
 
 __device__ __forceinline__ unsigned long long make_word(uint64_t h, uint32_t low) {
@@ -147,52 +129,6 @@ __global__ void names_flag_losers(int64_t n_slots, NameView t, int32_t* ctr) {
   if (len == 0) return;
   const char* p = t.pool + t.beg[s];
   if (table_find(t, p, len, name_hash(p, len)) != (int32_t)s) atomicMin(&ctr[0], (int32_t)s);
-}
-
-// beg / len of a set from its CSR offsets; ctr[1] += the named slots
-__global__ void names_spans(int64_t n_slots, const int64_t* __restrict__ off,
-                            int64_t* __restrict__ beg, int64_t* __restrict__ len, int32_t* ctr) {
-  const int64_t s = (int64_t)blockIdx.x * kTpb + threadIdx.x;
-  bool named = false;
-  if (s < n_slots) {
-    beg[s] = off[s];
-    len[s] = off[s + 1] - off[s];
-    named = off[s + 1] > off[s];
-  }
-  const unsigned long long m = __ballot(named);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&ctr[1], (int32_t)__popcll(m));
-}
-
-// The lengths of a remapped table: new slot j holds old slot src[j]; ctr[1] += the named ones
-__global__ void names_remap_lens(int64_t n_new, const int32_t* __restrict__ src,
-                                 const int64_t* __restrict__ len_old,
-                                 int64_t* __restrict__ len_new, int32_t* ctr) {
-  const int64_t j = (int64_t)blockIdx.x * kTpb + threadIdx.x;
-  bool named = false;
-  if (j < n_new) {
-    const int32_t s = src[j];
-    const int64_t len = s >= 0 ? len_old[s] : 0;
-    len_new[j] = len;
-    named = len > 0;
-  }
-  const unsigned long long m = __ballot(named);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&ctr[1], (int32_t)__popcll(m));
-}
-
-// Name j (old slot src[j], null: slot j) copied to its scanned place dst + beg_new[j]
-__global__ void names_gather(int64_t n, const int32_t* __restrict__ src,
-                             const int64_t* __restrict__ beg_old,
-                             const int64_t* __restrict__ len_old,
-                             const char* __restrict__ pool_old,
-                             const int64_t* __restrict__ beg_new, char* __restrict__ dst) {
-  const int64_t j = (int64_t)blockIdx.x * kTpb + threadIdx.x;
-  if (j >= n) return;
-  const int64_t s = src ? src[j] : j;
-  if (s < 0) return;
-  const int64_t len = len_old[s];
-  const char* p = pool_old + beg_old[s];
-  char* q = dst + beg_new[j];
-  for (int64_t k = 0; k < len; ++k) q[k] = p[k];
 }
 
 // ---- assignment
@@ -328,10 +264,6 @@ int rebuild_table(pas_ctx* ctx, NameTable& t, int64_t buckets, hipStream_t s) {
   return PAS_OK;
 }
 
-int no_table(pas_ctx* ctx, const char* fn) {
-  return set_error(ctx, PAS_ENOSNAP, std::string(fn) + ": no name table");
-}
-
 // pas_names_assign[_device] on device arrays (d_slot may be null), synchronous on s.
 int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
                         const char* d_bytes, int32_t* d_slot, int64_t new_cap,
@@ -394,7 +326,7 @@ int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t*
   assign_firsts<<<blocks_for(n + 1), kTpb, 0, s>>>(n, n_bytes, d_off, d_bytes, d_slot, d_hash,
                                                    sb - 1, d_scratch, d_first_of, d_flag, d_flen);
   PAS_HIP(ctx, hipGetLastError());
-  names_spare_flags<<<blocks_for(t.n_slots + 1), kTpb, 0, s>>>(t.n_slots, t.len, d_sflag);
+  names_spare_flags<<<blocks_for(t.n_slots + 1), kTpb, 0, s>>>(t.n_slots, t.sp.len, d_sflag);
   PAS_HIP(ctx, hipGetLastError());
   if ((rc = scan_run<uint32_t>(ctx, d_scan, scan_bytes, d_flag, d_rank, nn + 1, s))) return rc;
   if ((rc = scan_run<int64_t>(ctx, d_scan, scan_bytes, d_flen, d_fpos, nn + 1, s))) return rc;
@@ -415,19 +347,19 @@ int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t*
     return set_error(ctx, PAS_EINVAL, "pas_names_assign: new names and null output arrays");
 
   // (d), (e): nothing has changed so far; from here the table does
-  if ((rc = grow_pool(ctx, t, new_bytes, s, "name table: pool copy"))) return rc;
+  if ((rc = grow_pool(ctx, t.sp, new_bytes, s, "name table: pool copy"))) return rc;
   assign_spares<<<blocks_for(t.n_slots), kTpb, 0, s>>>(t.n_slots, n_new, d_sflag, d_srank,
                                                        d_spare);
   PAS_HIP(ctx, hipGetLastError());
   assign_commit<<<blocks_for(n), kTpb, 0, s>>>(n, n_bytes, d_off, d_bytes, d_flag, d_rank, d_fpos,
-                                               d_spare, t.pool_used, view_of(t), d_slot,
+                                               d_spare, t.sp.pool_used, view_of(t), d_slot,
                                                d_new_entry, d_new_slot);
   PAS_HIP(ctx, hipGetLastError());
   names_insert<<<blocks_for(n_new), kTpb, 0, s>>>(n_new, d_new_slot, view_of(t));
   PAS_HIP(ctx, hipGetLastError());
   assign_repeats<<<blocks_for(n), kTpb, 0, s>>>(n, d_first_of, d_flag, d_slot);
   PAS_HIP(ctx, hipGetLastError());
-  t.pool_used += new_bytes;
+  t.sp.pool_used = t.sp.live_bytes = t.sp.pool_used + new_bytes;
   t.n_named += (int32_t)n_new;
   PAS_HIP(ctx, hipMemcpyAsync(new_entry_out, d_new_entry, sizeof(int32_t) * n_new,
                               hipMemcpyDeviceToHost, s));
@@ -441,9 +373,7 @@ int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t*
 }  // namespace
 
 void free_names(NameTable& t) {
-  free_dev(t.beg);
-  free_dev(t.len);
-  free_dev(t.pool);
+  free_pool(t.sp);
   free_dev(t.table);
   t = NameTable{};
 }
@@ -478,12 +408,8 @@ int pas_names_set(pas_ctx* ctx, int32_t n_slots, const int64_t* name_off, const 
   if (rc) return rc;
   if ((rc = activate(ctx))) return rc;
   hipStream_t s = ctx->stream;
-  const int64_t total = name_off[n_slots];
   NameTable nt;
   nt.n_slots = n_slots;
-  nt.slot_cap = std::max<int64_t>(n_slots, 1);
-  nt.pool_cap = std::max<int64_t>(total, 1);
-  nt.pool_used = total;
   int32_t* d_ctr = nullptr;  // {lowest loser, named slots}
   const int32_t ctr0[2] = {INT32_MAX, 0};
   int32_t ctr[2] = {INT32_MAX, 0};
@@ -494,16 +420,9 @@ int pas_names_set(pas_ctx* ctx, int32_t n_slots, const int64_t* name_off, const 
   auto build = [&]() -> int {
     int r = st.upload();
     if (r) return r;
-    if ((r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s, "name table: span arrays")))
-      return r;
-    PAS_HIP(ctx, hipMalloc(&nt.pool, (size_t)nt.pool_cap));
-    if (total > 0)
-      PAS_HIP(ctx, hipMemcpyAsync(nt.pool, bytes, (size_t)total, hipMemcpyHostToDevice, s));
     PAS_HIP(ctx, hipMemcpyAsync(d_ctr, ctr0, sizeof(ctr0), hipMemcpyHostToDevice, s));
-    if (n_slots > 0) {
-      names_spans<<<blocks_for(n_slots), kTpb, 0, s>>>(n_slots, d_off, nt.beg, nt.len, d_ctr);
-      PAS_HIP(ctx, hipGetLastError());
-    }
+    if ((r = pool_set(ctx, nt.sp, n_slots, name_off, d_off, bytes, d_ctr + 1, s, kTable)))
+      return r;
     if ((r = rebuild_table(ctx, nt, buckets_for(n_slots), s))) return r;
     if (n_slots > 0) {
       names_flag_losers<<<blocks_for(n_slots), kTpb, 0, s>>>(n_slots, view_of(nt), d_ctr);
@@ -534,13 +453,13 @@ int pas_names_info(const pas_ctx* ctx, int32_t* n_slots, int32_t* n_named, int64
   if (!ctx->names.valid) return PAS_ENOSNAP;
   if (n_slots) *n_slots = ctx->names.n_slots;
   if (n_named) *n_named = ctx->names.n_named;
-  if (n_bytes) *n_bytes = ctx->names.pool_used;
+  if (n_bytes) *n_bytes = ctx->names.sp.pool_used;
   return PAS_OK;
 }
 
 int pas_names_drop(pas_ctx* ctx) {
   if (!ctx) return PAS_EINVAL;
-  if (!ctx->names.valid) return no_table(ctx, "pas_names_drop");
+  if (!ctx->names.valid) return no_table(ctx, "pas_names_drop", kTable);
   ctx->names.valid = false;
   return PAS_OK;
 }
@@ -549,42 +468,15 @@ int pas_names_get(pas_ctx* ctx, int64_t* name_off_out, char* bytes_out, int64_t 
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_get";
   NameTable& t = ctx->names;
-  if (!t.valid) return no_table(ctx, fn.c_str());
-  if (!name_off_out || cap < 0 || (cap > 0 && !bytes_out))
-    return set_error(ctx, PAS_EINVAL, fn + ": null output or cap < 0");
-  int rc = activate(ctx);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  const size_t ns = (size_t)t.n_slots;
-  const bool fits = cap >= t.pool_used;
-  size_t scan_bytes = 0;
-  if ((rc = scan_size<int64_t>(ctx, ns + 1, &scan_bytes))) return rc;
-  Staging st(ctx);
-  int64_t* d_off;
-  char *d_bytes, *d_scan;
-  st.out(d_off, name_off_out, ns + 1);
-  st.out(d_bytes, bytes_out, fits ? (size_t)t.pool_used : 0);
-  st.work(d_scan, scan_bytes);
-  if ((rc = st.upload())) return rc;
-  if ((rc = derived_wait(ctx, ctx->names_sync, s))) return rc;
-  if ((rc = scan_run<int64_t>(ctx, d_scan, scan_bytes, t.len, d_off, ns + 1, s))) return rc;
-  if (fits && ns > 0) {
-    names_gather<<<blocks_for(t.n_slots), kTpb, 0, s>>>(t.n_slots, nullptr, t.beg, t.len, t.pool,
-                                                        d_off, d_bytes);
-    PAS_HIP(ctx, hipGetLastError());
-  }
-  PAS_HIP(ctx, st.fetch());
-  if (!fits)
-    return set_error(ctx, PAS_ECAPACITY, fn + ": " + std::to_string(t.pool_used) +
-                                             " bytes of names, cap " + std::to_string(cap));
-  return PAS_OK;
+  if (!t.valid) return no_table(ctx, fn, kTable);
+  return pool_get(ctx, t.sp, t.n_slots, name_off_out, bytes_out, cap, &ctx->names_sync, fn);
 }
 
 int pas_names_resolve_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_name_off,
                              const char* d_bytes, int32_t* d_slot_out, void* hip_stream) {
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_resolve_device";
-  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (!ctx->names.valid) return no_table(ctx, fn, kTable);
   if (n < 0 || n_bytes < 0) return set_error(ctx, PAS_EINVAL, fn + ": n or n_bytes < 0");
   if (n == 0) return PAS_OK;
   if (!d_name_off || !d_slot_out || (n_bytes > 0 && !d_bytes))
@@ -599,7 +491,7 @@ int pas_names_resolve(pas_ctx* ctx, int64_t n, const int64_t* name_off, const ch
                       int32_t* slot_out) {
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_resolve";
-  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (!ctx->names.valid) return no_table(ctx, fn, kTable);
   if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
   if (n == 0) return PAS_OK;
   int rc = check_csr(ctx, n, name_off, bytes, fn);
@@ -628,7 +520,7 @@ int pas_names_assign_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int6
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_assign_device";
   if (n_new_out) *n_new_out = 0;
-  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (!ctx->names.valid) return no_table(ctx, fn, kTable);
   if (n < 0 || n > INT32_MAX || n_bytes < 0 || new_cap < 0)
     return set_error(ctx, PAS_EINVAL, fn + ": n, n_bytes or new_cap out of range");
   if (n == 0) return PAS_OK;
@@ -647,7 +539,7 @@ int pas_names_assign(pas_ctx* ctx, int64_t n, const int64_t* name_off, const cha
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_assign";
   if (n_new_out) *n_new_out = 0;
-  if (!ctx->names.valid) return no_table(ctx, fn.c_str());
+  if (!ctx->names.valid) return no_table(ctx, fn, kTable);
   if (n < 0 || n > INT32_MAX || new_cap < 0)
     return set_error(ctx, PAS_EINVAL, fn + ": n or new_cap out of range");
   if (n == 0) return PAS_OK;
@@ -675,33 +567,16 @@ int pas_names_resize(pas_ctx* ctx, int32_t n_slots_new, void* hip_stream) {
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_resize";
   NameTable& t = ctx->names;
-  if (!t.valid) return no_table(ctx, fn.c_str());
+  if (!t.valid) return no_table(ctx, fn, kTable);
   if (n_slots_new < t.n_slots)
     return set_error(ctx, PAS_EINVAL, fn + ": " + std::to_string(n_slots_new) + " slots, the " +
                                           "table has " + std::to_string(t.n_slots));
   int rc = activate(ctx);
   if (rc) return rc;
   hipStream_t s = pick_stream(ctx, hip_stream);
-  if (n_slots_new > t.slot_cap) {
-    int64_t *beg, *len;
-    if ((rc = alloc_spans(ctx, n_slots_new, &beg, &len, s, "name table: span arrays")))
-      return rc;
-    const size_t old = sizeof(int64_t) * (size_t)t.n_slots;
-    hipError_t e = hipSuccess;
-    if (old) e = hipMemcpyAsync(beg, t.beg, old, hipMemcpyDeviceToDevice, s);
-    if (old && e == hipSuccess) e = hipMemcpyAsync(len, t.len, old, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      free_dev(beg);
-      free_dev(len);
-      return check_hip(ctx, e, "pas_names_resize: span copy");
-    }
-    free_dev(t.beg);
-    free_dev(t.len);
-    t.beg = beg;
-    t.len = len;
-    t.slot_cap = n_slots_new;
-  }
+  if (n_slots_new > t.sp.span_cap &&
+      (rc = pool_repitch(ctx, t.sp, t.n_slots, 1, n_slots_new, 1, s, kTable, fn)))
+    return rc;
   t.n_slots = n_slots_new;
   if (2 * (int64_t)n_slots_new > t.buckets)  // the load factor would pass 1/2
     if ((rc = rebuild_table(ctx, t, buckets_for(n_slots_new), s))) return rc;
@@ -715,61 +590,32 @@ int pas_names_remap(pas_ctx* ctx, int32_t n_slots_new, const int32_t* src_slot,
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_remap";
   NameTable& t = ctx->names;
-  if (!t.valid) return no_table(ctx, fn.c_str());
-  if (n_slots_new < 0 || (n_slots_new > 0 && !src_slot))
-    return set_error(ctx, PAS_EINVAL, fn + ": bad slot count or null map");
-  int32_t last = -1;
-  for (int32_t j = 0; j < n_slots_new; ++j) {
-    const int32_t v = src_slot[j];
-    if (v == -1) continue;
-    if (v < 0 || v >= t.n_slots || v <= last)
-      return set_error(ctx, PAS_EINVAL, fn + ": entry " + std::to_string(j) + " is neither -1 " +
-                                            "nor a slot above the entries before it");
-    last = v;
-  }
-  int rc = activate(ctx);
+  if (!t.valid) return no_table(ctx, fn, kTable);
+  int rc = check_compact_map(ctx, n_slots_new, src_slot, t.n_slots, fn);
   if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
   hipStream_t s = pick_stream(ctx, hip_stream);
   const size_t n2 = (size_t)n_slots_new;
   size_t scan_bytes = 0;
   if ((rc = scan_size<int64_t>(ctx, n2 + 1, &scan_bytes))) return rc;
   SlotScope scope(ctx, s, 0, &rc);
   if (!scope.slot) return rc;
-  const size_t total = carve_size({sizeof(int32_t) * 2, sizeof(int32_t) * n2, scan_bytes});
+  const size_t total = carve_size({sizeof(int32_t), sizeof(int32_t) * n2, scan_bytes});
   char* base = static_cast<char*>(slot_buf(ctx, scope.slot, kBufNames, total, s, &rc));
   if (!base) return rc;
   Carve cv{base};
-  int32_t* d_ctr = cv.take<int32_t>(2);
+  int32_t* d_named = cv.take<int32_t>(1);
   int32_t* d_src = cv.take<int32_t>(n2);
   void* d_scan = cv.take<char>(scan_bytes);
   NameTable nt;
   nt.n_slots = n_slots_new;
-  nt.slot_cap = std::max<int64_t>(n_slots_new, 1);
-  int32_t ctr[2] = {0, 0};
-  int64_t bytes_new = 0;
   auto build = [&]() -> int {
-    int r = alloc_spans(ctx, nt.slot_cap, &nt.beg, &nt.len, s, "name table: span arrays");
-    if (r) return r;
-    PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(int32_t) * 2, s));
-    if (n2) {
+    PAS_HIP(ctx, hipMemsetAsync(d_named, 0, sizeof(int32_t), s));
+    if (n2)
       PAS_HIP(ctx, hipMemcpyAsync(d_src, src_slot, sizeof(int32_t) * n2, hipMemcpyHostToDevice, s));
-      names_remap_lens<<<blocks_for(n_slots_new), kTpb, 0, s>>>(n_slots_new, d_src, t.len, nt.len,
-                                                                d_ctr);
-      PAS_HIP(ctx, hipGetLastError());
-    }
-    if ((r = scan_run<int64_t>(ctx, d_scan, scan_bytes, nt.len, nt.beg, n2 + 1, s))) return r;
-    PAS_HIP(ctx, hipMemcpyAsync(&bytes_new, nt.beg + n2, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    PAS_HIP(ctx, hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
-    PAS_HIP(ctx, hipStreamSynchronize(s));
-    nt.pool_cap = std::max<int64_t>(bytes_new, 1);
-    nt.pool_used = bytes_new;
-    nt.n_named = ctr[1];
-    PAS_HIP(ctx, hipMalloc(&nt.pool, (size_t)nt.pool_cap));
-    if (n2) {
-      names_gather<<<blocks_for(n_slots_new), kTpb, 0, s>>>(n_slots_new, d_src, t.beg, t.len,
-                                                            t.pool, nt.beg, nt.pool);
-      PAS_HIP(ctx, hipGetLastError());
-    }
+    int r = pool_gathered(ctx, t.sp, n_slots_new, 1, d_src, d_scan, scan_bytes, d_named,
+                          &nt.n_named, &nt.sp, s, kTable);
+    if (r) return r;
     if ((r = rebuild_table(ctx, nt, buckets_for(n_slots_new), s))) return r;
     PAS_HIP(ctx, hipStreamSynchronize(s));
     return PAS_OK;

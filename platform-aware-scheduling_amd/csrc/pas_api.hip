@@ -280,7 +280,7 @@ void pas_destroy(pas_ctx* ctx) {
   if (ctx->policies.viol) (void)hipFree(ctx->policies.viol);
   if (ctx->policies.viol_sync.ev) (void)hipEventDestroy(ctx->policies.viol_sync.ev);
   free_names(ctx->names);
-  free_gas_cards(ctx->gas_cards);
+  free_pool(ctx->gas_cards.sp);
   if (ctx->names_sync.ev) (void)hipEventDestroy(ctx->names_sync.ev);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->gas_sync_fault) (void)hipHostFree(ctx->gas_sync_fault);

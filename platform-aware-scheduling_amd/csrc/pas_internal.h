@@ -230,24 +230,34 @@ struct TasPolicies {
   DerivedSync viol_sync;
 };
 
+// Spans into one byte pool (span_pool.hip): the storage under the two resident name tables.
+// Entry i is pool[beg[i] .. beg[i] + len[i]).  The span arrays hold span_cap + 1 entries (the
+// scans' last element) and len is 0 from the table's entries on.  The pool only grows:
+// pool_used counts every byte ever appended, live_bytes the bytes the spans still name (the
+// sum of the lengths); a pool is packed by a scan of the lengths and one gather.
+struct SpanPool {
+  int64_t* beg = nullptr;
+  int64_t* len = nullptr;
+  int64_t span_cap = 0;
+  char* pool = nullptr;
+  int64_t pool_used = 0;
+  int64_t pool_cap = 0;
+  int64_t live_bytes = 0;
+};
+
 // The resident node-name table (name_table.hip): which name stands in which node slot, for
 // every snapshot of the context (combined contexts share one slot numbering, so it belongs to
-// neither).  A slot's name is pool[beg[s] .. beg[s] + len[s]); len 0 marks a spare slot, so
-// the empty name never has a slot.  The pool's order is the order of arrival, not of the
-// slots.  `table` is an open-addressing hash of the named slots, `buckets` a power of two >=
-// 2 * n_slots: word = tag << 32 | slot (name_hash.h), all ones = empty, linear probing with
-// wraparound; nothing is ever deleted in place (a remap rebuilds).  The span arrays hold
-// slot_cap + 1 entries and len is 0 from n_slots on.  Storage only grows.
+// neither).  Slot s is entry s of `sp`; len 0 marks a spare slot, so the empty name never has
+// a slot.  The pool's order is the order of arrival, not of the slots, and no byte of it is
+// ever dead (live_bytes = pool_used).  `table` is an open-addressing hash of the named slots,
+// `buckets` a power of two >= 2 * n_slots: word = tag << 32 | slot (name_hash.h), all ones =
+// empty, linear probing with wraparound; nothing is ever deleted in place (a remap rebuilds).
+// Storage only grows.
 struct NameTable {
   bool valid = false;
   int32_t n_slots = 0;
   int32_t n_named = 0;
-  int64_t slot_cap = 0;
-  int64_t* beg = nullptr;
-  int64_t* len = nullptr;
-  char* pool = nullptr;
-  int64_t pool_used = 0;  // = the sum of the lengths
-  int64_t pool_cap = 0;
+  SpanPool sp;
   unsigned long long* table = nullptr;
   int64_t buckets = 0;
 };
@@ -255,22 +265,16 @@ struct NameTable {
 // The resident card-name table (gas_cards.hip): the names of the card slots of every node slot,
 // beside the GAS snapshot struct and not in it (resize and compact replace that struct).  Row s
 // holds k entries in the order of used[s][.]: the label cards in sort.Strings order, then what
-// the caller keeps behind them (parked cards).  Entry (s, c) is pool[beg[s * k + c] ..
-// + len[s * k + c]); names are opaque bytes and the empty name is a name like any other.  The
-// span arrays hold n_slots * k + 1 entries (the scans' last element; len is 0 there).  A row
-// rewrite appends the new bytes to the pool and leaves the old ones dead: pool_used counts
-// both, live_bytes (the sum of row_bytes, the rows' byte totals kept on the host) the bytes
-// the spans still name.  When the dead bytes pass the live ones the pool is gathered.
+// the caller keeps behind them (parked cards).  Entry (s, c) is entry s * k + c of `sp`; names
+// are opaque bytes and the empty name is a name like any other.  A row rewrite appends the new
+// bytes to the pool and leaves the old ones dead: sp.live_bytes is the sum of row_bytes, the
+// rows' byte totals kept on the host.  When the dead bytes pass the live ones the pool is
+// gathered.
 struct GasCardNames {
   bool valid = false;
   int32_t n_slots = 0;
   int32_t k = 0;
-  int64_t* beg = nullptr;
-  int64_t* len = nullptr;
-  char* pool = nullptr;
-  int64_t pool_used = 0;
-  int64_t pool_cap = 0;
-  int64_t live_bytes = 0;
+  SpanPool sp;
   std::vector<int64_t> row_bytes;  // [n_slots]
   std::vector<uint32_t> stamp;     // [n_slots] the last update call that named the slot
   uint32_t stamp_clock = 0;
@@ -493,6 +497,8 @@ int tas_update_quantities_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
                                  const int32_t* d_entry_node, const int64_t* d_lit_off,
                                  const char* d_bytes, int32_t* kind_out, int32_t* scale_out,
                                  int64_t* bad_entry, hipStream_t s);
+// free_pool (span_pool.hip): the span arrays and the pool of sp, which is empty afterwards.
+void free_pool(SpanPool& sp);
 // Name table (name_table.hip).  free_names: every array of the table (pas_destroy).
 // names_resolve_launch: d_slot[i] = the slot of name i = d_bytes[d_off[i] .. d_off[i + 1])
 // (offsets read clamped into [0, n_bytes]) or -1, enqueued on s after the last table change;
@@ -502,8 +508,6 @@ void free_names(NameTable& t);
 int names_resolve_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
                          const char* d_bytes, int32_t* d_slot, uint64_t* d_hash,
                          uint32_t* d_unknown, bool count_empty, hipStream_t s);
-// Card-name table (gas_cards.hip): every array of the table (pas_destroy).
-void free_gas_cards(GasCardNames& t);
 // Pod events from annotation strings (gas_annotations.hip).  annotations_resolve_launch: the
 // parse-alone form on device arrays, enqueued on s: per event the verdict of the rules of
 // pas_gas_apply_annotations (d_kind null: no kind is checked; d_name_off non-null: d_node holds

@@ -1,6 +1,8 @@
-// span_pool.h — what the two resident name tables share (name_table.hip: node names,
-// gas_cards.hip: card names): spans (beg, len) into one byte pool that only grows, the CSR
-// check of their host forms and the scans that pack a pool.
+// span_pool.h — the layer under the two resident name tables (name_table.hip: node names,
+// gas_cards.hip: card names): a SpanPool (pas_internal.h) is spans (beg, len) into one byte
+// pool that only grows.  Here: the scans, the CSR check of the host forms, and what
+// span_pool.hip builds on them.  `table` names the table in an error ("name table"), `fn` the
+// entry point.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,56 +38,51 @@ inline void free_dev(void* p) {
   if (p) (void)hipFree(p);
 }
 
-// Span arrays of `cap` entries (+ 1: the scans' last element), all zero.  `what` names the
-// table in the error.
-inline int alloc_spans(pas_ctx* ctx, int64_t cap, int64_t** beg, int64_t** len, hipStream_t s,
-                       const char* what) {
-  *beg = *len = nullptr;
-  const size_t bytes = sizeof(int64_t) * ((size_t)cap + 1);
-  hipError_t e = hipMalloc(beg, bytes);
-  if (e == hipSuccess) e = hipMalloc(len, bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(*len, 0, bytes, s);
-  if (e == hipSuccess) e = hipMemsetAsync(*beg, 0, bytes, s);
-  if (e != hipSuccess) {
-    free_dev(*beg);
-    free_dev(*len);
-    *beg = *len = nullptr;
-    return check_hip(ctx, e, what);
-  }
-  return PAS_OK;
-}
+int no_table(pas_ctx* ctx, const std::string& fn, const char* table);
 
 // offsets [n + 1] of a host form: from 0 and non-decreasing
-inline int check_csr(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
-                     const std::string& fn) {
-  if (!off || off[0] != 0) return set_error(ctx, PAS_EINVAL, fn + ": offsets must start at 0");
-  for (int64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return set_error(ctx, PAS_EINVAL, fn + ": offsets decrease");
-  if (off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  return PAS_OK;
-}
+int check_csr(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
+              const std::string& fn);
 
-// Room for t.pool_used + more bytes in t.pool (NameTable, GasCardNames); synchronous on s when
-// the pool moves.
-template <class Table>
-inline int grow_pool(pas_ctx* ctx, Table& t, int64_t more, hipStream_t s, const char* what) {
-  const int64_t need = t.pool_used + more;
-  if (need <= t.pool_cap) return PAS_OK;
-  const int64_t cap = std::max(need, 2 * t.pool_cap);
-  char* np = nullptr;
-  PAS_HIP(ctx, hipMalloc(&np, (size_t)cap));
-  hipError_t e = hipSuccess;
-  if (t.pool_used > 0)
-    e = hipMemcpyAsync(np, t.pool, (size_t)t.pool_used, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    free_dev(np);
-    return check_hip(ctx, e, what);
-  }
-  free_dev(t.pool);
-  t.pool = np;
-  t.pool_cap = cap;
-  return PAS_OK;
-}
+// A compact map of n_new rows over n_old: every entry is -1 or a row above the entries before
+// it.
+int check_compact_map(pas_ctx* ctx, int32_t n_new, const int32_t* src, int32_t n_old,
+                      const std::string& fn);
+
+// Span arrays of `cap` entries (+ 1: the scans' last element), all zero.
+int alloc_spans(pas_ctx* ctx, int64_t cap, int64_t** beg, int64_t** len, hipStream_t s,
+                const char* what);
+
+// Room for sp.pool_used + more bytes in sp.pool; synchronous on s when the pool moves.
+int grow_pool(pas_ctx* ctx, SpanPool& sp, int64_t more, hipStream_t s, const char* what);
+
+// A set from its host form: sp = spans of n entries from d_off (the uploaded name_off) over a
+// pool that is a copy of bytes, enqueued on s.  d_named (may be null): a zeroed counter, + the
+// entries that are not empty.  sp is empty on entry; a failure leaves it to the caller's
+// free_pool.
+int pool_set(pas_ctx* ctx, SpanPool& sp, int64_t n, const int64_t* name_off, const int64_t* d_off,
+             const char* bytes, int32_t* d_named, hipStream_t s, const char* table);
+
+// out = n_rows_new rows of k entries, row j the row d_map[j] of src (-1: an empty row; d_map
+// null: the rows as they are), in storage of its own with the pool packed in entry order.
+// d_scan: scan_size<int64_t>(n_rows_new * k + 1) bytes.  d_named (may be null): a zeroed
+// counter, + the entries that are not empty, read back into *named.  Synchronizes s once (the
+// byte total decides the pool's size) and leaves the gather enqueued.  src is untouched; a
+// failure frees what was allocated.
+int pool_gathered(pas_ctx* ctx, const SpanPool& src, int64_t n_rows_new, int32_t k,
+                  const int32_t* d_map, void* d_scan, size_t scan_bytes, int32_t* d_named,
+                  int32_t* named, SpanPool* out, hipStream_t s, const char* table);
+
+// The entries of sp in entry order: offsets [n + 1] and the live bytes; PAS_ECAPACITY with the
+// offsets delivered and the bytes withheld when cap is short.  On ctx->stream, after the change
+// `after` stands for (null: the table only changes synchronously), synchronous.
+int pool_get(pas_ctx* ctx, const SpanPool& sp, int64_t n, int64_t* off_out, char* bytes_out,
+             int64_t cap, const DerivedSync* after, const std::string& fn);
+
+// New span arrays of n_rows_new x k_new entries holding the n_rows_old x k_old ones (the rest
+// empty), swapped in; the pool as it is.  Synchronous on s.
+int pool_repitch(pas_ctx* ctx, SpanPool& sp, int64_t n_rows_old, int32_t k_old,
+                 int64_t n_rows_new, int32_t k_new, hipStream_t s, const char* table,
+                 const std::string& fn);
 
 }  // namespace pas

@@ -99,6 +99,27 @@ def test_update_resize_remap_against_the_model(ctx, n_slots, k):
 
 
 @pytest.mark.gpu
+def test_table_with_no_rows(ctx):
+    """No row at all: set, get and remap launch nothing and still answer; the table then grows
+    from nothing and takes an update."""
+    k = 8
+    ctx.gas_card_names_set(0, k, [0], b"")
+    assert ctx.gas_card_names_info() == (0, k, 0)
+    off, blob = ctx.gas_card_names_get()
+    assert off.tolist() == [0] and blob == b""
+    ctx.gas_card_names_remap([])
+    assert ctx.gas_card_names_info() == (0, k, 0)
+    assert read(ctx) == []
+    ctx.gas_card_names_resize(3, k)
+    rows = [[b""] * k for _ in range(3)]
+    assert read(ctx) == rows
+    rows[2] = [b"late%d" % c if c % 2 else b"" for c in range(k)]
+    ctx.gas_card_names_update([2], *pack_names(rows[2]))
+    assert ctx.gas_card_names_info() == (3, k, sum(map(len, rows[2])))
+    assert read(ctx) == rows
+
+
+@pytest.mark.gpu
 def test_repeated_updates_do_not_grow_the_pool_without_bound(ctx):
     n_slots, k = 65, 16
     rows = model_rows(n_slots, k, 5)

@@ -448,6 +448,44 @@ def test_remap(ctx):
     assert ctx.names_info() == (0, 0, 0)
 
 
+@pytest.mark.parametrize("n_slots", [63, 64, 65, 257, 600])
+def test_remap_across_wave_and_block_edges(ctx, n_slots):
+    """Tables of one wave less a lane, one wave, one wave and a lane, a block and a lane, and
+    more than two blocks, every third slot spare.  The map keeps every second slot in ascending
+    order, with -1 entries at the front, in the middle and at the end: the named count (one
+    ballot per wave, a last wave that is not full) and the packed pool against the model."""
+    names = [b"" if i % 3 == 2 else b"edge-%d" % i for i in range(n_slots)]
+    model = install(ctx, names)
+    assert ctx.names_info() == (n_slots, len(model.index), sum(map(len, names)))
+    kept = list(range(0, n_slots, 2))
+    mid = len(kept) // 2
+    src = [-1, -1] + kept[:mid] + [-1] + kept[mid:] + [-1, -1, -1]
+    ctx.names_remap(src)
+    model.remap(src)
+    assert table_names(ctx) == model.names
+    assert ctx.names_info() == (len(src), len(model.index), sum(map(len, model.names)))
+    check_resolve(ctx, model, names)
+    # the lowest spare slots go first: the two -1 entries at the front, then the next spare one
+    spare = [j for j, n in enumerate(model.names) if not n]
+    assert spare[:2] == [0, 1] and len(spare) > 6
+    got = check_assign(ctx, model, "host", [b"fresh-0", names[0], b"fresh-1", b"fresh-2"])
+    assert got == ([0, 2, 1, spare[2]], [0, 2, 3], spare[:3], 3, True)
+
+
+def test_get_with_a_short_buffer(ctx):
+    """A buffer one byte short: PAS_ECAPACITY, the offsets are still delivered and the message
+    names the byte count (the raw call: Context.names_get sizes its buffer from names_info)."""
+    names = [b"short-%d" % i for i in range(65)]
+    install(ctx, names)
+    n_bytes = sum(map(len, names))
+    off = np.zeros(len(names) + 1, np.int64)
+    buf = np.zeros(n_bytes, np.uint8)
+    rc = ctx._l.pas_names_get(ctx._h, off.ctypes.data, buf.ctypes.data, n_bytes - 1)
+    assert rc == ECAPACITY and off[-1] == n_bytes
+    assert off.tolist() == pack(names)[0].tolist()
+    assert str(n_bytes) in ctx.last_error()
+
+
 # ------------------------------------------------------------------ scale
 def test_hundred_thousand_names(ctx):
     n = 100000
