@@ -150,6 +150,13 @@ int pas_quantity_as_int64(const char* quantity, int64_t* out);
 int pas_quantity_parse_fixed(const char* bytes, int64_t len, int64_t* whole, uint32_t* nano,
                              int32_t* decimals, int32_t* fit);
 
+/* Quantity.AsInt64 of one literal given as a byte span, from the same routine: *out is what
+ * pas_quantity_as_int64 answers (0 for an inf.Dec-backed literal, for an int64Amount with a
+ * negative scale and on overflow; value * 10^scale otherwise, scale = exponent - fraction digits).
+ * Host only.  Returns the status of pas_quantity_parse_fixed ("1e19": PAS_ENOTEXACT and 0); out
+ * may be NULL. */
+int pas_quantity_as_int64_fixed(const char* bytes, int64_t len, int64_t* out);
+
 /* A batch of literals parsed on the device, one lane per literal: literal i is
  * bytes[lit_off[i] .. lit_off[i + 1]).  Per literal the outputs of pas_quantity_parse_fixed
  * (whole, nano 0 unless its status is PAS_OK; an output array may be NULL).  The call returns
@@ -1195,6 +1202,111 @@ int pas_gas_nodes_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to
                                 const int32_t* d_upd_src, int32_t* d_status_out,
                                 void* hip_stream);
 
+/* Node events from label and allocatable strings, parsed and resolved on the device
+ * (csrc/gas_node_strings.hip): what the informer hands over goes in as it is, and the row walker
+ * of pas_gas_nodes_update and the card-name table (below) do the writing.  Update u names its
+ * node by slot (upd_node) or, in the _names forms, by name through the name table; gives its
+ * state, the "gpu.intel.com/cards" label label_bytes[label_off[u] .. label_off[u + 1]) and one
+ * allocatable literal per resource kind q of the snapshot, cap_bytes[cap_off[u * Q + q] ..
+ * cap_off[u * Q + q + 1]).  PAS_ABI_VERSION is unchanged: additions only. */
+#define PAS_GAS_NODE_GONE (-1)    /* the node is not in the lister (FetchNode error) */
+#define PAS_GAS_NODE_NO_LABEL 0   /* no cards label (errWontFit, scheduler.go:290-298) */
+#define PAS_GAS_NODE_LABEL 1      /* the label, the empty string included (one card "") */
+/* Per update, in this order:
+ * 1. A state outside {-1, 0, 1} or a slot outside [0, n_nodes) is PAS_GAS_ERR_INPUT, nothing
+ *    changes.  _names forms: an empty name is PAS_GAS_ERR_INPUT; a name without a slot in the
+ *    snapshot is PAS_GAS_ERR_INPUT unless the state is GONE (the caller gives first-seen nodes
+ *    their slots with pas_names_assign beforehand), and with GONE it is PAS_GAS_OK and nothing
+ *    changes (n_cards_out -1).
+ * 2. GONE: n_cards -1, cap 0, the row and its names stay where they are; no literal is read.
+ * 3. NO_LABEL: n_cards 0, cap 0, the row and its names stay; no literal is read.
+ * 4. LABEL: pieces = 1 + count('.') is gpuCount (scheduler.go:132-148); n_cards is the number of
+ *    distinct pieces; cap[q] = AsInt64(literal q) / gpuCount, truncating toward zero
+ *    (resource_map.go:129-145).  An empty literal span is a resource the node does not have: 0.
+ *    A literal ParseQuantity rejects makes the update PAS_GAS_ERR_INPUT, nothing changes.
+ * 5. The new row of a LABEL update: the label cards in sort.Strings order (bytewise; a name
+ *    before any name it is a prefix of), then the parked cards: the old row's slots, in old slot
+ *    order, whose name the label does not list, the first max_cards - n_cards of them; the rest
+ *    are dropped and counted in n_dropped_out.  An empty name outside the old label range
+ *    [0, max(n_cards_old, 0)) is an unused slot: never parked, never counted.  A label card takes
+ *    the usage of the lowest old slot whose name has the same length and bytes (unused slots
+ *    included: their usage is zero), else zero usage (src -1).
+ * 6. Several updates of one node see each other in call order, as in pas_gas_nodes_update: the
+ *    resolve-and-apply steps run once per position in the longest run of one node (one round for
+ *    a batch without a repeated node; every further round synchronizes once more).
+ * Before anything resident is written the call synchronizes hip_stream once and reads back the
+ * largest distinct count, the new rows' byte totals and the longest run.  A distinct count above
+ * max_cards: PAS_ECAPACITY, nothing changed, the snapshot stays at gen_from; the caller grows the
+ * snapshot and the card-name table by a tier and calls again.  *need_cards (host memory in every
+ * form, may be NULL) is the largest distinct count of the call's pending updates, at most
+ * PAS_GAS_MAX_CARDS + 1.  The new rows' names are appended to the card-name table's pool on the
+ * device and the pool is gathered by the rule of pas_gas_card_names_update.
+ * Outputs: status_out [U]; n_cards_out [U], cap_out [U][Q] and n_dropped_out [U] may be NULL
+ * (n_cards 0 and cap 0 for a PAS_GAS_ERR_INPUT update).
+ * Errors: gen_from is checked and the snapshot moves to gen_to exactly as in
+ * pas_gas_nodes_update.  PAS_ENOSNAP without a snapshot, a card-name table or (_names) a name
+ * table; PAS_EINVAL unless the card-name table's shape equals the snapshot's.  The host forms
+ * return PAS_EINVAL unless every offset array starts at 0 and never decreases, and for a slot or
+ * a state out of range.  The _device forms check nothing of the offsets: both ends of every
+ * span are read clamped into its blob and the end not before the begin, so nothing outside the
+ * call's arrays, the workspace and the resident arrays is read or written.  A HIP failure after
+ * the first write leaves the snapshot and the card-name table invalid.  As for every snapshot
+ * change, the caller orders the call after readers on other streams. */
+int pas_gas_nodes_update_strings(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                 int32_t n_updates, const int32_t* upd_node,
+                                 const int32_t* upd_state, const int64_t* label_off,
+                                 const char* label_bytes, const int64_t* cap_off /*[U*Q+1]*/,
+                                 const char* cap_bytes, int32_t* status_out, int32_t* n_cards_out,
+                                 int64_t* cap_out /*[U][Q]*/, int32_t* n_dropped_out,
+                                 int32_t* need_cards);
+int pas_gas_nodes_update_strings_device(
+    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_updates,
+    const int32_t* d_upd_node, const int32_t* d_upd_state, int64_t n_label_bytes,
+    const int64_t* d_label_off, const char* d_label_bytes, int64_t n_cap_bytes,
+    const int64_t* d_cap_off, const char* d_cap_bytes, int32_t* d_status_out,
+    int32_t* d_n_cards_out, int64_t* d_cap_out, int32_t* d_n_dropped_out, int32_t* need_cards,
+    void* hip_stream);
+int pas_gas_nodes_update_strings_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                       int32_t n_updates, const int64_t* node_name_off,
+                                       const char* node_name_bytes, const int32_t* upd_state,
+                                       const int64_t* label_off, const char* label_bytes,
+                                       const int64_t* cap_off, const char* cap_bytes,
+                                       int32_t* status_out, int32_t* n_cards_out,
+                                       int64_t* cap_out, int32_t* n_dropped_out,
+                                       int32_t* need_cards);
+int pas_gas_nodes_update_strings_names_device(
+    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_updates, int64_t n_name_bytes,
+    const int64_t* d_node_name_off, const char* d_node_name_bytes, const int32_t* d_upd_state,
+    int64_t n_label_bytes, const int64_t* d_label_off, const char* d_label_bytes,
+    int64_t n_cap_bytes, const int64_t* d_cap_off, const char* d_cap_bytes,
+    int32_t* d_status_out, int32_t* d_n_cards_out, int64_t* d_cap_out, int32_t* d_n_dropped_out,
+    int32_t* need_cards, void* hip_stream);
+/* The parse and the resolve alone: every update against the resident row (no chaining), nothing
+ * resident is written and no generation is checked.  gpu_count_out [U] is the number of pieces
+ * (0 unless LABEL), src_out [U][max_cards] the slot map pas_gas_nodes_update would take
+ * (identity for GONE and NO_LABEL; all -1 for a settled update and for a distinct count above
+ * max_cards, which n_cards_out reports, capped at PAS_GAS_MAX_CARDS + 1).  Every output except
+ * status_out may be NULL.  The _device form is asynchronous on hip_stream. */
+int pas_gas_nodes_resolve_strings(pas_ctx* ctx, int32_t n_updates, const int32_t* upd_node,
+                                  const int32_t* upd_state, const int64_t* label_off,
+                                  const char* label_bytes, const int64_t* cap_off,
+                                  const char* cap_bytes, int32_t* status_out,
+                                  int32_t* n_cards_out, int32_t* gpu_count_out, int64_t* cap_out,
+                                  int32_t* src_out /*[U][max_cards]*/, int32_t* n_dropped_out);
+int pas_gas_nodes_resolve_strings_device(
+    pas_ctx* ctx, int32_t n_updates, const int32_t* d_upd_node, const int32_t* d_upd_state,
+    int64_t n_label_bytes, const int64_t* d_label_off, const char* d_label_bytes,
+    int64_t n_cap_bytes, const int64_t* d_cap_off, const char* d_cap_bytes,
+    int32_t* d_status_out, int32_t* d_n_cards_out, int32_t* d_gpu_count_out, int64_t* d_cap_out,
+    int32_t* d_src_out, int32_t* d_n_dropped_out, void* hip_stream);
+/* One cards label on the host, the same routines (csrc/label_fixed.h): *n_pieces = 1 +
+ * count('.'), *n_cards = the distinct pieces, counted up to PAS_GAS_MAX_CARDS + 1 (a label costs
+ * time linear in its bytes per card counted), and name_span [cap][2] = (begin, length) of the
+ * first cap cards in rank order.  No context; PAS_EINVAL for a negative size or a missing
+ * array. */
+int pas_gas_label_parse(const char* bytes, int64_t len, int64_t* n_pieces, int32_t* n_cards,
+                        int64_t* name_span /*[cap][2]*/, int64_t cap);
+
 /* Grow the resident snapshot in place: n_nodes_new >= n_nodes and max_cards_new >= max_cards,
  * PAS_EINVAL for a smaller value (PAS_ECAPACITY past PAS_GAS_MAX_CARDS).  Content is kept (the
  * rows are re-pitched on the device, no host copy); new node slots have n_cards -1, cap 0 and
@@ -1692,6 +1804,11 @@ int pas_gas_card_names_info(const pas_ctx* ctx, int32_t* n_slots, int32_t* k, in
  * when cap >= the live bytes, else PAS_ECAPACITY (the size needed is name_off_out[n_slots * k],
  * and in the message; n_bytes of _info is always enough). */
 int pas_gas_card_names_get(pas_ctx* ctx, int64_t* name_off_out, char* bytes_out, int64_t cap);
+/* The same for the rows row_slot[0 .. n_rows) alone, in call order (a slot may repeat; one outside
+ * the table is PAS_EINVAL): name_off_out [n_rows * k + 1], and bytes_out [cap] when cap >= those
+ * rows' bytes, else PAS_ECAPACITY with the offsets delivered. */
+int pas_gas_card_names_get_rows(pas_ctx* ctx, int32_t n_rows, const int32_t* row_slot,
+                                int64_t* name_off_out, char* bytes_out, int64_t cap);
 int pas_gas_card_names_drop(pas_ctx* ctx);
 
 /* ------------------------------------------------------------------------- */

@@ -85,6 +85,13 @@ int gather_in(pas_ctx* ctx, GasCardNames& t, int32_t n_slots_new, const int32_t*
 
 }  // namespace
 
+int card_names_gather_dead(pas_ctx* ctx, hipStream_t s, const std::string& fn) {
+  GasCardNames& t = ctx->gas_cards;
+  if (t.sp.pool_used - t.sp.live_bytes > t.sp.live_bytes)  // more dead bytes than live ones
+    return gather_in(ctx, t, t.n_slots, nullptr, s, fn);
+  return PAS_OK;
+}
+
 }  // namespace pas
 
 using namespace pas;
@@ -185,9 +192,7 @@ int pas_gas_card_names_update(pas_ctx* ctx, int32_t n_rows, const int32_t* row_s
     sp.live_bytes += b - t.row_bytes[row_slot[r]];
     t.row_bytes[row_slot[r]] = b;
   }
-  if (sp.pool_used - sp.live_bytes > sp.live_bytes)  // more dead bytes than live ones
-    return gather_in(ctx, t, t.n_slots, nullptr, s, fn);
-  return PAS_OK;
+  return card_names_gather_dead(ctx, s, fn);
 }
 
 int pas_gas_card_names_resize(pas_ctx* ctx, int32_t n_slots_new, int32_t k_new,
@@ -249,6 +254,24 @@ int pas_gas_card_names_get(pas_ctx* ctx, int64_t* name_off_out, char* bytes_out,
   GasCardNames& t = ctx->gas_cards;
   if (!t.valid) return no_table(ctx, fn, kTable);
   return pool_get(ctx, t.sp, (int64_t)t.n_slots * t.k, name_off_out, bytes_out, cap, nullptr, fn);
+}
+
+int pas_gas_card_names_get_rows(pas_ctx* ctx, int32_t n_rows, const int32_t* row_slot,
+                                int64_t* name_off_out, char* bytes_out, int64_t cap) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_gas_card_names_get_rows";
+  GasCardNames& t = ctx->gas_cards;
+  if (!t.valid) return no_table(ctx, fn, kTable);
+  if (n_rows < 0 || (n_rows > 0 && !row_slot)) return set_error(ctx, PAS_EINVAL, fn + ": bad rows");
+  int64_t total = 0;
+  for (int32_t r = 0; r < n_rows; ++r) {
+    if (row_slot[r] < 0 || row_slot[r] >= t.n_slots)
+      return set_error(ctx, PAS_EINVAL, fn + ": row " + std::to_string(r) + " names slot " +
+                                            std::to_string(row_slot[r]) + ", the table has " +
+                                            std::to_string(t.n_slots));
+    total += t.row_bytes[row_slot[r]];
+  }
+  return pool_get_rows(ctx, t.sp, n_rows, t.k, row_slot, total, name_off_out, bytes_out, cap, fn);
 }
 
 int pas_gas_card_names_drop(pas_ctx* ctx) {

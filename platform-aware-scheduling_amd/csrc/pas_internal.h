@@ -307,7 +307,10 @@ enum SlotBuf {
   // the same batch's per-event words, sized before it: the largest pending list, verdicts,
   // listed counts, the nodes handed to the walker and the slots of the nodes given by name
   kBufAnnotEvents = 11,
-  kSlotBufs = 12
+  // the per-update words, slot maps, capacities, new spans and scan storage of a node-event batch
+  // given as strings (gas_node_strings.hip)
+  kBufNodeStrings = 12,
+  kSlotBufs = 13
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -535,6 +538,10 @@ int gas_apply_annotations_launch(pas_ctx* ctx, int32_t n_events, const int32_t* 
                                  const int32_t* d_ncont, int64_t n_ann_bytes,
                                  const int64_t* d_ann_off, const char* d_ann_bytes,
                                  int32_t* d_status, hipStream_t s);
+// The card-name table's pool gathered on s when its dead bytes have passed the live ones
+// (gas_cards.hip: the rule of pas_gas_card_names_update), for a caller that appended rows on the
+// device and kept row_bytes / live_bytes / pool_used in step (gas_node_strings.hip).
+int card_names_gather_dead(pas_ctx* ctx, hipStream_t s, const std::string& fn);
 // The resident snapshot gathered into storage of n_nodes_new (>= the resident count) x
 // n_metrics_new (tas_reshape.hip): new column m is old column src_col[m] or, for -1, empty
 // (src_col: host [n_metrics_new], distinct old columns or -1; the caller has checked it and

@@ -15,4 +15,10 @@ int pas_quantity_parse_fixed(const char* bytes, int64_t len, int64_t* whole, uin
   return r.status;
 }
 
+int pas_quantity_as_int64_fixed(const char* bytes, int64_t len, int64_t* out) {
+  const pas::QuantityFixed r = pas::parse_quantity_fixed(bytes, len);
+  if (out) *out = r.as_int64;
+  return r.status;
+}
+
 }  // extern "C"

@@ -46,6 +46,7 @@ struct QuantityFixed {
   uint32_t nano;
   int32_t decimals;  // pas_quantity_decimals (0 for PAS_EINVAL)
   int32_t fit;       // the largest s in 0..9 at which pas_quantity_to_scaled succeeds, or -1
+  int64_t as_int64;  // pas_quantity_as_int64: 0 for an inf.Dec, a negative scale or an overflow
 };
 
 namespace qf {
@@ -128,6 +129,7 @@ PAS_QF_HD inline QuantityFixed parse_quantity_fixed(const char* p, int64_t len) 
   r.nano = 0;
   r.decimals = 0;
   r.fit = -1;
+  r.as_int64 = 0;
   if (!p || len <= 0) return r;
 
   // ---- parseQuantityString: sign, integer digits (leading zeros stripped), fraction, suffix
@@ -298,6 +300,10 @@ PAS_QF_HD inline QuantityFixed parse_quantity_fixed(const char* p, int64_t len) 
     }
     r.fit = s;
   }
+  // AsInt64: an int64Amount of scale >= 0 is the integer q (rem is 0), inside int64 or 0; the
+  // scale is exponent - dlen, and 0 under a binary suffix (dlen is 0 on its fast path)
+  if (fast && (binary || (int64_t)exponent - dlen >= 0) && q <= (uint64_t)INT64_MAX)
+    r.as_int64 = positive ? (int64_t)q : -(int64_t)q;
   r.status = PAS_OK;
   return r;
 }

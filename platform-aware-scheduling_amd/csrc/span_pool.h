@@ -79,6 +79,13 @@ int pool_gathered(pas_ctx* ctx, const SpanPool& src, int64_t n_rows_new, int32_t
 int pool_get(pas_ctx* ctx, const SpanPool& sp, int64_t n, int64_t* off_out, char* bytes_out,
              int64_t cap, const DerivedSync* after, const std::string& fn);
 
+// The rows row_slot[0 .. n_rows) (host array, every entry a row of sp) of k entries each, in call
+// order: offsets [n_rows * k + 1] and their bytes, `total` of them (the caller's count); the
+// capacity rule, stream and synchronization of pool_get.
+int pool_get_rows(pas_ctx* ctx, const SpanPool& sp, int64_t n_rows, int32_t k,
+                  const int32_t* row_slot, int64_t total, int64_t* off_out, char* bytes_out,
+                  int64_t cap, const std::string& fn);
+
 // New span arrays of n_rows_new x k_new entries holding the n_rows_old x k_old ones (the rest
 // empty), swapped in; the pool as it is.  Synchronous on s.
 int pool_repitch(pas_ctx* ctx, SpanPool& sp, int64_t n_rows_old, int32_t k_old,

@@ -262,6 +262,46 @@ int pool_get(pas_ctx* ctx, const SpanPool& sp, int64_t n, int64_t* off_out, char
   return PAS_OK;
 }
 
+int pool_get_rows(pas_ctx* ctx, const SpanPool& sp, int64_t n_rows, int32_t k,
+                  const int32_t* row_slot, int64_t total, int64_t* off_out, char* bytes_out,
+                  int64_t cap, const std::string& fn) {
+  if (!off_out || cap < 0 || (cap > 0 && !bytes_out))
+    return set_error(ctx, PAS_EINVAL, fn + ": null output or cap < 0");
+  int rc = activate(ctx);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  const int64_t n = n_rows * k;
+  const bool fits = cap >= total;
+  size_t scan_bytes = 0;
+  if ((rc = scan_size<int64_t>(ctx, (size_t)n + 1, &scan_bytes))) return rc;
+  Staging st(ctx);
+  int32_t* d_rows;
+  int64_t *d_off, *d_len;
+  char *d_bytes, *d_scan;
+  st.in(d_rows, row_slot, (size_t)n_rows);
+  st.out(d_off, off_out, (size_t)n + 1);
+  st.out(d_bytes, bytes_out, fits ? (size_t)total : 0);
+  st.work(d_len, (size_t)n + 1);
+  st.work(d_scan, scan_bytes);
+  if ((rc = st.upload())) return rc;
+  PAS_HIP(ctx, hipMemsetAsync(d_len + n, 0, sizeof(int64_t), s));
+  if (n > 0) {
+    spans_remap_lens<<<blocks_for(n), kTpb, 0, s>>>(n, k, d_rows, sp.len, d_len, nullptr);
+    PAS_HIP(ctx, hipGetLastError());
+  }
+  if ((rc = scan_run<int64_t>(ctx, d_scan, scan_bytes, d_len, d_off, (size_t)n + 1, s))) return rc;
+  if (fits && n > 0) {
+    spans_gather<<<blocks_for(n), kTpb, 0, s>>>(n, k, d_rows, sp.beg, sp.len, sp.pool, d_off,
+                                                d_bytes, total);
+    PAS_HIP(ctx, hipGetLastError());
+  }
+  PAS_HIP(ctx, st.fetch());
+  if (!fits)
+    return set_error(ctx, PAS_ECAPACITY, fn + ": " + std::to_string(total) +
+                                             " bytes of names, cap " + std::to_string(cap));
+  return PAS_OK;
+}
+
 int pool_repitch(pas_ctx* ctx, SpanPool& sp, int64_t n_rows_old, int32_t k_old,
                  int64_t n_rows_new, int32_t k_new, hipStream_t s, const char* table,
                  const std::string& fn) {

@@ -48,6 +48,7 @@ PAS_TAS_FILTER = 1
 PAS_TAS_PRIORITIZE = 2
 
 PAS_GAS_MAX_CARDS = 64
+PAS_GAS_NODE_GONE, PAS_GAS_NODE_NO_LABEL, PAS_GAS_NODE_LABEL = -1, 0, 1
 PAS_GAS_MAX_RES = 4
 PAS_GAS_MAX_SELECTIONS = 64
 PAS_GAS_PACKED = 8
@@ -134,6 +135,7 @@ SIGNATURES = {
     "pas_tas_snapshot_update_wide": (c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P]),
     "pas_tas_snapshot_update_wide_device": (
         c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P]),
+    "pas_quantity_as_int64_fixed": (c_int, [c_char_p, c_int64, POINTER(c_int64)]),
     "pas_quantity_parse_fixed": (
         c_int, [c_char_p, c_int64, POINTER(c_int64), POINTER(c_uint32), POINTER(c_int32),
                 POINTER(c_int32)]),
@@ -304,7 +306,28 @@ SIGNATURES = {
                 _P, _P]),
     "pas_gas_annotation_parse": (
         c_int, [c_char_p, c_int64, c_int32, POINTER(c_int64), _P, POINTER(c_int64), _P, c_int64]),
+    "pas_gas_label_parse": (
+        c_int, [c_char_p, c_int64, POINTER(c_int64), POINTER(c_int32), _P, c_int64]),
+    # node events from label and allocatable strings (csrc/gas_node_strings.hip)
+    "pas_gas_nodes_update_strings": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                POINTER(c_int32)]),
+    "pas_gas_nodes_update_strings_device": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P,
+                _P, _P, POINTER(c_int32), _P]),
+    "pas_gas_nodes_update_strings_names": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                POINTER(c_int32)]),
+    "pas_gas_nodes_update_strings_names_device": (
+        c_int, [_P, c_uint64, c_uint64, c_int32, c_int64, _P, _P, _P, c_int64, _P, _P, c_int64,
+                _P, _P, _P, _P, _P, _P, POINTER(c_int32), _P]),
+    "pas_gas_nodes_resolve_strings": (
+        c_int, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pas_gas_nodes_resolve_strings_device": (
+        c_int, [_P, c_int32, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P,
+                _P]),
     # the resident card-name table (csrc/gas_cards.hip)
+    "pas_gas_card_names_get_rows": (c_int, [_P, c_int32, _P, _P, _P, c_int64]),
     "pas_gas_card_names_set": (c_int, [_P, c_int32, c_int32, _P, _P]),
     "pas_gas_card_names_update": (c_int, [_P, c_int32, _P, _P, _P]),
     "pas_gas_card_names_resize": (c_int, [_P, c_int32, c_int32, _P]),

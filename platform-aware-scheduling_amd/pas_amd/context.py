@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 from ctypes import byref, c_double, c_int32, c_int64, c_uint64, c_void_p
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -116,6 +116,31 @@ def quantity_parse_fixed(q) -> Tuple[int, int, int, int, int]:
     rc = _lib.load().pas_quantity_parse_fixed(b, len(b), byref(whole), byref(nano), byref(dec),
                                               byref(fit))
     return rc, whole.value, nano.value, dec.value, fit.value
+
+
+def quantity_as_int64_fixed(q) -> Tuple[int, int]:
+    """(status, value) of one literal (str or bytes, no terminator needed) from the fixed-width
+    parser the device runs (pas_quantity_as_int64_fixed): value is quantity_as_int64's answer, the
+    status is quantity_parse_fixed's and is returned, not raised."""
+    b = q.encode() if isinstance(q, str) else bytes(q)
+    out = c_int64()
+    rc = _lib.load().pas_quantity_as_int64_fixed(b, len(b), byref(out))
+    return rc, out.value
+
+
+def gas_label_parse(label, cap: Optional[int] = None):
+    """(n_pieces, n_cards, spans) of one "gpu.intel.com/cards" label (str or bytes, no terminator
+    needed) from the routine the device runs (pas_gas_label_parse, csrc/label_fixed.h): the
+    pieces of the split on ".", the distinct ones counted up to PAS_GAS_MAX_CARDS + 1, and the
+    (begin, length) spans of the first cap cards (default: all counted) in rank order."""
+    b = label.encode() if isinstance(label, str) else bytes(label)
+    n = _lib.PAS_GAS_MAX_CARDS + 1 if cap is None else int(cap)
+    spans = np.full((max(n, 1), 2), -7, np.int64)
+    pieces, cards = c_int64(), ctypes.c_int32()
+    rc = _lib.load().pas_gas_label_parse(b, len(b), byref(pieces), byref(cards), _ptr(spans), n)
+    if rc != _lib.PAS_OK:
+        raise PasError(rc, "pas_gas_label_parse")
+    return pieces.value, cards.value, [tuple(x) for x in spans[:min(n, cards.value)].tolist()]
 
 
 def name_hash(name) -> int:
@@ -1415,6 +1440,30 @@ class Context:
                     "pas_gas_card_names_get")
         return off, buf[:int(off[-1])].tobytes()
 
+    def gas_card_names_get_rows(self, row_slot, decode: bool = False) -> List[list]:
+        """The names of the rows row_slot alone (pas_gas_card_names_get_rows): per row its k
+        names in slot order, as bytes, or with decode as str (UTF-8, undecodable bytes as
+        surrogate escapes)."""
+        rows = np.ascontiguousarray(row_slot, dtype=np.int32).reshape(-1)
+        _, k, nb = self.gas_card_names_info()
+        off = np.zeros(len(rows) * k + 1, np.int64)
+        buf = np.zeros(max(nb, 1), np.uint8)
+        rc = self._l.pas_gas_card_names_get_rows(
+            self._h, len(rows), _ptr(rows) if rows.size else None, _ptr(off), _ptr(buf), nb)
+        if rc == _lib.PAS_ECAPACITY:  # (rows repeated past the pool's size)
+            buf = np.zeros(int(off[-1]), np.uint8)
+            rc = self._l.pas_gas_card_names_get_rows(self._h, len(rows), _ptr(rows), _ptr(off),
+                                                     _ptr(buf), len(buf))
+        self._check(rc, "pas_gas_card_names_get_rows")
+        raw, o = buf[:int(off[-1])].tobytes(), off.tolist()
+        if decode and raw.isascii():  # byte offsets are character offsets: one decode
+            raw = raw.decode()
+            decode = False
+        out = [[raw[o[i]:o[i + 1]] for i in range(r * k, r * k + k)] for r in range(len(rows))]
+        if decode:
+            out = [[c.decode("utf-8", "surrogateescape") for c in row] for row in out]
+        return out
+
     def gas_card_names_drop(self):
         self._check(self._l.pas_gas_card_names_drop(self._h), "pas_gas_card_names_drop")
 
@@ -1461,6 +1510,131 @@ class Context:
                                           _ptr(n_cards), _ptr(cap), _ptr(src), _ptr(st))
         self._check(rc, "pas_gas_nodes_update")
         return st
+
+    def _node_strings(self, u, states, label_off, cap_off):
+        q = self.gas_shape[2]
+        states = np.ascontiguousarray(states, dtype=np.int32).reshape(-1)
+        l_off, u2 = self._csr(label_off)
+        c_off, uq = self._csr(cap_off)
+        assert states.shape == (u,) and u2 == u and uq == u * q, \
+            "one state and label per update, n_res literals per update"
+        return states, l_off, c_off
+
+    def _nodes_update_strings(self, fn, gen_from, gen_to, u, head, states, label_off, label_blob,
+                              cap_off, cap_blob):
+        q = self.gas_shape[2]
+        states, l_off, c_off = self._node_strings(u, states, label_off, cap_off)
+        st = np.zeros(max(u, 1), np.int32)
+        n_cards = np.zeros(max(u, 1), np.int32)
+        cap = np.zeros((max(u, 1), max(q, 1)), np.int64)
+        dropped = np.zeros(max(u, 1), np.int32)
+        need = c_int32()
+        rc = getattr(self._l, fn)(
+            self._h, gen_from, gen_to, u, *head, _ptr(states), _ptr(l_off),
+            _ptr(self._blob(label_blob)), _ptr(c_off), _ptr(self._blob(cap_blob)), _ptr(st),
+            _ptr(n_cards), _ptr(cap.reshape(-1)[:max(u * q, 1)]), _ptr(dropped), byref(need))
+        if rc == _lib.PAS_ECAPACITY:
+            e = PasError(rc, f"{fn}: {self.last_error()}")
+            e.need_cards = need.value
+            raise e
+        self._check(rc, fn)
+        return st[:u], n_cards[:u], cap.reshape(-1)[:u * q].reshape(u, q), dropped[:u]
+
+    def gas_nodes_update_strings(self, gen_from: int, gen_to: int, nodes, states, label_off,
+                                 label_blob, cap_off, cap_blob):
+        """Node events from strings (pas_gas_nodes_update_strings): update u gives node slot
+        nodes[u] the state states[u] (PAS_GAS_NODE_GONE / NO_LABEL / LABEL), the cards label
+        label_blob[label_off[u]:label_off[u + 1]] and one allocatable literal per resource kind,
+        cap_blob[cap_off[u * Q + q]:...] (snapshot.pack_node_strings).  Returns (status [U],
+        n_cards [U], cap [U][Q], n_dropped [U]).  PasError(PAS_ECAPACITY) carries need_cards, the
+        largest distinct card count: nothing has changed, grow by a tier and call again."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        return self._nodes_update_strings("pas_gas_nodes_update_strings", gen_from, gen_to,
+                                          len(nodes), (_ptr(nodes) if nodes.size else None,),
+                                          states, label_off, label_blob, cap_off, cap_blob)
+
+    def gas_nodes_update_strings_names(self, gen_from: int, gen_to: int, node_name_off,
+                                       node_name_blob, states, label_off, label_blob, cap_off,
+                                       cap_blob):
+        """The same with each update's node given by name, resolved through the name table
+        (pas_gas_nodes_update_strings_names): first-seen nodes take their slots through
+        names_assign beforehand."""
+        n_off, u = self._csr(node_name_off)
+        return self._nodes_update_strings("pas_gas_nodes_update_strings_names", gen_from, gen_to,
+                                          u, (_ptr(n_off), _ptr(self._blob(node_name_blob))),
+                                          states, label_off, label_blob, cap_off, cap_blob)
+
+    def gas_nodes_resolve_strings(self, nodes, states, label_off, label_blob, cap_off, cap_blob):
+        """The parse and the resolve alone (pas_gas_nodes_resolve_strings), nothing resident
+        written: (status [U], n_cards [U], gpu_count [U], cap [U][Q], src [U][max_cards],
+        n_dropped [U])."""
+        _, k, q = self.gas_shape
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        u = len(nodes)
+        states, l_off, c_off = self._node_strings(u, states, label_off, cap_off)
+        st, n_cards, gpus, dropped = (np.zeros(max(u, 1), np.int32) for _ in range(4))
+        cap = np.zeros(max(u * q, 1), np.int64)
+        src = np.zeros(max(u * k, 1), np.int32)
+        rc = self._l.pas_gas_nodes_resolve_strings(
+            self._h, u, _ptr(nodes) if nodes.size else None, _ptr(states), _ptr(l_off),
+            _ptr(self._blob(label_blob)), _ptr(c_off), _ptr(self._blob(cap_blob)), _ptr(st),
+            _ptr(n_cards), _ptr(gpus), _ptr(cap), _ptr(src), _ptr(dropped))
+        self._check(rc, "pas_gas_nodes_resolve_strings")
+        return (st[:u], n_cards[:u], gpus[:u], cap[:u * q].reshape(u, q),
+                src[:u * k].reshape(u, k), dropped[:u])
+
+    def gas_nodes_update_strings_device(self, gen_from: int, gen_to: int, n_updates: int, nodes_t,
+                                        states_t, n_label_bytes: int, label_off_t, label_bytes_t,
+                                        n_cap_bytes: int, cap_off_t, cap_bytes_t, status_t,
+                                        n_cards_t=None, cap_t=None, dropped_t=None,
+                                        stream=None) -> int:
+        """pas_gas_nodes_update_strings_device on device tensors: synchronizes the stream once
+        per run position (once for a batch without a repeated node); returns need_cards.
+        PasError(PAS_ECAPACITY) carries need_cards too."""
+        need = c_int32()
+        rc = self._l.pas_gas_nodes_update_strings_device(
+            self._h, gen_from, gen_to, n_updates, _dptr(nodes_t), _dptr(states_t), n_label_bytes,
+            _dptr(label_off_t), _dptr(label_bytes_t), n_cap_bytes, _dptr(cap_off_t),
+            _dptr(cap_bytes_t), _dptr(status_t), _dptr(n_cards_t), _dptr(cap_t),
+            _dptr(dropped_t), byref(need), _stream(stream))
+        if rc == _lib.PAS_ECAPACITY:
+            e = PasError(rc, f"pas_gas_nodes_update_strings_device: {self.last_error()}")
+            e.need_cards = need.value
+            raise e
+        self._check(rc, "pas_gas_nodes_update_strings_device")
+        return need.value
+
+    def gas_nodes_update_strings_names_device(self, gen_from: int, gen_to: int, n_updates: int,
+                                              n_name_bytes: int, name_off_t, name_bytes_t,
+                                              states_t, n_label_bytes: int, label_off_t,
+                                              label_bytes_t, n_cap_bytes: int, cap_off_t,
+                                              cap_bytes_t, status_t, n_cards_t=None, cap_t=None,
+                                              dropped_t=None, stream=None) -> int:
+        need = c_int32()
+        rc = self._l.pas_gas_nodes_update_strings_names_device(
+            self._h, gen_from, gen_to, n_updates, n_name_bytes, _dptr(name_off_t),
+            _dptr(name_bytes_t), _dptr(states_t), n_label_bytes, _dptr(label_off_t),
+            _dptr(label_bytes_t), n_cap_bytes, _dptr(cap_off_t), _dptr(cap_bytes_t),
+            _dptr(status_t), _dptr(n_cards_t), _dptr(cap_t), _dptr(dropped_t), byref(need),
+            _stream(stream))
+        if rc == _lib.PAS_ECAPACITY:
+            e = PasError(rc, f"pas_gas_nodes_update_strings_names_device: {self.last_error()}")
+            e.need_cards = need.value
+            raise e
+        self._check(rc, "pas_gas_nodes_update_strings_names_device")
+        return need.value
+
+    def gas_nodes_resolve_strings_device(self, n_updates: int, nodes_t, states_t,
+                                         n_label_bytes: int, label_off_t, label_bytes_t,
+                                         n_cap_bytes: int, cap_off_t, cap_bytes_t, status_t,
+                                         n_cards_t=None, gpus_t=None, cap_t=None, src_t=None,
+                                         dropped_t=None, stream=None):
+        rc = self._l.pas_gas_nodes_resolve_strings_device(
+            self._h, n_updates, _dptr(nodes_t), _dptr(states_t), n_label_bytes,
+            _dptr(label_off_t), _dptr(label_bytes_t), n_cap_bytes, _dptr(cap_off_t),
+            _dptr(cap_bytes_t), _dptr(status_t), _dptr(n_cards_t), _dptr(gpus_t), _dptr(cap_t),
+            _dptr(src_t), _dptr(dropped_t), _stream(stream))
+        self._check(rc, "pas_gas_nodes_resolve_strings_device")
 
     def gas_nodes_update_device(self, gen_from: int, gen_to: int, n_updates: int, nodes_t,
                                 n_cards_t, cap_t, src_t, status_t, stream=None):

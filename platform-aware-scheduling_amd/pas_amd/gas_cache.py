@@ -15,7 +15,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .snapshot import card_remap, gas_node_row, pack_card_names, pack_names, parse_annotation
+from .snapshot import (card_remap, gas_node_row, pack_card_names, pack_names, pack_node_strings,
+                       parse_annotation)
 
 CARD_ANNOTATION = "gas-container-cards"  # cardAnnotationName (scheduler.go)
 
@@ -137,13 +138,34 @@ class GasCache:
     pas_names_assign (the lowest spare slot, which is the slot chosen here), and growth,
     compact and rebuild keep both tables in step.  Outcomes, annotated, card_names, parked and
     the resident usage are those of the default mode.  max_cards names the snapshot's card
-    slots per node when the context cannot tell (from_nodes passes it)."""
+    slots per node when the context cannot tell (from_nodes passes it).
+
+    device_nodes=True (with device_events) leaves the string work of a node event to the device
+    as well: a node batch is one pas_gas_nodes_update_strings_names call over the nodes' names,
+    cards labels and allocatable literals as the informer hands them over
+    (snapshot.pack_node_strings: nothing is split, sorted, parsed or looked up on the host).  The
+    batch closes when a node name repeats, the rule pod batches follow per key.  First-seen names
+    take their slots through pas_names_assign before the call (PAS_ECAPACITY there grows the
+    node slots), and afterwards card_names[slot] and parked[slot] of the touched slots are read
+    back with pas_gas_card_names_get_rows, n_cards and cap come from the call's outputs, and
+    "dropped: ..." is the old host row minus the row read back, in old order.  PAS_ECAPACITY of
+    the strings call changed nothing: a batch of several items is sent again in two halves, a
+    single item grows the card slots to the tier its label needs and is sent again, so every
+    item meets the max_cards the default mode gives it.  Outcomes, card_names, parked and the
+    resident state equal the default mode's but for one case: a parked card named "" is an
+    unused slot to the device (pas.h), so a card "" that leaves the label is parked once and
+    forgotten by the next label update of its node, with its usage.
+    from_nodes(..., device_nodes=True) is the cold start: an empty snapshot of the smallest
+    tier and empty tables, then the nodes as one batch."""
 
     def __init__(self, ctx, gen: int, node_names: Sequence[str],
                  card_names: Sequence[Sequence[str]], kinds: Sequence[str],
                  n_cards=None, cap=None,
                  requests: Optional[Callable[[dict], Tuple[np.ndarray, np.ndarray, int]]] = None,
-                 device_events: bool = False, max_cards: Optional[int] = None):
+                 device_events: bool = False, max_cards: Optional[int] = None,
+                 device_nodes: bool = False):
+        if device_nodes and not device_events:
+            raise ValueError("device_nodes needs device_events: the tables are installed by it")
         if device_events and "" in node_names:
             raise ValueError("device_events: the empty node name marks a spare slot")
         self.ctx, self.gen = ctx, gen
@@ -159,6 +181,7 @@ class GasCache:
         self.annotated: Dict[str, str] = {}  # annotatedPods
         self._queue: List[Tuple[str, dict, str]] = []  # (action, pod or node, annotation)
         self.device_events = bool(device_events)
+        self.device_nodes = bool(device_nodes)
         if self.device_events:
             k = self._k()
             ctx.gas_card_names_set(len(self.node_names), k,
@@ -171,6 +194,24 @@ class GasCache:
         """A cache over a fresh snapshot of the v1.Node objects `nodes` (zero usage) plus
         spare_nodes spare slots, uploaded as generation gen; max_cards is the smallest of
         8 / 16 / 64 that holds the largest label."""
+        if kw.get("device_nodes"):  # nothing is read on the host: the nodes are the first batch
+            n, k = len(nodes) + int(spare_nodes), CARD_TIERS[0]
+            n_cards, cap = np.full(n, -1, np.int32), np.zeros((n, len(kinds)), np.int64)
+            ctx.gas_snapshot_set(gen, n_cards, cap, np.zeros((n, k, len(kinds)), np.int64))
+            cache = cls(ctx, gen, [None] * n, [[] for _ in range(n)], kinds, n_cards=n_cards,
+                        cap=cap, max_cards=k, **kw)
+            names = [_node_name(node) for node in nodes]
+            if "" in names:
+                raise ValueError("device_events: the empty node name marks a spare slot")
+            if len(set(names)) == len(names):  # one batch, past the queue and its result list
+                if nodes:
+                    cache._send_node_strings([(name, NODE_ADDED, node)
+                                              for name, node in zip(names, nodes)])
+            else:
+                for node in nodes:
+                    cache.add_node(node)
+                cache.flush()
+            return cache
         rows = [gas_node_row(_node_dict(node), kinds) for node in nodes]
         names: List[Optional[str]] = [_node_name(node) for node in nodes]
         n, q = len(rows) + int(spare_nodes), len(kinds)
@@ -319,6 +360,75 @@ class GasCache:
                 *pack_card_names([u[4] for u in updates], None, self._k()))
         return [int(s) for s in st]
 
+    def _own_rows(self):
+        if self.n_cards is not None and self.cap is not None and not self._rows_owned:
+            self.n_cards = np.array(self.n_cards, np.int32)  # the caller's arrays stay
+            self.cap = np.array(self.cap, np.int64)
+            self._rows_owned = True
+
+    def _send_node_strings(self, items) -> List[str]:
+        """device_nodes: the outcomes of one batch of node items (name, action, node), no name
+        twice, as one pas_gas_nodes_update_strings_names call (two halves, or a larger tier, on
+        PAS_ECAPACITY)."""
+        names = [name for name, _, _ in items]
+        live = [name for name, action, _ in items if action != NODE_DELETED]
+        slot_of: Dict[str, int] = {}
+        while live:  # first-seen names take the lowest spare slots, in order
+            try:
+                slots, _, _ = self.ctx.names_assign(*pack_names(live))
+                slot_of.update(zip(live, slots.tolist()))
+                for name, slot in slot_of.items():
+                    if self.node_names[slot] is None:
+                        self.node_names[slot] = name
+                        self.node_index[name] = slot
+                break
+            except _lib.PasError as e:
+                if e.code != _lib.PAS_ECAPACITY:
+                    raise
+                n = len(self.node_names)
+                self._grow(n + (max(64, n // 8) + 63) // 64 * 64, self._k())
+        gone = [name for name, action, _ in items if action == NODE_DELETED]
+        if gone:
+            slot_of.update(zip(gone, self.ctx.names_resolve(*pack_names(gone)).tolist()))
+        packed = pack_node_strings(
+            [None if action == NODE_DELETED else _node_dict(node) for _, action, node in items],
+            self.kinds)
+        try:
+            st, n_cards, cap, _ = self.ctx.gas_nodes_update_strings_names(
+                self.gen, self.gen + 1, *pack_names(names), *packed)
+        except _lib.PasError as e:
+            if e.code != _lib.PAS_ECAPACITY:
+                raise
+            if len(items) > 1:  # nothing has changed: the items before the large label go first
+                half = len(items) // 2
+                return (self._send_node_strings(items[:half]) +
+                        self._send_node_strings(items[half:]))
+            self._grow(len(self.node_names), _tier(int(e.need_cards)))
+            return self._send_node_strings(items)
+        self.gen += 1
+        st, labels = st.tolist(), np.maximum(n_cards, 0).tolist()
+        outcomes = [OK if s == _lib.PAS_GAS_OK else ERR_INPUT for s in st]
+        touched = [(u, slot_of[name]) for u, name in enumerate(names)
+                   if st[u] == _lib.PAS_GAS_OK and slot_of[name] >= 0]
+        if not touched:
+            return outcomes
+        at, slots = (list(x) for x in zip(*touched))
+        rows = self.ctx.gas_card_names_get_rows(slots, decode=True)
+        for u, slot, row in zip(at, slots, rows):
+            label = labels[u]
+            parked = [c for c in row[label:] if c]  # (a parked "" is an unused slot)
+            old = self.card_names[slot] + self.parked[slot]
+            self.card_names[slot], self.parked[slot] = row[:label], parked
+            if old:
+                new = set(row)
+                dropped = [c for c in old if c and c not in new]
+                if dropped:
+                    outcomes[u] = "dropped: " + ", ".join(dropped)
+        if self.n_cards is not None and self.cap is not None:
+            self._own_rows()
+            self.n_cards[slots], self.cap[slots] = n_cards[at], cap[at]
+        return outcomes
+
     # ------------------------------------------------------------ the worker
     def _plan(self, action: str, pod: dict, annotation: str):
         """handlePod's switch and adjustPodResources' argument check for one item: an outcome
@@ -411,7 +521,29 @@ class GasCache:
             node_batch.clear()
             node_slots.clear()
 
+        string_batch, string_at = [], []  # device_nodes: (name, action, node) and their i
+        string_names = set()
+
+        def close_strings():
+            if string_batch:
+                for i, item, outcome in zip(string_at, string_batch,
+                                            self._send_node_strings(string_batch)):
+                    results[i] = (item[0], item[1], outcome)
+            string_batch.clear()
+            string_at.clear()
+            string_names.clear()
+
         for i, (action, pod, annotation) in enumerate(queue):
+            if action in _NODE_ACTIONS and self.device_nodes:
+                close()  # a node item closes the open pod batch
+                name = _node_name(pod)
+                if name in string_names:
+                    close_strings()  # its row is the one the first item leaves
+                string_names.add(name)
+                string_batch.append((name, action, pod))
+                string_at.append(i)
+                continue
+            close_strings()
             if action in _NODE_ACTIONS:
                 close()  # a node item closes the open pod batch
                 outcome, update = self._plan_node(action, pod, close_nodes)
@@ -435,6 +567,7 @@ class GasCache:
             keys.add(key)
         close()
         close_nodes()
+        close_strings()
         return results  # type: ignore[return-value]
 
     def compact(self, spare_nodes: int = 0) -> List[int]:

@@ -173,6 +173,28 @@ def pack_card_names(card_names: Sequence[Sequence], parked: Optional[Sequence[Se
     return pack_names(flat)
 
 
+def pack_node_strings(nodes: Sequence[Optional[dict]], kinds: Sequence[str]):
+    """(states int32 [U], label_off int64 [U + 1], label_blob, cap_off int64 [U * Q + 1],
+    cap_blob) for Context.gas_nodes_update_strings[_names]: per node dict as gas_node_row reads
+    it ({"labels": ..., "allocatable": ...}, or None for a node the lister does not know) its
+    state (PAS_GAS_NODE_GONE / NO_LABEL / LABEL), its cards label as it is and one allocatable
+    literal per kind (empty for a kind the node does not advertise or that is no
+    "gpu.intel.com/" resource).  Nothing is split, sorted or parsed."""
+    states = np.zeros(len(nodes), np.int32)
+    labels: List = []
+    lits: List = []
+    for i, node in enumerate(nodes):
+        node_labels = (node.get("labels") or {}) if node is not None else {}
+        listed = node is not None and GPU_LIST_LABEL in node_labels
+        states[i] = (_lib.PAS_GAS_NODE_GONE if node is None else
+                     _lib.PAS_GAS_NODE_LABEL if listed else _lib.PAS_GAS_NODE_NO_LABEL)
+        labels.append(node_labels[GPU_LIST_LABEL] if listed else "")
+        alloc = (node.get("allocatable") or {}) if listed else {}
+        lits.extend(alloc[k] if k in alloc and k.startswith(RESOURCE_PREFIX) else ""
+                    for k in kinds)
+    return (states,) + pack_names(labels) + pack_names(lits)
+
+
 def go_sort_strings(names):
     """sort.Strings: bytewise order of the UTF-8 encodings ("card10" < "card2")."""
     return sorted(names, key=lambda s: s.encode())
