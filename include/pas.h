@@ -1152,6 +1152,82 @@ int pas_gas_annotation_parse(const char* bytes, int64_t len, int32_t max_contain
                              int64_t* n_segments, int32_t* cards_per_container,
                              int64_t* n_listed, int64_t* name_span /*[cap][2]*/, int64_t cap);
 
+/* Bind annotations rendered from the card-name table: the inverse of the calls above.  bindNode
+ * writes a pod's cards as the "gas-container-cards" string, card names joined by "," and the
+ * containers' segments by "|" (scheduler.go:317-335, 423-431); a placement answers in slots and
+ * counts.  Bind b is on node slot bind_node[b] with n_containers[b] containers and renders to
+ * ann_bytes_out[ann_off_out[b] .. ann_off_out[b + 1]), from one of two forms:
+ *   counts form   counts [B][max_containers][max_cards] as pas_gas_bind_counts / pas_gas_place
+ *                 give it (max_cards is the resident snapshot's): container c lists card k
+ *                 counts[c][k] times, in ascending k;
+ *   ranks form    cards_per_container [B][max_containers] and cards [B][cards_ld], the containers'
+ *                 cards consecutively: the arrays pas_gas_annotations_resolve emits and
+ *                 pas_gas_apply takes, so the render is the exact inverse of the resident parser.
+ * Card k (rank r) of the bind's node is name (node, k) of the card-name table.
+ *
+ * The grammar (csrc/annotation_fixed.h, one routine for host and device): n_containers segments
+ * joined by '|', so n_containers - 1 bars, and 0 containers render ""; a container without cards
+ * is an empty segment; the names of a segment are joined by ','.  Names are opaque bytes: the
+ * empty name renders as itself, so "a,,b" can come out, as the parser reads it.  (A segment that
+ * lists the empty name once and nothing else renders as no bytes, which the parser, like Go's
+ * Split, reads as a segment without cards: the one value whose round trip is not exact.)
+ *
+ * status_out[b]:
+ *   PAS_GAS_OK            the bind renders.  Node -1 (an unplaced pod) is PAS_GAS_OK with an
+ *                         empty span, told from a rendered "" by the node;
+ *   PAS_GAS_ERR_INPUT     with an empty span: any other node outside [0, n_nodes); a negative
+ *                         count; a nonzero count on a card slot at or past L = n_cards[node]
+ *                         clamped into [0, max_cards] (a parked or unused slot: a bind never
+ *                         selects one); a rank outside [0, L); (ranks form) more listed cards
+ *                         than cards_ld; a negative cards_per_container reads as 0;
+ *   PAS_GAS_ERR_OVERFLOW  with an empty span: otherwise, a rendered length past INT32_MAX bytes.
+ *                         The lengths are summed saturating, so counts up to INT64_MAX are
+ *                         ordinary input.
+ * Statuses, ann_off_out [B + 1] and *n_bytes_out (the byte total; may be NULL) are always
+ * delivered, the bytes only when cap >= the total; else the call returns PAS_ECAPACITY with the
+ * size in the message and writes no byte.  cap == 0 with ann_bytes_out NULL is the sizing call.
+ *
+ * PAS_ENOSNAP without a GAS snapshot or a card-name table; PAS_EINVAL, the message naming the
+ * card-name table, unless that table has n_slots == n_nodes and k == max_cards of the resident
+ * snapshot (the rule of pas_gas_apply_annotations).  The host forms return PAS_EINVAL unless
+ * every n_containers is in [0, max_containers] and every node is -1 or in [0, n_nodes); the
+ * _device forms clamp n_containers into that range and report the nodes through status_out.
+ * The _device forms synchronize hip_stream once: the byte total comes back to the host, which
+ * checks cap before the write pass is enqueued (per-stream workspace; PAS_ENOMEM if it cannot be
+ * allocated).  Nothing resident is written and no generation moves.  PAS_ABI_VERSION is
+ * unchanged: additions only. */
+int pas_gas_annotations_render(pas_ctx* ctx, int32_t n_binds, const int32_t* bind_node,
+                               const int32_t* n_containers, int32_t max_containers,
+                               const int64_t* counts, int32_t* status_out /*[n_binds]*/,
+                               int64_t* ann_off_out /*[n_binds + 1]*/, char* ann_bytes_out,
+                               int64_t cap, int64_t* n_bytes_out);
+int pas_gas_annotations_render_device(pas_ctx* ctx, int32_t n_binds, const int32_t* d_bind_node,
+                                      const int32_t* d_n_containers, int32_t max_containers,
+                                      const int64_t* d_counts, int32_t* d_status_out,
+                                      int64_t* d_ann_off_out, char* d_ann_bytes_out, int64_t cap,
+                                      int64_t* n_bytes_out, void* hip_stream);
+int pas_gas_annotations_render_ranks(pas_ctx* ctx, int32_t n_binds, const int32_t* bind_node,
+                                     const int32_t* n_containers, int32_t max_containers,
+                                     const int32_t* cards_per_container, const int32_t* cards,
+                                     int32_t cards_ld, int32_t* status_out /*[n_binds]*/,
+                                     int64_t* ann_off_out /*[n_binds + 1]*/, char* ann_bytes_out,
+                                     int64_t cap, int64_t* n_bytes_out);
+int pas_gas_annotations_render_ranks_device(
+    pas_ctx* ctx, int32_t n_binds, const int32_t* d_bind_node, const int32_t* d_n_containers,
+    int32_t max_containers, const int32_t* d_cards_per_container, const int32_t* d_cards,
+    int32_t cards_ld, int32_t* d_status_out, int64_t* d_ann_off_out, char* d_ann_bytes_out,
+    int64_t cap, int64_t* n_bytes_out, void* hip_stream);
+/* One annotation on the host, the same routine and the twin of pas_gas_annotation_parse: counts
+ * [n_containers][k] over a row of k names, name c = name_bytes[name_off[c] .. name_off[c + 1]),
+ * of which the first n_cards (clamped into [0, k]) are label cards.  *status_out and
+ * *n_bytes_out are as above; PAS_ECAPACITY (nothing written) when the length exceeds cap.  No
+ * context; PAS_EINVAL for a negative size, a missing array or offsets that do not start at 0 or
+ * decrease. */
+int pas_gas_annotation_render(int32_t n_containers, int32_t k, int32_t n_cards,
+                              const int64_t* counts, const int64_t* name_off,
+                              const char* name_bytes, int32_t* status_out, char* bytes_out,
+                              int64_t cap, int64_t* n_bytes_out);
+
 /* Read back the resident usage used[N][K][Q] and its generation. */
 int pas_gas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* used_out);
 /* Read back the resident n_cards [N] and cap_per_gpu [N][Q] and the generation. */
@@ -1707,6 +1783,22 @@ int pas_names_resolve(pas_ctx* ctx, int64_t n, const int64_t* name_off, const ch
                       int32_t* slot_out);
 int pas_names_resolve_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_name_off,
                              const char* d_bytes, int32_t* d_slot_out, void* hip_stream);
+
+/* The other direction, for a Binding's target: entry i is the name of slot slot[i] - slot_base,
+ * off_out [n + 1] and the bytes (n <= INT32_MAX).  A spare slot and a slot outside the table, -1
+ * included, render as an empty span, so the place_node of pas_gas_place goes in unchanged with
+ * its node_base; a slot may repeat.  off_out and *n_bytes_out (may be NULL) are always delivered,
+ * the bytes only when cap >= the total, else PAS_ECAPACITY with the size in the message; cap == 0
+ * with bytes_out NULL is the sizing call.  It is the scan and gather of
+ * pas_gas_annotations_render with one name per span.  Reads the table only; the _device form
+ * synchronizes hip_stream once (the byte total) and waits for the last table change like
+ * pas_names_resolve_device. */
+int pas_names_render(pas_ctx* ctx, int64_t n, const int32_t* slot, int32_t slot_base,
+                     int64_t* off_out /*[n + 1]*/, char* bytes_out, int64_t cap,
+                     int64_t* n_bytes_out);
+int pas_names_render_device(pas_ctx* ctx, int64_t n, const int32_t* d_slot, int32_t slot_base,
+                            int64_t* d_off_out, char* d_bytes_out, int64_t cap,
+                            int64_t* n_bytes_out, void* hip_stream);
 
 /* Lookup plus first-seen assignment (n <= INT32_MAX).  The distinct non-empty names without a
  * slot, in order of first appearance among the entries, receive the spare slots in ascending

@@ -231,6 +231,19 @@ void free_gas(pas_ctx* ctx) {
   g.derived_sync.ev = ev;
 }
 
+int gas_annotations_tables(pas_ctx* ctx, bool by_name, const std::string& fn) {
+  const GasCardNames& t = ctx->gas_cards;
+  if (!t.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no card-name table");
+  if (by_name && !ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
+  if (t.n_slots != ctx->gas.n_nodes || t.k != ctx->gas.max_cards)
+    return set_error(ctx, PAS_EINVAL,
+                     fn + ": the card-name table is " + std::to_string(t.n_slots) + " x " +
+                         std::to_string(t.k) + ", the GAS snapshot " +
+                         std::to_string(ctx->gas.n_nodes) + " x " +
+                         std::to_string(ctx->gas.max_cards));
+  return PAS_OK;
+}
+
 }  // namespace pas
 
 using namespace pas;
@@ -1944,22 +1957,6 @@ int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_ev
       return rc;
   }
   return gas_write_finish(ctx, gen_to, n_events > 0, st, fn);
-}
-
-// What the annotation forms share (pas_gas_annotations_resolve*, pas_gas_apply_annotations*):
-// the card-name table is there and has the resident snapshot's shape, and the name table is
-// there when the nodes come by name.  The caller has checked the snapshot.
-static int gas_annotations_tables(pas_ctx* ctx, bool by_name, const std::string& fn) {
-  const GasCardNames& t = ctx->gas_cards;
-  if (!t.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no card-name table");
-  if (by_name && !ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
-  if (t.n_slots != ctx->gas.n_nodes || t.k != ctx->gas.max_cards)
-    return set_error(ctx, PAS_EINVAL,
-                     fn + ": the card-name table is " + std::to_string(t.n_slots) + " x " +
-                         std::to_string(t.k) + ", the GAS snapshot " +
-                         std::to_string(ctx->gas.n_nodes) + " x " +
-                         std::to_string(ctx->gas.max_cards));
-  return PAS_OK;
 }
 
 // offsets [n + 1] of a host form's byte spans: from 0, non-decreasing, bytes when any

@@ -310,7 +310,11 @@ enum SlotBuf {
   // the per-update words, slot maps, capacities, new spans and scan storage of a node-event batch
   // given as strings (gas_node_strings.hip)
   kBufNodeStrings = 12,
-  kSlotBufs = 13
+  // the per-span lengths and scan storage of a render (gas_render.hip), and the rendered bytes
+  // of a host form, sized after the call's read-back
+  kBufRender = 13,
+  kBufRenderBytes = 14,
+  kSlotBufs = 15
 };
 
 // Per-call device scratch of the _device entry points (TAS rule ranges and pod descriptors,
@@ -511,6 +515,11 @@ void free_names(NameTable& t);
 int names_resolve_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
                          const char* d_bytes, int32_t* d_slot, uint64_t* d_hash,
                          uint32_t* d_unknown, bool count_empty, hipStream_t s);
+// What the annotation forms share (pas_gas_annotations_resolve*, pas_gas_apply_annotations*,
+// pas_gas_annotations_render*): the card-name table is there and has the resident snapshot's
+// shape, and the name table is there when the nodes come by name.  The caller has checked the
+// snapshot.
+int gas_annotations_tables(pas_ctx* ctx, bool by_name, const std::string& fn);
 // Pod events from annotation strings (gas_annotations.hip).  annotations_resolve_launch: the
 // parse-alone form on device arrays, enqueued on s: per event the verdict of the rules of
 // pas_gas_apply_annotations (d_kind null: no kind is checked; d_name_off non-null: d_node holds

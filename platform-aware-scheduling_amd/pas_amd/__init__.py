@@ -7,7 +7,8 @@ Importing it loads the library and fails loudly when it has not been built.
 from . import _lib
 from ._lib import (PAS_OP_EQUALS, PAS_OP_GREATER_THAN, PAS_OP_LESS_THAN, PAS_TAS_FILTER,
                    PAS_TAS_PRIORITIZE, PasError)
-from .context import (RULE_DTYPE, Context, gas_annotation_parse, label_patch_json,
+from .context import (RULE_DTYPE, Context, gas_annotation_parse, gas_annotation_render,
+                      label_patch_json,
                       label_patch_json_batch, make_rules, name_hash, parse_operator,
                       quantity_as_int64, quantity_decimals,
                       quantity_parse_fixed, quantity_to_milli, quantity_to_scaled,
@@ -18,6 +19,6 @@ LIB = _lib.load()
 __all__ = [
     "Context", "PasError", "RULE_DTYPE", "make_rules", "parse_operator", "quantity_to_milli",
     "quantity_to_scaled", "quantity_to_wide", "quantity_decimals", "quantity_parse_fixed",
-    "quantity_as_int64", "name_hash", "gas_annotation_parse", "w64", "label_patch_json", "label_patch_json_batch", "PAS_OP_LESS_THAN", "PAS_OP_GREATER_THAN", "PAS_OP_EQUALS",
+    "quantity_as_int64", "name_hash", "gas_annotation_parse", "gas_annotation_render", "w64", "label_patch_json", "label_patch_json_batch", "PAS_OP_LESS_THAN", "PAS_OP_GREATER_THAN", "PAS_OP_EQUALS",
     "PAS_TAS_FILTER", "PAS_TAS_PRIORITIZE", "LIB",
 ]

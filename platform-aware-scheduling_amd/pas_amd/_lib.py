@@ -306,6 +306,20 @@ SIGNATURES = {
                 _P, _P]),
     "pas_gas_annotation_parse": (
         c_int, [c_char_p, c_int64, c_int32, POINTER(c_int64), _P, POINTER(c_int64), _P, c_int64]),
+    # bind annotations rendered from the card-name table (csrc/gas_render.hip)
+    "pas_gas_annotations_render": (
+        c_int, [_P, c_int32, _P, _P, c_int32, _P, _P, _P, _P, c_int64, POINTER(c_int64)]),
+    "pas_gas_annotations_render_device": (
+        c_int, [_P, c_int32, _P, _P, c_int32, _P, _P, _P, _P, c_int64, POINTER(c_int64), _P]),
+    "pas_gas_annotations_render_ranks": (
+        c_int, [_P, c_int32, _P, _P, c_int32, _P, _P, c_int32, _P, _P, _P, c_int64,
+                POINTER(c_int64)]),
+    "pas_gas_annotations_render_ranks_device": (
+        c_int, [_P, c_int32, _P, _P, c_int32, _P, _P, c_int32, _P, _P, _P, c_int64,
+                POINTER(c_int64), _P]),
+    "pas_gas_annotation_render": (
+        c_int, [c_int32, c_int32, c_int32, _P, _P, _P, POINTER(c_int32), _P, c_int64,
+                POINTER(c_int64)]),
     "pas_gas_label_parse": (
         c_int, [c_char_p, c_int64, POINTER(c_int64), POINTER(c_int32), _P, c_int64]),
     # node events from label and allocatable strings (csrc/gas_node_strings.hip)
@@ -435,6 +449,9 @@ SIGNATURES = {
     "pas_names_drop": (c_int, [_P]),
     "pas_names_resolve": (c_int, [_P, c_int64, _P, _P, _P]),
     "pas_names_resolve_device": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
+    "pas_names_render": (c_int, [_P, c_int64, _P, c_int32, _P, _P, c_int64, POINTER(c_int64)]),
+    "pas_names_render_device": (
+        c_int, [_P, c_int64, _P, c_int32, _P, _P, c_int64, POINTER(c_int64), _P]),
     "pas_names_assign": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, _P, POINTER(c_int64)]),
     "pas_names_assign_device": (
         c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, _P, _P, POINTER(c_int64), _P]),

@@ -171,6 +171,42 @@ def gas_annotation_parse(annotation, max_containers: Optional[int] = None,
             [tuple(x) for x in spans[:min(n, listed.value)].tolist()])
 
 
+def gas_annotation_render(counts, card_names, n_cards: Optional[int] = None,
+                          cap: Optional[int] = None) -> Tuple[int, bytes]:
+    """(status, bytes) of one "gas-container-cards" value from counts [C][K] over the K names
+    card_names (str or bytes), of which the first n_cards (default: all) are label cards, from
+    the routine the device runs (pas_gas_annotation_render, csrc/annotation_fixed.h).  The
+    status (PAS_GAS_OK / PAS_GAS_ERR_INPUT / PAS_GAS_ERR_OVERFLOW) is returned, not raised; a cap
+    below the rendered length raises PasError(PAS_ECAPACITY) with the length in err.n_bytes."""
+    names = [n.encode() if isinstance(n, str) else bytes(n) for n in card_names]
+    k = len(names)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1, k) if k else \
+        np.zeros((len(counts), 0), np.int64)
+    off = np.zeros(k + 1, np.int64)
+    np.cumsum([len(n) for n in names], out=off[1:])
+    blob = Context._blob(b"".join(names))
+    l = _lib.load()
+    status, n_bytes = c_int32(), c_int64()
+
+    def call(buf, room):
+        return l.pas_gas_annotation_render(
+            counts.shape[0], k, k if n_cards is None else int(n_cards),
+            _ptr(counts) if counts.size else None, _ptr(off), _ptr(blob), byref(status),
+            _ptr(buf), room, byref(n_bytes))
+    rc = call(None, 0)  # the sizing call
+    if rc == _lib.PAS_ECAPACITY and (cap is None or cap >= n_bytes.value):
+        buf = np.zeros(n_bytes.value if cap is None else max(int(cap), 1), np.uint8)
+        rc = call(buf, len(buf))
+        raw = buf[:n_bytes.value].tobytes()
+    else:
+        raw = b""
+    if rc != _lib.PAS_OK:
+        err = PasError(rc, "pas_gas_annotation_render")
+        err.n_bytes = n_bytes.value
+        raise err
+    return status.value, raw
+
+
 def quantity_as_int64(q: str) -> int:
     """resource.Quantity.AsInt64 with `ok` ignored (gpuscheduler/utils.go:23)."""
     out = c_int64()
@@ -1391,6 +1427,121 @@ class Context:
             max_containers, n_ann_bytes, _dptr(ann_off_t), _dptr(ann_bytes_t), cards_ld,
             _dptr(verdict_t), _dptr(listed_t), _dptr(cpc_t), _dptr(cards_t), _stream(stream))
         self._check(rc, "pas_gas_annotations_resolve_device")
+
+    # ---- bind annotations and node names rendered on the device (csrc/gas_render.hip)
+    @staticmethod
+    def _split_spans(raw: bytes, off, decode: bool) -> list:
+        """The spans raw[off[i]:off[i + 1]] as bytes, or with decode as str (UTF-8, undecodable
+        bytes as surrogate escapes)."""
+        o = [int(x) for x in off]
+        if decode and raw.isascii():  # byte offsets are character offsets: one decode
+            raw, decode = raw.decode(), False
+        out = [raw[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+        return [s.decode("utf-8", "surrogateescape") for s in out] if decode else out
+
+    def _rendered(self, what: str, call, off, decode: bool) -> list:
+        """The sizing call, then the call with the room it asked for."""
+        total = c_int64()
+        rc = call(None, 0, byref(total))
+        buf = np.zeros(max(total.value, 1), np.uint8)
+        if rc == _lib.PAS_ECAPACITY:
+            rc = call(_ptr(buf), total.value, byref(total))
+        self._check(rc, what)
+        return self._split_spans(buf[:int(off[-1])].tobytes(), off, decode)
+
+    def gas_annotations_render(self, bind_node, n_containers, counts, decode: bool = False):
+        """The "gas-container-cards" values of binds given as counts [B][C][K] on node slots
+        bind_node (-1: an unplaced pod), from the resident card-name table
+        (pas_gas_annotations_render): (statuses [B], the B values as bytes, or as str with
+        decode).  A bind whose status is not PAS_GAS_OK renders empty."""
+        node = np.ascontiguousarray(bind_node, dtype=np.int32).reshape(-1)
+        ncont = np.ascontiguousarray(n_containers, dtype=np.int32).reshape(-1)
+        b, k = len(node), self.gas_shape[1]
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        assert len(ncont) == b and counts.size % max(b * k, 1) == 0, "counts is [B][C][K]"
+        c = counts.size // (b * k) if b else 0
+        status = np.zeros(max(b, 1), np.int32)
+        off = np.zeros(b + 1, np.int64)
+
+        def call(buf, cap, total):
+            return self._l.pas_gas_annotations_render(
+                self._h, b, _ptr(node), _ptr(ncont), c, _ptr(counts.reshape(-1)), _ptr(status),
+                _ptr(off), buf, cap, total)
+        return status[:b], self._rendered("pas_gas_annotations_render", call, off, decode)
+
+    def gas_annotations_render_ranks(self, bind_node, n_containers, cards_per_container, cards,
+                                     decode: bool = False):
+        """The same from cards_per_container [B][C] and the containers' card ranks, consecutive
+        in cards [B][cards_ld]: the arrays gas_annotations_resolve returns
+        (pas_gas_annotations_render_ranks)."""
+        node = np.ascontiguousarray(bind_node, dtype=np.int32).reshape(-1)
+        ncont = np.ascontiguousarray(n_containers, dtype=np.int32).reshape(-1)
+        b = len(node)
+        cpc = np.ascontiguousarray(cards_per_container, dtype=np.int32).reshape(b, -1 if b else 0)
+        cards = np.ascontiguousarray(cards, dtype=np.int32).reshape(b, -1 if b else 0)
+        status = np.zeros(max(b, 1), np.int32)
+        off = np.zeros(b + 1, np.int64)
+
+        def call(buf, cap, total):
+            return self._l.pas_gas_annotations_render_ranks(
+                self._h, b, _ptr(node), _ptr(ncont), cpc.shape[1] if b else 0,
+                _ptr(cpc.reshape(-1)), _ptr(cards.reshape(-1)), cards.shape[1] if b else 0,
+                _ptr(status), _ptr(off), buf, cap, total)
+        return status[:b], self._rendered("pas_gas_annotations_render_ranks", call, off, decode)
+
+    def _render_device(self, fn, what: str, head, status_t, off_t, bytes_t, cap: int, stream):
+        total = c_int64()
+        rc = fn(self._h, *head, *((_dptr(status_t),) if status_t is not None else ()),
+                _dptr(off_t), _dptr(bytes_t), cap, byref(total), _stream(stream))
+        if rc != _lib.PAS_OK:
+            msg = self._l.pas_last_error(self._h)
+            err = PasError(rc, f"{what}: {msg.decode() if msg else ''}")
+            err.n_bytes = total.value  # PAS_ECAPACITY: the room the bytes need
+            raise err
+        return total.value
+
+    def gas_annotations_render_device(self, n_binds: int, bind_node_t, ncont_t,
+                                      max_containers: int, counts_t, status_t, ann_off_t,
+                                      ann_bytes_t, cap: int, stream=None) -> int:
+        """pas_gas_annotations_render_device on device tensors; returns the byte total.  The
+        stream is synchronized once; a short cap (0 with ann_bytes_t None: the sizing call)
+        raises PasError(PAS_ECAPACITY) with the total in err.n_bytes and the statuses and
+        offsets delivered."""
+        return self._render_device(
+            self._l.pas_gas_annotations_render_device, "pas_gas_annotations_render_device",
+            (n_binds, _dptr(bind_node_t), _dptr(ncont_t), max_containers, _dptr(counts_t)),
+            status_t, ann_off_t, ann_bytes_t, cap, stream)
+
+    def gas_annotations_render_ranks_device(self, n_binds: int, bind_node_t, ncont_t,
+                                            max_containers: int, cpc_t, cards_t, cards_ld: int,
+                                            status_t, ann_off_t, ann_bytes_t, cap: int,
+                                            stream=None) -> int:
+        return self._render_device(
+            self._l.pas_gas_annotations_render_ranks_device,
+            "pas_gas_annotations_render_ranks_device",
+            (n_binds, _dptr(bind_node_t), _dptr(ncont_t), max_containers, _dptr(cpc_t),
+             _dptr(cards_t), cards_ld), status_t, ann_off_t, ann_bytes_t, cap, stream)
+
+    def names_render(self, slots, slot_base: int = 0, decode: bool = False) -> list:
+        """The names of the node slots slots[i] - slot_base from the resident name table
+        (pas_names_render), as bytes or with decode as str; a spare slot or one outside the
+        table, -1 included, gives the empty name."""
+        slot = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        off = np.zeros(len(slot) + 1, np.int64)
+
+        def call(buf, cap, total):
+            return self._l.pas_names_render(self._h, len(slot),
+                                            _ptr(slot) if slot.size else None, slot_base,
+                                            _ptr(off), buf, cap, total)
+        return self._rendered("pas_names_render", call, off, decode)
+
+    def names_render_device(self, n: int, slot_t, slot_base: int, off_t, bytes_t, cap: int,
+                            stream=None) -> int:
+        """pas_names_render_device on device tensors; returns the byte total (short cap: as
+        gas_annotations_render_device)."""
+        return self._render_device(self._l.pas_names_render_device, "pas_names_render_device",
+                                   (n, _dptr(slot_t), slot_base), None, off_t, bytes_t, cap,
+                                   stream)
 
     # ---- the resident card-name table (csrc/gas_cards.hip)
     def gas_card_names_set(self, n_slots: int, k: int, name_off, blob):

@@ -327,12 +327,19 @@ class GASExtender:
 
     The context holds the GAS snapshot (generation `gen`) built by
     pas_amd.snapshot.gas_snapshot_from_nodes over `node_names` with `card_names` and `kinds`;
-    `pods` resolves BindingArgs to pods ({(namespace, name): v1.Pod JSON object})."""
+    `pods` resolves BindingArgs to pods ({(namespace, name): v1.Pod JSON object}).
+
+    device_annotations=True: the context holds the card-name table of that snapshot (as
+    GasCache(device_events=True) installs it) and bind renders the "gas-container-cards" value
+    from it on the device (pas_gas_annotations_render), reading no host copy of the card
+    names; the responses and the stored annotation are the same bytes either way."""
 
     def __init__(self, ctx: Context, gen: int, node_names: Sequence[str],
                  card_names: Sequence[Sequence[str]], kinds: Sequence[str],
-                 pods: Optional[Dict[Tuple[str, str], dict]] = None):
+                 pods: Optional[Dict[Tuple[str, str], dict]] = None,
+                 device_annotations: bool = False):
         self.ctx, self.gen = ctx, gen
+        self.device_annotations = bool(device_annotations)
         self.node_names = list(node_names)
         self.node_index = {n: i for i, n in enumerate(node_names)}
         self.name_table = wire.NameTable(node_names)
@@ -446,11 +453,16 @@ class GASExtender:
         self.gen += 1
         if st[0] != _lib.PAS_GAS_OK:
             return 404, self._error("will not fit")  # errWontFit (:49)
-        from .snapshot import annotation_counts
-        names = self.card_names[node]
-        pod.setdefault("metadata", {}).setdefault("annotations", {})[
-            "gas-container-cards"] = annotation_counts(cnt[0, :, : len(names)], int(ncont[0]),
-                                                       names)
+        if self.device_annotations:  # from the resident card-name table
+            rst, (cards,) = self.ctx.gas_annotations_render([node], ncont[:1], cnt[:1],
+                                                            decode=True)
+            if rst[0] != _lib.PAS_GAS_OK:
+                raise _lib.PasError(_lib.PAS_EINVAL, f"bind annotation: status {int(rst[0])}")
+        else:
+            from .snapshot import annotation_counts
+            names = self.card_names[node]
+            cards = annotation_counts(cnt[0, :, : len(names)], int(ncont[0]), names)
+        pod.setdefault("metadata", {}).setdefault("annotations", {})["gas-container-cards"] = cards
         return 200, wire.binding_result("")
 
     def prioritize(self, body: bytes) -> Tuple[int, bytes]:

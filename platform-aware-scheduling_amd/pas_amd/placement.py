@@ -23,6 +23,8 @@ from collections import namedtuple
 
 import torch
 
+from ._lib import PAS_ECAPACITY, PasError
+
 INT32_MAX = 2**31 - 1
 INT64_MIN, INT64_MAX = -2**63, 2**63 - 1
 
@@ -32,11 +34,21 @@ unplaced), round int32 [P] (0-based round the pod was placed in, -1 = unplaced),
 (pas_gas_place_device's result word, 0 for an unplaced pod), all on the device; n_placed,
 rounds (top-k + place passes run) and gas_gen (the GAS generation after the last pass)."""
 
+AnnotatedPlacement = namedtuple("AnnotatedPlacement",
+                                PlacementResult._fields + ("status", "ann_off", "ann_bytes",
+                                                           "node_off", "node_bytes"))
+AnnotatedPlacement.__doc__ = """place_to_completion(annotate=True)'s result: PlacementResult's
+fields, then what bindNode writes per pod, rendered on the device
+(pas_gas_annotations_render_device, pas_names_render_device): status int32 [P] (PAS_GAS_OK for every pod of a sound placement),
+pod p's "gas-container-cards" value ann_bytes[ann_off[p]:ann_off[p + 1]] and its node's name
+node_bytes[node_off[p]:node_off[p + 1]] (the Binding's target), both empty for an unplaced pod;
+offsets int64 [P + 1], bytes uint8, all on the device."""
+
 
 def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: int, rules_t,
                         rule_off_t, prio_t, cand_t, max_containers: int, i915_index: int, req_t,
                         mask_t, ncont_t, k: int, node_base: int = 0, wide: bool = False,
-                        max_rounds=None, stream=None, pod_policy_t=None) -> PlacementResult:
+                        max_rounds=None, stream=None, pod_policy_t=None, annotate: bool = False):
     """Place a batch until every pod is placed or has provably run out of nodes (the module's
     docstring has the equivalence).  The pod batch tensors are those of
     Context.tas_gas_topk[_wide]_device and Context.gas_place_device; wide selects the wide
@@ -53,7 +65,13 @@ def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: i
     cursor advances by k records per round.  Passing it raises RuntimeError (the passes run so
     far stay committed, the snapshot is at gas_gen + max_rounds).  Errors of the two device
     calls propagate as PasError: a stale generation before anything changed, PAS_EDEVICE from
-    the place call as pas_gas_place_device reports it."""
+    the place call as pas_gas_place_device reports it.
+
+    annotate: every round also takes the selections as counts per container and card, and after
+    the last round one pas_gas_annotations_render_device and one pas_names_render_device call
+    turn the batch into the strings the shim writes (the card-name table and the name table must
+    be resident); the result is an AnnotatedPlacement.  Without it nothing changes: the same
+    device calls, a PlacementResult."""
     stream = torch.cuda.current_stream() if stream is None else stream
     if max_rounds is None:
         max_rounds = -(-ctx.gas_shape[0] // k) + 1
@@ -75,6 +93,12 @@ def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: i
         r_node = torch.empty(p, dtype=torch.int32, device=dev)
         r_rank = torch.empty(p, dtype=torch.int32, device=dev)
         r_res = torch.empty(p, dtype=torch.int32, device=dev)
+        if annotate:
+            shape = (p, max_containers, ctx.gas_shape[1])
+            r_counts = torch.empty(shape, dtype=torch.int64, device=dev)
+            counts = torch.zeros(shape, dtype=torch.int64, device=dev)
+        else:
+            r_counts = None
         gen, rounds, n_placed = gas_gen, 0, 0
         while True:
             if rounds >= max_rounds:
@@ -97,7 +121,7 @@ def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: i
             placed_now, _ = ctx.gas_place_device(gen, gen + 1, p, max_containers, i915_index,
                                                  req_t, mask_t, ncont_t, k, k, node_base,
                                                  top_node, top_len, r_node, r_rank, r_res,
-                                                 stream=stream)
+                                                 counts_t=r_counts, stream=stream)
             gen += 1
             n_placed += placed_now
             if p == 0:
@@ -107,6 +131,8 @@ def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: i
             node = torch.where(placed, r_node, node)
             res = torch.where(placed, r_res, res)
             rnd = torch.where(placed, torch.full_like(rnd, rounds), rnd)
+            if annotate:
+                counts = torch.where(placed[:, None, None], r_counts, counts)
             rounds += 1
             # the next cursors: the end for a placed pod, the row's last record otherwise (the
             # padding record, i.e. the end, when the row was shorter than k)
@@ -118,4 +144,30 @@ def place_to_completion(ctx, tas_gen: int, gas_gen: int, n_pods: int, n_rules: i
             # queued: unplaced with a full row (finished pods come back with an empty row)
             if not bool((~placed & (top_len == k)).any()):
                 break
-        return PlacementResult(node, rnd, res, n_placed, rounds, gen)
+        result = PlacementResult(node, rnd, res, n_placed, rounds, gen)
+        if not annotate:
+            return result
+        # the strings: one render of the annotations and one of the names
+        bind_node = torch.where(node >= 0, node - node_base, torch.full_like(node, -1))
+        status = torch.zeros(max(p, 1), dtype=torch.int32, device=dev)[:p]
+        ann_off = torch.zeros(p + 1, dtype=torch.int64, device=dev)
+        node_off = torch.zeros(p + 1, dtype=torch.int64, device=dev)
+
+        def rendered(call, room):
+            # one call when the guessed room holds the bytes, else a second with the exact room
+            out = torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
+            try:
+                total = call(out, room)
+            except PasError as e:
+                if e.code != PAS_ECAPACITY:
+                    raise
+                total = e.n_bytes
+                out = torch.empty(total, dtype=torch.uint8, device=dev)
+                call(out, total)
+            return out[:total]
+        ann_bytes = rendered(lambda out, cap: ctx.gas_annotations_render_device(
+            p, bind_node, ncont_t, max_containers, counts, status, ann_off, out, cap,
+            stream=stream), 32 * p * max(max_containers, 1))
+        node_bytes = rendered(lambda out, cap: ctx.names_render_device(
+            p, node, node_base, node_off, out, cap, stream=stream), 64 * p)
+        return AnnotatedPlacement(*result, status, ann_off, ann_bytes, node_off, node_bytes)
