@@ -105,7 +105,7 @@ int pas_gas_card_names_set(pas_ctx* ctx, int32_t n_slots, int32_t k, const int64
   if (n_slots < 0 || k < 1 || k > PAS_GAS_MAX_CARDS)
     return set_error(ctx, PAS_EINVAL, fn + ": n_slots < 0 or k outside [1, PAS_GAS_MAX_CARDS]");
   const int64_t entries = (int64_t)n_slots * k;
-  int rc = check_csr(ctx, entries, name_off, bytes, fn);
+  int rc = check_host_spans(ctx, entries, name_off, bytes, fn);
   if (rc) return rc;
   if ((rc = activate(ctx))) return rc;
   hipStream_t s = ctx->stream;
@@ -147,7 +147,7 @@ int pas_gas_card_names_update(pas_ctx* ctx, int32_t n_rows, const int32_t* row_s
   if (n_rows == 0) return PAS_OK;
   if (!row_slot) return set_error(ctx, PAS_EINVAL, fn + ": null input");
   const int64_t entries = (int64_t)n_rows * t.k;
-  int rc = check_csr(ctx, entries, name_off, bytes, fn);
+  int rc = check_host_spans(ctx, entries, name_off, bytes, fn);
   if (rc) return rc;
   for (int32_t r = 0; r < n_rows; ++r)
     if (row_slot[r] < 0 || row_slot[r] >= t.n_slots)

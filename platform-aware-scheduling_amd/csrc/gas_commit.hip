@@ -104,37 +104,36 @@ int walk_launch(pas_ctx* ctx, int32_t n_ops, const uint32_t* d_key, const int32_
 }  // namespace
 
 int gas_apply_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
-                     const int32_t* d_pod, const int32_t* d_node, int32_t n_pods,
-                     int32_t max_containers, const int64_t* d_req, const uint32_t* d_mask,
-                     const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
-                     int32_t cards_ld, int32_t* d_status, hipStream_t s) {
+                     const int32_t* d_pod, const int32_t* d_node, const PodBatch& pods,
+                     const int32_t* d_cpc, const int32_t* d_cards, int32_t cards_ld,
+                     int32_t* d_status, hipStream_t s) {
   if (n_events == 0) return PAS_OK;
+  const int32_t n_pods = pods.n_pods;
   NodeRuns runs(ctx, n_events, d_node, [=] __device__(int32_t e) {
     const int32_t k = d_kind[e], p = d_pod[e];
     return (k == PAS_GAS_EV_ADD || k == PAS_GAS_EV_REMOVE) && p >= 0 && p < n_pods;
   }, s);
   if (runs.rc) return runs.rc;
   BindArgs a{};
-  a.C = max_containers, a.i915 = -1;
+  a.C = pods.max_containers, a.i915 = -1;
   a.order = runs.order, a.op_pod = d_pod;
-  a.req = d_req, a.mask = d_mask, a.ncont = d_ncont;
+  a.req = pods.req, a.mask = pods.mask, a.ncont = pods.n_containers;
   a.cpc = d_cpc, a.cards = d_cards, a.cards_stride = cards_ld;
   a.status = d_status;
   return walk_launch<Op::kEvents>(ctx, n_events, runs.key, d_kind, a, s);
 }
 
-int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_ops, int32_t max_containers,
-                      int32_t i915_index, const int32_t* d_order, const uint32_t* d_key,
-                      const int32_t* d_pod, const int64_t* d_req, const uint32_t* d_mask,
-                      const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
+int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_ops, int32_t i915_index,
+                      const int32_t* d_order, const uint32_t* d_key, const int32_t* d_pod,
+                      const PodBatch& pods, const int32_t* d_cpc, const int32_t* d_cards,
                       int32_t cards_stride, uint32_t* d_res, int32_t* d_status,
                       uint8_t* d_cards_out, int32_t* d_nsel_out, int64_t* d_counts_out,
                       const int64_t* d_counts, hipStream_t s) {
   if (n_ops == 0) return PAS_OK;
   BindArgs a{};
-  a.C = max_containers, a.i915 = i915_index;
+  a.C = pods.max_containers, a.i915 = i915_index;
   a.order = d_order, a.op_pod = d_pod;
-  a.req = d_req, a.mask = d_mask, a.ncont = d_ncont;
+  a.req = pods.req, a.mask = pods.mask, a.ncont = pods.n_containers;
   a.cpc = d_cpc, a.cards = d_cards, a.cards_stride = cards_stride;
   a.res_out = d_res, a.status = d_status, a.cards_out = d_cards_out, a.nsel_out = d_nsel_out;
   a.counts_out = d_counts_out, a.counts = d_counts;

@@ -2398,11 +2398,13 @@ int gas_fault_check(pas_ctx* ctx) {
                    "are incomplete (set PAS_GAS_SYNC=events under kernel-serializing tools)");
 }
 
-int gas_fit_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t i915_index,
-                   const int64_t* d_req, const uint32_t* d_req_mask,
-                   const int32_t* d_n_containers, uint32_t* d_res, int64_t ld_res, uint64_t* d_fit,
-                   pas_gas_selection* d_side, int64_t side_cap, int64_t* d_side_count,
-                   hipStream_t s) {
+int gas_fit_launch(pas_ctx* ctx, int32_t i915_index, const PodBatch& pods, uint32_t* d_res,
+                   int64_t ld_res, uint64_t* d_fit, pas_gas_selection* d_side, int64_t side_cap,
+                   int64_t* d_side_count, hipStream_t s) {
+  const int32_t n_pods = pods.n_pods, max_containers = pods.max_containers;
+  const int64_t* d_req = pods.req;
+  const uint32_t* d_req_mask = pods.mask;
+  const int32_t* d_n_containers = pods.n_containers;
   const GasSnapshot& g = ctx->gas;
   const int32_t N = g.n_nodes, Q = g.n_res, K = g.max_cards;
   constexpr int32_t kCounts = (1 + kClasses) * (PAS_GAS_MAX_RES + 1) + 1;  // lists + generic pods

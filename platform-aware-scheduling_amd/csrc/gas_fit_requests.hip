@@ -58,10 +58,8 @@ __global__ __launch_bounds__(kTpb) void gas_fit_requests_kernel(
 }  // namespace
 
 int gas_fit_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
-                            const int32_t* d_req_node, int32_t max_containers,
-                            int32_t i915_index, const int64_t* d_req, const uint32_t* d_mask,
-                            const int32_t* d_ncont, uint64_t* d_fit, int64_t ld_words,
-                            HostStage* stage, hipStream_t s) {
+                            const int32_t* d_req_node, int32_t i915_index, const PodBatch& pods,
+                            uint64_t* d_fit, int64_t ld_words, HostStage* stage, hipStream_t s) {
   const int32_t longest = request_longest(n_requests, req_off);
   if (longest == 0) return PAS_OK;  // no row has a word
   const GasSnapshot& g = ctx->gas;
@@ -72,9 +70,9 @@ int gas_fit_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req
   int32_t* d_off = static_cast<int32_t*>(sc.slot->p);
   if ((rc = upload_host(ctx, d_off, req_off, b_off, !stage, s))) return rc;
   BindArgs a{};
-  a.K = g.max_cards, a.Q = g.n_res, a.C = max_containers, a.i915 = i915_index;
+  a.K = g.max_cards, a.Q = g.n_res, a.C = pods.max_containers, a.i915 = i915_index;
   a.n_cards = g.n_cards, a.cap = g.cap, a.used = g.used;
-  a.req = d_req, a.mask = d_mask, a.ncont = d_ncont;
+  a.req = pods.req, a.mask = pods.mask, a.ncont = pods.n_containers;
   const dim3 grid((unsigned)n_requests, request_chunks(longest, kTpb));
   card_tier(g.max_cards, [&](auto km) {
     gas_fit_requests_kernel<decltype(km)::value><<<grid, kTpb, 0, s>>>(g.n_nodes, d_off,

@@ -45,7 +45,7 @@
 #include <string>
 #include <vector>
 
-#include "csr_entry.h"
+#include "card_rows.h"
 #include "gas_group.h"
 #include "host_staging.h"
 #include "label_fixed.h"
@@ -57,38 +57,16 @@ namespace pas {
 namespace {
 
 constexpr int kTpb = 256;
-constexpr int32_t kPending = PAS_GAS_ANN_PENDING;  // (-1: no status has that value)
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTpb - 1) / kTpb); }
 
-__device__ __forceinline__ int32_t sat32(int64_t v) {
-  return v > INT32_MAX ? INT32_MAX : (int32_t)v;
-}
+constexpr int32_t kPending = PAS_GAS_ANN_PENDING;  // (-1: no status has that value)
 
-// the wave's largest v into *dst (one lane issues the atomic)
-__device__ __forceinline__ void wave_max(int32_t v, int32_t* dst) {
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  if ((threadIdx.x & 63) == 0 && v > *(volatile int32_t*)dst) atomicMax(dst, v);
-}
-
-struct CardView {
-  int32_t k;
-  const int64_t* beg;
-  const int64_t* len;
-  const char* pool;
-};
-
-struct Blob {
-  int64_t n_bytes;
-  const int64_t* off;
-  const char* bytes;
-};
-
-// Rules 1-4 of pas_gas_nodes_update_strings for update u.  name_off non-null: node[u] is the
+// Rules 1-4 of pas_gas_nodes_update_strings for update u.  names.off non-null: node[u] is the
 // slot the name table gave the update's node name (-1 without one).
 __global__ __launch_bounds__(kTpb) void node_strings_parse(
-    int32_t U, int32_t N, int32_t Q, const int32_t* __restrict__ node, int64_t n_name_bytes,
-    const int64_t* __restrict__ name_off, const int32_t* __restrict__ state, Blob label, Blob lit,
+    int32_t U, int32_t N, int32_t Q, const int32_t* __restrict__ node, ByteSpans names,
+    const int32_t* __restrict__ state, ByteSpans label, ByteSpans lit,
     int32_t* __restrict__ verdict, int32_t* __restrict__ n_cards, int32_t* __restrict__ gpu_count,
     int64_t* __restrict__ cap, int32_t* most) {
   const int32_t u = blockIdx.x * kTpb + threadIdx.x;
@@ -99,9 +77,9 @@ __global__ __launch_bounds__(kTpb) void node_strings_parse(
     int32_t v = kPending, nc = 0, gpus = 0;
     if (st != PAS_GAS_NODE_GONE && st != PAS_GAS_NODE_NO_LABEL && st != PAS_GAS_NODE_LABEL) {
       v = PAS_GAS_ERR_INPUT;
-    } else if (name_off) {
+    } else if (names.off) {
       int64_t nb;
-      if (entry_span(name_off, n_name_bytes, u, &nb) == 0)
+      if (names.span(u, &nb) == 0)
         v = PAS_GAS_ERR_INPUT;
       else if (!held)  // a node the snapshot never held leaves without a trace
         v = st == PAS_GAS_NODE_GONE ? PAS_GAS_OK : PAS_GAS_ERR_INPUT;
@@ -113,13 +91,13 @@ __global__ __launch_bounds__(kTpb) void node_strings_parse(
     if (st == PAS_GAS_NODE_GONE && v != PAS_GAS_ERR_INPUT) nc = -1;
     if (v == kPending && st == PAS_GAS_NODE_LABEL) {
       int64_t b;
-      const int64_t len = entry_span(label.off, label.n_bytes, u, &b);
+      const int64_t len = label.span(u, &b);
       const int64_t pieces = label_pieces(label.bytes + b, len);
       gpus = sat32(pieces);
       nc = label_count(label.bytes + b, len, PAS_GAS_MAX_CARDS + 1);
       for (int32_t q = 0; q < Q; ++q) {
         int64_t lb;
-        const int64_t ll = entry_span(lit.off, lit.n_bytes, (int64_t)u * Q + q, &lb);
+        const int64_t ll = lit.span((int64_t)u * Q + q, &lb);
         if (ll == 0) continue;  // a resource the node does not have
         const QuantityFixed r = parse_quantity_fixed(lit.bytes + lb, ll);
         if (r.status == PAS_EINVAL) v = PAS_GAS_ERR_INPUT;
@@ -162,19 +140,6 @@ __global__ __launch_bounds__(kTpb) void node_strings_rounds(int32_t U, int32_t N
   wave_max(mine, longest);
 }
 
-// The lowest slot of the row whose name is p[0 .. n), else -1
-__device__ __forceinline__ int32_t slot_of(const CardView& t, int64_t row, const char* __restrict__ p,
-                                           int64_t n) {
-  for (int32_t r = 0; r < t.k; ++r) {
-    if (t.len[row + r] != n) continue;
-    const char* q = t.pool + t.beg[row + r];
-    int64_t i = 0;
-    while (i < n && q[i] == p[i]) ++i;
-    if (i == n) return r;
-  }
-  return -1;
-}
-
 // Rule 5 for the pending updates at run position r (r < 0: every pending update, the resolve
 // form): the slot map src [U][K], the parked cards lost, the new row's bytes (-1: the update
 // writes no names: its row stays) and the node handed to the walker (N: not this round).
@@ -183,7 +148,7 @@ __global__ __launch_bounds__(kTpb) void node_strings_resolve(
     int32_t U, int32_t N, int32_t r, const int32_t* __restrict__ node,
     const int32_t* __restrict__ verdict, const int32_t* __restrict__ round,
     const int32_t* __restrict__ n_cards, const int32_t* __restrict__ n_cards_res, CardView t,
-    Blob label, int32_t* __restrict__ src, int32_t* __restrict__ n_dropped,
+    ByteSpans label, int32_t* __restrict__ src, int32_t* __restrict__ n_dropped,
     int64_t* __restrict__ row_bytes, int64_t* __restrict__ scan_in,
     int32_t* __restrict__ walker_node) {
   const int32_t u = blockIdx.x * kTpb + threadIdx.x;
@@ -219,12 +184,12 @@ __global__ __launch_bounds__(kTpb) void node_strings_resolve(
   const int64_t row = (int64_t)n * K;
   const int32_t l_old = max(0, min(n_cards_res[n], K));
   int64_t lb;
-  const int64_t ll = entry_span(label.off, label.n_bytes, u, &lb);
+  const int64_t ll = label.span(u, &lb);
   const char* p = label.bytes + lb;
   int64_t bytes = 0, b = 0, l = 0;
   for (int32_t i = 0; i < nc; ++i) {  // the label cards in rank order
     label_next(p, ll, i > 0, b, l, &b, &l);
-    src_u[i] = slot_of(t, row, p + b, l);
+    src_u[i] = row_find(t, row, t.k, p + b, l);
     bytes += l;
   }
   int32_t at = nc, dropped = 0;
@@ -251,13 +216,14 @@ __global__ __launch_bounds__(kTpb) void node_strings_names(
     int32_t U, const int32_t* __restrict__ node, const int32_t* __restrict__ n_cards,
     const int64_t* __restrict__ row_bytes, const int64_t* __restrict__ row_off,
     const int32_t* __restrict__ src, CardView t, char* __restrict__ pool, int64_t base,
-    int64_t pool_cap, Blob label, int64_t* __restrict__ new_beg, int64_t* __restrict__ new_len) {
+    int64_t pool_cap, ByteSpans label, int64_t* __restrict__ new_beg,
+    int64_t* __restrict__ new_len) {
   const int32_t u = blockIdx.x * kTpb + threadIdx.x;
   if (u >= U || row_bytes[u] < 0) return;
   const int32_t K = t.k, nc = n_cards[u];
   const int64_t row = (int64_t)node[u] * K;
   int64_t lb;
-  const int64_t ll = entry_span(label.off, label.n_bytes, u, &lb);
+  const int64_t ll = label.span(u, &lb);
   const char* p = label.bytes + lb;
   int64_t cur = base + row_off[u], b = 0, l = 0;
   int64_t* nb = new_beg + (int64_t)u * K;
@@ -304,17 +270,13 @@ __global__ __launch_bounds__(kTpb) void node_strings_status(int32_t U,
   if (u < U) status[u] = verdict[u] == kPending ? PAS_GAS_OK : verdict[u];
 }
 
-CardView view_of(const GasCardNames& t) { return CardView{t.k, t.sp.beg, t.sp.len, t.sp.pool}; }
-
 // the call's arrays on the device
 struct NodeStrings {
   int32_t U;
   const int32_t* node;  // null: the nodes by name
-  int64_t n_name_bytes;
-  const int64_t* name_off;
-  const char* name_bytes;
+  ByteSpans names;
   const int32_t* state;
-  Blob label, lit;
+  ByteSpans label, lit;
   int32_t *status, *n_cards, *gpu_count;  // outputs: any but status may be null
   int64_t* cap;
   int32_t *src, *n_dropped;
@@ -365,19 +327,18 @@ int stage_parse(pas_ctx* ctx, AuxSlot* slot, const NodeStrings& a, bool update, 
   w->new_beg = cv.take<int64_t>(uk);
   w->new_len = cv.take<int64_t>(uk);
   w->scan_tmp = cv.take<char>(w->scan_bytes);
-  const int64_t* name_off = nullptr;
+  ByteSpans names{};
   *d_node = a.node;
   if (!a.node) {  // the nodes by name: lookup only, into the slot's buffer
-    rc = names_resolve_launch(ctx, a.U, a.n_name_bytes, a.name_off, a.name_bytes, w->slot, nullptr,
-                              nullptr, false, s);
+    rc = names_resolve_launch(ctx, a.U, a.names, w->slot, nullptr, nullptr, false, s);
     if (rc) return rc;
     *d_node = w->slot;
-    name_off = a.name_off;
+    names = a.names;
   }
   PAS_HIP(ctx, hipMemsetAsync(w->scal, 0, 16, s));
   node_strings_parse<<<blocks_for(a.U), kTpb, 0, s>>>(
-      a.U, g.n_nodes, g.n_res, *d_node, a.n_name_bytes, name_off, a.state, a.label, a.lit,
-      w->verdict, w->n_cards, w->gpu_count, w->cap, w->scal);
+      a.U, g.n_nodes, g.n_res, *d_node, names, a.state, a.label, a.lit, w->verdict, w->n_cards,
+      w->gpu_count, w->cap, w->scal);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
 }
@@ -511,43 +472,21 @@ int strings_check(pas_ctx* ctx, bool by_name, const uint64_t* gen_from, int32_t 
   return PAS_OK;
 }
 
-int blob_check(pas_ctx* ctx, int64_t n_bytes, const void* bytes, const std::string& fn) {
-  if (n_bytes < 0 || (n_bytes > 0 && !bytes))
-    return set_error(ctx, PAS_EINVAL, fn + ": null bytes or a byte count < 0");
-  return PAS_OK;
-}
-
-// A failed update past its first write leaves the snapshot and the table of unknown content
-int update_finish(pas_ctx* ctx, int rc, bool began, uint64_t gen_to) {
-  if (rc) {
-    if (began) ctx->gas.valid = ctx->gas_cards.valid = false;
-    return rc;
-  }
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
-}
-
 int update_device(pas_ctx* ctx, bool by_name, uint64_t gen_from, uint64_t gen_to, NodeStrings a,
                   int32_t* need_cards, void* hip_stream, const std::string& fn) {
   if (!ctx) return PAS_EINVAL;
-  int rc = strings_check(ctx, by_name, &gen_from, a.U, a.node, a.name_off, a.state, a.label.off,
+  int rc = strings_check(ctx, by_name, &gen_from, a.U, a.node, a.names.off, a.state, a.label.off,
                          a.lit.off, a.status, fn);
   if (rc) return rc;
-  if (a.U > 0 && ((rc = blob_check(ctx, a.label.n_bytes, a.label.bytes, fn)) ||
-                  (rc = blob_check(ctx, a.lit.n_bytes, a.lit.bytes, fn)) ||
-                  (by_name && (rc = blob_check(ctx, a.n_name_bytes, a.name_bytes, fn)))))
+  if (a.U > 0 && ((rc = check_device_spans(ctx, a.U, a.label, fn + ": label_off")) ||
+                  (rc = check_device_spans(ctx, a.U, a.lit, fn + ": cap_off")) ||
+                  (by_name &&
+                   (rc = check_device_spans(ctx, a.U, a.names, fn + ": node_name_off")))))
     return rc;
   if ((rc = activate(ctx))) return rc;
   bool began = false;
   rc = update_launch(ctx, a, need_cards, &began, pick_stream(ctx, hip_stream), fn);
-  return update_finish(ctx, rc, began, gen_to);
-}
-
-// offsets [n + 1] of a host form's byte spans: from 0, non-decreasing, bytes when any
-int spans_check(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
-                const std::string& what) {
-  return check_csr(ctx, n, off, bytes, what);
+  return gas_finish(ctx, rc, began, gen_to, true);
 }
 
 struct HostArgs {
@@ -573,13 +512,13 @@ int strings_host(pas_ctx* ctx, bool by_name, bool update, uint64_t gen_from, uin
                          h.name_off, h.state, h.label_off, h.cap_off, h.status, fn);
   if (rc) return rc;
   if (need_cards) *need_cards = 0;
-  if (h.n_updates == 0) return update ? update_finish(ctx, PAS_OK, false, gen_to) : PAS_OK;
+  if (h.n_updates == 0) return update ? gas_finish(ctx, PAS_OK, false, gen_to, true) : PAS_OK;
   const GasSnapshot& g = ctx->gas;
   const size_t U = (size_t)h.n_updates, K = (size_t)g.max_cards, Q = (size_t)g.n_res;
-  if ((rc = spans_check(ctx, h.n_updates, h.label_off, h.label_bytes, fn + ": label_off")) ||
-      (rc = spans_check(ctx, (int64_t)(U * Q), h.cap_off, h.cap_bytes, fn + ": cap_off")) ||
-      (by_name &&
-       (rc = spans_check(ctx, h.n_updates, h.name_off, h.name_bytes, fn + ": node_name_off"))))
+  if ((rc = check_host_spans(ctx, h.n_updates, h.label_off, h.label_bytes, fn + ": label_off")) ||
+      (rc = check_host_spans(ctx, (int64_t)(U * Q), h.cap_off, h.cap_bytes, fn + ": cap_off")) ||
+      (by_name && (rc = check_host_spans(ctx, h.n_updates, h.name_off, h.name_bytes,
+                                         fn + ": node_name_off"))))
     return rc;
   for (size_t u = 0; u < U; ++u) {
     if (!by_name && (h.node[u] < 0 || h.node[u] >= g.n_nodes))
@@ -591,20 +530,13 @@ int strings_host(pas_ctx* ctx, bool by_name, bool update, uint64_t gen_from, uin
   Staging st(ctx);
   NodeStrings a{};
   a.U = h.n_updates;
-  int32_t *d_node = nullptr, *d_state;
-  int64_t *d_name_off = nullptr, *d_label_off, *d_cap_off;
-  char *d_name_bytes = nullptr, *d_label_bytes, *d_cap_bytes;
-  if (by_name) {
-    st.in(d_name_off, h.name_off, U + 1);
-    st.in(d_name_bytes, h.name_bytes, (size_t)h.name_off[U]);
-  } else {
-    st.in(d_node, h.node, U);
-  }
-  st.in(d_state, h.state, U);
-  st.in(d_label_off, h.label_off, U + 1);
-  st.in(d_label_bytes, h.label_bytes, (size_t)h.label_off[U]);
-  st.in(d_cap_off, h.cap_off, U * Q + 1);
-  st.in(d_cap_bytes, h.cap_bytes, (size_t)h.cap_off[U * Q]);
+  if (by_name)
+    st.in_spans(a.names, h.n_updates, h.name_off, h.name_bytes);
+  else
+    st.in(a.node, h.node, U);
+  st.in(a.state, h.state, U);
+  st.in_spans(a.label, h.n_updates, h.label_off, h.label_bytes);
+  st.in_spans(a.lit, (int64_t)(U * Q), h.cap_off, h.cap_bytes);
   st.out(a.status, h.status, U);
   st.out_opt(a.n_cards, h.n_cards, U);
   st.out_opt(a.gpu_count, h.gpu_count, U);
@@ -612,13 +544,6 @@ int strings_host(pas_ctx* ctx, bool by_name, bool update, uint64_t gen_from, uin
   st.out_opt(a.src, h.src, U * K);
   st.out_opt(a.n_dropped, h.n_dropped, U);
   if ((rc = st.upload())) return rc;
-  a.node = d_node;
-  a.n_name_bytes = by_name ? h.name_off[U] : 0;
-  a.name_off = d_name_off;
-  a.name_bytes = d_name_bytes;
-  a.state = d_state;
-  a.label = Blob{h.label_off[U], d_label_off, d_label_bytes};
-  a.lit = Blob{h.cap_off[U * Q], d_cap_off, d_cap_bytes};
   if (!update) {
     if ((rc = resolve_launch(ctx, a, ctx->stream))) return rc;
     PAS_HIP(ctx, st.fetch());
@@ -630,7 +555,7 @@ int strings_host(pas_ctx* ctx, bool by_name, bool update, uint64_t gen_from, uin
     began = true;
     rc = set_error(ctx, PAS_EDEVICE, fn + ": copy of the results");
   }
-  return update_finish(ctx, rc, began, gen_to);
+  return gas_finish(ctx, rc, began, gen_to, true);
 }
 
 }  // namespace
@@ -687,10 +612,10 @@ int pas_gas_nodes_update_strings_device(
     const int64_t* d_cap_off, const char* d_cap_bytes, int32_t* d_status_out,
     int32_t* d_n_cards_out, int64_t* d_cap_out, int32_t* d_n_dropped_out, int32_t* need_cards,
     void* hip_stream) {
-  NodeStrings a{n_updates, d_upd_node, 0, nullptr, nullptr, d_upd_state,
-                Blob{n_label_bytes, d_label_off, d_label_bytes},
-                Blob{n_cap_bytes, d_cap_off, d_cap_bytes}, d_status_out, d_n_cards_out, nullptr,
-                d_cap_out, nullptr, d_n_dropped_out};
+  NodeStrings a{n_updates, d_upd_node, ByteSpans{}, d_upd_state,
+                ByteSpans{n_label_bytes, d_label_off, d_label_bytes},
+                ByteSpans{n_cap_bytes, d_cap_off, d_cap_bytes}, d_status_out, d_n_cards_out,
+                nullptr, d_cap_out, nullptr, d_n_dropped_out};
   return update_device(ctx, false, gen_from, gen_to, a, need_cards, hip_stream,
                        "pas_gas_nodes_update_strings_device");
 }
@@ -702,10 +627,10 @@ int pas_gas_nodes_update_strings_names_device(
     int64_t n_cap_bytes, const int64_t* d_cap_off, const char* d_cap_bytes,
     int32_t* d_status_out, int32_t* d_n_cards_out, int64_t* d_cap_out, int32_t* d_n_dropped_out,
     int32_t* need_cards, void* hip_stream) {
-  NodeStrings a{n_updates, nullptr, n_name_bytes, d_node_name_off, d_node_name_bytes, d_upd_state,
-                Blob{n_label_bytes, d_label_off, d_label_bytes},
-                Blob{n_cap_bytes, d_cap_off, d_cap_bytes}, d_status_out, d_n_cards_out, nullptr,
-                d_cap_out, nullptr, d_n_dropped_out};
+  NodeStrings a{n_updates, nullptr, ByteSpans{n_name_bytes, d_node_name_off, d_node_name_bytes},
+                d_upd_state, ByteSpans{n_label_bytes, d_label_off, d_label_bytes},
+                ByteSpans{n_cap_bytes, d_cap_off, d_cap_bytes}, d_status_out, d_n_cards_out,
+                nullptr, d_cap_out, nullptr, d_n_dropped_out};
   return update_device(ctx, true, gen_from, gen_to, a, need_cards, hip_stream,
                        "pas_gas_nodes_update_strings_names_device");
 }
@@ -718,15 +643,15 @@ int pas_gas_nodes_resolve_strings_device(
     int32_t* d_src_out, int32_t* d_n_dropped_out, void* hip_stream) {
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_gas_nodes_resolve_strings_device";
-  NodeStrings a{n_updates, d_upd_node, 0, nullptr, nullptr, d_upd_state,
-                Blob{n_label_bytes, d_label_off, d_label_bytes},
-                Blob{n_cap_bytes, d_cap_off, d_cap_bytes}, d_status_out, d_n_cards_out,
+  NodeStrings a{n_updates, d_upd_node, ByteSpans{}, d_upd_state,
+                ByteSpans{n_label_bytes, d_label_off, d_label_bytes},
+                ByteSpans{n_cap_bytes, d_cap_off, d_cap_bytes}, d_status_out, d_n_cards_out,
                 d_gpu_count_out, d_cap_out, d_src_out, d_n_dropped_out};
   int rc = strings_check(ctx, false, nullptr, n_updates, d_upd_node, nullptr, d_upd_state,
                          d_label_off, d_cap_off, d_status_out, fn);
   if (rc) return rc;
-  if (n_updates > 0 && ((rc = blob_check(ctx, n_label_bytes, d_label_bytes, fn)) ||
-                        (rc = blob_check(ctx, n_cap_bytes, d_cap_bytes, fn))))
+  if (n_updates > 0 && ((rc = check_device_spans(ctx, n_updates, a.label, fn + ": label_off")) ||
+                        (rc = check_device_spans(ctx, n_updates, a.lit, fn + ": cap_off"))))
     return rc;
   if ((rc = activate(ctx))) return rc;
   return resolve_launch(ctx, a, pick_stream(ctx, hip_stream));

@@ -213,9 +213,8 @@ __global__ __launch_bounds__(kTpb) void place_commit_kernel(PlaceArgs a, BindArg
 
 }  // namespace
 
-int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t i915_index,
-                     const int64_t* d_req, const uint32_t* d_mask, const int32_t* d_ncont,
-                     int32_t k, int32_t ld, int32_t node_base, const int32_t* d_cand,
+int gas_place_launch(pas_ctx* ctx, int32_t i915_index, const PodBatch& pods, int32_t k,
+                     int32_t ld, int32_t node_base, const int32_t* d_cand,
                      const int32_t* d_cand_len, int32_t* d_place_node, int32_t* d_place_rank,
                      uint32_t* d_res, uint8_t* d_cards_out, int32_t* d_nsel_out,
                      int64_t* d_counts_out, int32_t* n_placed, int32_t* n_rounds,
@@ -223,6 +222,7 @@ int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32
   *began = false;
   if (n_placed) *n_placed = 0;
   if (n_rounds) *n_rounds = 0;
+  const int32_t n_pods = pods.n_pods;
   if (n_pods == 0) return PAS_OK;
   GasSnapshot& g = ctx->gas;
   const size_t P = (size_t)n_pods, N = (size_t)std::max(g.n_nodes, 1);
@@ -249,7 +249,7 @@ int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32
   unsigned long long* d_blocker = cv.take<unsigned long long>(N);
   void* d_sort_tmp = cv.take<char>(sort_bytes);
 
-  const int32_t K = g.max_cards, C = max_containers;
+  const int32_t K = g.max_cards, C = pods.max_containers;
   PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(PlaceCtr), s));
   PAS_HIP(ctx, hipMemsetAsync(d_blocker, 0, 8 * N, s));
   if (d_cards_out) PAS_HIP(ctx, hipMemsetAsync(d_cards_out, 0, P * PAS_GAS_MAX_SELECTIONS, s));
@@ -262,7 +262,7 @@ int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32
   BindArgs b{};
   b.K = K, b.Q = g.n_res, b.C = C, b.i915 = i915_index;
   b.n_cards = g.n_cards, b.cap = g.cap, b.used = g.used;
-  b.req = d_req, b.mask = d_mask, b.ncont = d_ncont;
+  b.req = pods.req, b.mask = pods.mask, b.ncont = pods.n_containers;
   b.res_out = d_res, b.cards_out = d_cards_out, b.nsel_out = d_nsel_out;
   b.counts_out = C > 0 ? d_counts_out : nullptr;
   const unsigned pod_blocks = (unsigned)((P + kPodTpb - 1) / kPodTpb);

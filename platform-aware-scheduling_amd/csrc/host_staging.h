@@ -1,5 +1,7 @@
-// host_staging.h — the arrays of one host-pointer entry point in the context's scratch
-// (pas_api.hip only; the _device forms and the _launch functions stage nothing).
+// host_staging.h — the arrays of one host-pointer entry point in the context's scratch (every
+// file with host forms: pas_api.hip, tas_ingest.hip, name_table.hip, span_pool.hip,
+// gas_cards.hip, gas_annotations.hip, gas_node_strings.hip, gas_render.hip; the _device forms
+// and the _launch functions stage nothing).
 #pragma once
 
 #include <algorithm>
@@ -26,12 +28,23 @@ class Staging {
   void in(T*& d, const T* host, size_t count) { add(&d, host, count, kIn, false); }
   template <typename T>
   void in_opt(T*& d, const T* host, size_t count) { add(&d, host, count, kIn, true); }
+  template <typename T>  // (a record's read-only field)
+  void in(const T*& d, const T* host, size_t count) {
+    add(const_cast<T**>(&d), host, count, kIn, false);
+  }
   template <typename T>
   void out(T*& d, T* host, size_t count) { add(&d, host, count, kOut, false); }
   template <typename T>
   void out_opt(T*& d, T* host, size_t count) { add(&d, host, count, kOut, true); }
   template <typename T>
   void work(T*& d, size_t count) { add(&d, static_cast<const T*>(nullptr), count, kWork, false); }
+  // The n byte spans of a host form (checked: check_host_spans), two arrays: d gets the byte
+  // total now and the device pointers at upload().  n == 0 states both arrays empty.
+  void in_spans(ByteSpans& d, int64_t n, const int64_t* off, const char* bytes) {
+    d.n_bytes = n > 0 ? off[n] : 0;
+    in(d.off, off, n > 0 ? (size_t)n + 1 : 0);
+    in(d.bytes, bytes, (size_t)d.n_bytes);
+  }
 
   int upload() {
     size_t total = 0;
@@ -59,6 +72,11 @@ class Staging {
     const hipError_t es = hipStreamSynchronize(ctx_->stream);
     return e != hipSuccess ? e : es;
   }
+  // fetch() as a status, for the forms whose results are the last thing that can fail
+  int fetch_results(const std::string& fn) {
+    const hipError_t e = fetch();
+    return e == hipSuccess ? PAS_OK : check_hip(ctx_, e, (fn + ": copy of the results").c_str());
+  }
 
  private:
   enum Role { kIn, kOut, kWork };
@@ -82,5 +100,18 @@ class Staging {
   Buf buf_[kMax];
   int n_ = 0;
 };
+
+// The pod batch of a GAS host form stated to st (three arrays): req [P][C][Q], req_mask [P][C]
+// and n_containers [P].
+inline void stage_pods(Staging& st, PodBatch& d, int32_t n_pods, int32_t max_containers,
+                       const int64_t* req, const uint32_t* req_mask,
+                       const int32_t* n_containers) {
+  const size_t P = (size_t)n_pods, C = (size_t)max_containers;
+  d.n_pods = n_pods;
+  d.max_containers = max_containers;
+  st.in(d.req, req, P * C * (size_t)st.ctx()->gas.n_res);
+  st.in(d.mask, req_mask, P * C);
+  st.in(d.n_containers, n_containers, P);
+}
 
 }  // namespace pas

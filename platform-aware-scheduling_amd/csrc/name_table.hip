@@ -265,11 +265,13 @@ int rebuild_table(pas_ctx* ctx, NameTable& t, int64_t buckets, hipStream_t s) {
 }
 
 // pas_names_assign[_device] on device arrays (d_slot may be null), synchronous on s.
-int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
-                        const char* d_bytes, int32_t* d_slot, int64_t new_cap,
-                        int32_t* new_entry_out, int32_t* new_slot_out, int64_t* n_new_out,
-                        hipStream_t s) {
+int names_assign_launch(pas_ctx* ctx, int64_t n, ByteSpans names, int32_t* d_slot,
+                        int64_t new_cap, int32_t* new_entry_out, int32_t* new_slot_out,
+                        int64_t* n_new_out, hipStream_t s) {
   NameTable& t = ctx->names;
+  const int64_t n_bytes = names.n_bytes;
+  const int64_t* d_off = names.off;
+  const char* d_bytes = names.bytes;
   if (n_new_out) *n_new_out = 0;
   if (n == 0) return PAS_OK;
   const size_t nn = (size_t)n, ns = (size_t)t.n_slots;
@@ -311,7 +313,7 @@ int names_assign_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t*
 
   // (a) the lookups; one word back: the entries that name a new node
   PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(uint32_t) * 4, s));
-  rc = names_resolve_launch(ctx, n, n_bytes, d_off, d_bytes, d_slot, d_hash, d_ctr, false, s);
+  rc = names_resolve_launch(ctx, n, names, d_slot, d_hash, d_ctr, false, s);
   if (rc) return rc;
   uint32_t n_unknown = 0;
   PAS_HIP(ctx, hipMemcpyAsync(&n_unknown, d_ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -378,14 +380,14 @@ void free_names(NameTable& t) {
   t = NameTable{};
 }
 
-int names_resolve_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
-                         const char* d_bytes, int32_t* d_slot, uint64_t* d_hash,
-                         uint32_t* d_unknown, bool count_empty, hipStream_t s) {
+int names_resolve_launch(pas_ctx* ctx, int64_t n, ByteSpans names, int32_t* d_slot,
+                         uint64_t* d_hash, uint32_t* d_unknown, bool count_empty, hipStream_t s) {
   if (n <= 0) return PAS_OK;
   int rc = derived_wait(ctx, ctx->names_sync, s);
   if (rc) return rc;
-  names_lookup<<<blocks_for(n), kTpb, 0, s>>>(n, n_bytes, d_off, d_bytes, view_of(ctx->names),
-                                              d_slot, d_hash, d_unknown, count_empty ? 1 : 0);
+  names_lookup<<<blocks_for(n), kTpb, 0, s>>>(n, names.n_bytes, names.off, names.bytes,
+                                              view_of(ctx->names), d_slot, d_hash, d_unknown,
+                                              count_empty ? 1 : 0);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
 }
@@ -404,7 +406,7 @@ int pas_names_set(pas_ctx* ctx, int32_t n_slots, const int64_t* name_off, const 
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_set";
   if (n_slots < 0) return set_error(ctx, PAS_EINVAL, fn + ": n_slots < 0");
-  int rc = check_csr(ctx, n_slots, name_off, bytes, fn);
+  int rc = check_host_spans(ctx, n_slots, name_off, bytes, fn);
   if (rc) return rc;
   if ((rc = activate(ctx))) return rc;
   hipStream_t s = ctx->stream;
@@ -477,14 +479,14 @@ int pas_names_resolve_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int
   if (!ctx) return PAS_EINVAL;
   const std::string fn = "pas_names_resolve_device";
   if (!ctx->names.valid) return no_table(ctx, fn, kTable);
-  if (n < 0 || n_bytes < 0) return set_error(ctx, PAS_EINVAL, fn + ": n or n_bytes < 0");
-  if (n == 0) return PAS_OK;
-  if (!d_name_off || !d_slot_out || (n_bytes > 0 && !d_bytes))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  int rc = activate(ctx);
-  if (rc) return rc;
-  return names_resolve_launch(ctx, n, n_bytes, d_name_off, d_bytes, d_slot_out, nullptr, nullptr,
-                              false, pick_stream(ctx, hip_stream));
+  const ByteSpans names{n_bytes, d_name_off, d_bytes};
+  if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
+  int rc = check_device_spans(ctx, n, names, fn);
+  if (rc || n == 0) return rc;
+  if (!d_slot_out) return set_error(ctx, PAS_EINVAL, fn + ": null output");
+  if ((rc = activate(ctx))) return rc;
+  return names_resolve_launch(ctx, n, names, d_slot_out, nullptr, nullptr, false,
+                              pick_stream(ctx, hip_stream));
 }
 
 int pas_names_resolve(pas_ctx* ctx, int64_t n, const int64_t* name_off, const char* bytes,
@@ -494,20 +496,17 @@ int pas_names_resolve(pas_ctx* ctx, int64_t n, const int64_t* name_off, const ch
   if (!ctx->names.valid) return no_table(ctx, fn, kTable);
   if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
   if (n == 0) return PAS_OK;
-  int rc = check_csr(ctx, n, name_off, bytes, fn);
+  int rc = check_host_spans(ctx, n, name_off, bytes, fn);
   if (rc) return rc;
   if (!slot_out) return set_error(ctx, PAS_EINVAL, fn + ": null output");
   if ((rc = activate(ctx))) return rc;
   Staging st(ctx);
-  int64_t* d_off;
-  char* d_bytes;
+  ByteSpans names;
   int32_t* d_slot;
-  st.in(d_off, name_off, (size_t)n + 1);
-  st.in(d_bytes, bytes, (size_t)name_off[n]);
+  st.in_spans(names, n, name_off, bytes);
   st.out(d_slot, slot_out, (size_t)n);
   if ((rc = st.upload())) return rc;
-  rc = names_resolve_launch(ctx, n, name_off[n], d_off, d_bytes, d_slot, nullptr, nullptr, false,
-                            ctx->stream);
+  rc = names_resolve_launch(ctx, n, names, d_slot, nullptr, nullptr, false, ctx->stream);
   if (rc) return rc;
   PAS_HIP(ctx, st.fetch());
   return PAS_OK;
@@ -521,16 +520,14 @@ int pas_names_assign_device(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int6
   const std::string fn = "pas_names_assign_device";
   if (n_new_out) *n_new_out = 0;
   if (!ctx->names.valid) return no_table(ctx, fn, kTable);
-  if (n < 0 || n > INT32_MAX || n_bytes < 0 || new_cap < 0)
-    return set_error(ctx, PAS_EINVAL, fn + ": n, n_bytes or new_cap out of range");
-  if (n == 0) return PAS_OK;
-  if (!d_name_off || (n_bytes > 0 && !d_bytes))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  int rc = activate(ctx);
-  if (rc) return rc;
-  return names_assign_launch(ctx, n, n_bytes, d_name_off, d_bytes, d_slot_out, new_cap,
-                             new_entry_out, new_slot_out, n_new_out,
-                             pick_stream(ctx, hip_stream));
+  const ByteSpans names{n_bytes, d_name_off, d_bytes};
+  if (n < 0 || n > INT32_MAX || new_cap < 0)
+    return set_error(ctx, PAS_EINVAL, fn + ": n or new_cap out of range");
+  int rc = check_device_spans(ctx, n, names, fn);
+  if (rc || n == 0) return rc;
+  if ((rc = activate(ctx))) return rc;
+  return names_assign_launch(ctx, n, names, d_slot_out, new_cap, new_entry_out, new_slot_out,
+                             n_new_out, pick_stream(ctx, hip_stream));
 }
 
 int pas_names_assign(pas_ctx* ctx, int64_t n, const int64_t* name_off, const char* bytes,
@@ -543,19 +540,17 @@ int pas_names_assign(pas_ctx* ctx, int64_t n, const int64_t* name_off, const cha
   if (n < 0 || n > INT32_MAX || new_cap < 0)
     return set_error(ctx, PAS_EINVAL, fn + ": n or new_cap out of range");
   if (n == 0) return PAS_OK;
-  int rc = check_csr(ctx, n, name_off, bytes, fn);
+  int rc = check_host_spans(ctx, n, name_off, bytes, fn);
   if (rc) return rc;
   if ((rc = activate(ctx))) return rc;
   Staging st(ctx);
-  int64_t* d_off;
-  char* d_bytes;
+  ByteSpans names;
   int32_t* d_slot;
-  st.in(d_off, name_off, (size_t)n + 1);
-  st.in(d_bytes, bytes, (size_t)name_off[n]);
+  st.in_spans(names, n, name_off, bytes);
   st.out_opt(d_slot, slot_out, (size_t)n);
   if ((rc = st.upload())) return rc;
-  rc = names_assign_launch(ctx, n, name_off[n], d_off, d_bytes, d_slot, new_cap, new_entry_out,
-                           new_slot_out, n_new_out, ctx->stream);
+  rc = names_assign_launch(ctx, n, names, d_slot, new_cap, new_entry_out, new_slot_out,
+                           n_new_out, ctx->stream);
   if (rc && rc != PAS_ECAPACITY) return rc;
   const std::string msg = ctx->err;  // (PAS_ECAPACITY: slot_out holds the plain lookups)
   PAS_HIP(ctx, st.fetch());

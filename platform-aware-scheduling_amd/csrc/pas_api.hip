@@ -1,5 +1,7 @@
-// pas_api.hip — the C-ABI surface (include/pas.h): context, errors, timing, quantity
-// parsing and the host-pointer wrappers around the device launches.
+// pas_api.hip — the C-ABI surface (include/pas.h): context, errors, timing and the
+// host-pointer wrappers around the device launches.  The verbs that take strings keep their
+// entry points next to their kernels (tas_ingest.hip, name_table.hip, gas_cards.hip,
+// gas_annotations.hip, gas_node_strings.hip, gas_render.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -244,6 +246,57 @@ int gas_annotations_tables(pas_ctx* ctx, bool by_name, const std::string& fn) {
   return PAS_OK;
 }
 
+int check_update(pas_ctx* ctx, uint64_t gen_from, int32_t n_cols, const int32_t* cols,
+                 const void* vals, const void* present, const char* fn) {
+  if (!ctx->tas.valid) return set_error(ctx, PAS_ENOSNAP, std::string(fn) + ": no TAS snapshot");
+  if (ctx->tas.gen != gen_from)
+    return set_error(ctx, PAS_ESTALE, std::string(fn) + ": resident generation " +
+                                          std::to_string(ctx->tas.gen) + ", update from " +
+                                          std::to_string(gen_from));
+  const int32_t M = ctx->tas.n_metrics;
+  if (n_cols < 0 || n_cols > M)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad column count");
+  if (n_cols > 0 && (!cols || (ctx->tas.n_nodes > 0 && (!vals || !present))))
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
+  std::vector<char> seen((size_t)M, 0);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    if (cols[c] < 0 || cols[c] >= M || seen[(size_t)cols[c]]++)
+      return set_error(ctx, PAS_EINVAL,
+                       std::string(fn) + ": columns must be distinct metric indices < n_metrics");
+  }
+  return PAS_OK;
+}
+
+int check_gas_gen(pas_ctx* ctx, uint64_t gen) {
+  if (!ctx->gas.valid) return set_error(ctx, PAS_ENOSNAP, "no GAS snapshot uploaded");
+  if (ctx->gas.gen != gen) return set_error(ctx, PAS_ESTALE, "GAS snapshot generation mismatch");
+  return PAS_OK;
+}
+
+int gas_pod_check(pas_ctx* ctx, int32_t p, int32_t max_containers,
+                  const uint32_t* req_mask, const int32_t* n_containers,
+                  const char* fn) {
+  if (n_containers[p] < 0 || n_containers[p] > max_containers)
+    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": n_containers out of range");
+  for (int32_t c = 0; c < n_containers[p]; ++c)
+    if ((req_mask[(int64_t)p * max_containers + c] & ~PAS_REQ_UNKNOWN_KIND) >> ctx->gas.n_res)
+      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": mask bit >= n_res");
+  return PAS_OK;
+}
+
+int gas_finish(pas_ctx* ctx, int rc, bool wrote, uint64_t gen_to, bool cards) {
+  if (rc) {
+    if (wrote) {
+      ctx->gas.valid = false;
+      if (cards) ctx->gas_cards.valid = false;
+    }
+    return rc;
+  }
+  ctx->gas.gen = gen_to;
+  ++ctx->gas.epoch;
+  return PAS_OK;
+}
+
 }  // namespace pas
 
 using namespace pas;
@@ -384,27 +437,6 @@ int pas_tas_snapshot_set_device(pas_ctx* ctx, uint64_t gen, int32_t n_nodes, int
                             pick_stream(ctx, hip_stream));
 }
 
-static int check_update(pas_ctx* ctx, uint64_t gen_from, int32_t n_cols, const int32_t* cols,
-                        const void* vals, const void* present, const char* fn) {
-  if (!ctx->tas.valid) return set_error(ctx, PAS_ENOSNAP, std::string(fn) + ": no TAS snapshot");
-  if (ctx->tas.gen != gen_from)
-    return set_error(ctx, PAS_ESTALE, std::string(fn) + ": resident generation " +
-                                          std::to_string(ctx->tas.gen) + ", update from " +
-                                          std::to_string(gen_from));
-  const int32_t M = ctx->tas.n_metrics;
-  if (n_cols < 0 || n_cols > M)
-    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": bad column count");
-  if (n_cols > 0 && (!cols || (ctx->tas.n_nodes > 0 && (!vals || !present))))
-    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
-  std::vector<char> seen((size_t)M, 0);
-  for (int32_t c = 0; c < n_cols; ++c) {
-    if (cols[c] < 0 || cols[c] >= M || seen[(size_t)cols[c]]++)
-      return set_error(ctx, PAS_EINVAL,
-                       std::string(fn) + ": columns must be distinct metric indices < n_metrics");
-  }
-  return PAS_OK;
-}
-
 // The host forms' staging: the columns (nano with the wide form only) into the context's
 // scratch, the update on the context's stream, and its end awaited.
 static int stage_update(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols, const int32_t* cols,
@@ -480,249 +512,6 @@ int pas_tas_snapshot_update_wide_device(pas_ctx* ctx, uint64_t gen_from, uint64_
   if ((rc = activate(ctx))) return rc;
   return tas_snapshot_update_wide(ctx, gen_to, n_cols, cols, d_whole, d_nano, d_present,
                                   pick_stream(ctx, hip_stream));
-}
-
-// ---- Quantity literals parsed on the device (tas_ingest.hip)
-
-// offsets [n + 1] of a host form: from 0 and non-decreasing
-static int check_offsets(pas_ctx* ctx, int64_t n, const int64_t* off, const std::string& what) {
-  if (!off || off[0] != 0) return set_error(ctx, PAS_EINVAL, what + ": offsets must start at 0");
-  for (int64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return set_error(ctx, PAS_EINVAL, what + ": offsets decrease");
-  return PAS_OK;
-}
-
-int pas_quantities_to_wide(pas_ctx* ctx, int64_t n, const int64_t* lit_off, const char* bytes,
-                           int64_t* whole, uint32_t* nano, int32_t* decimals, int32_t* status) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_quantities_to_wide";
-  if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
-  if (n == 0) return PAS_OK;
-  int rc = check_offsets(ctx, n, lit_off, fn);
-  if (rc) return rc;
-  if (lit_off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  if ((rc = activate(ctx))) return rc;
-  Staging st(ctx);
-  int64_t *d_off, *d_whole;
-  char* d_bytes;
-  uint32_t* d_nano;
-  int32_t *d_dec, *d_status;
-  st.in(d_off, lit_off, (size_t)n + 1);
-  st.in(d_bytes, bytes, (size_t)lit_off[n]);
-  st.out_opt(d_whole, whole, (size_t)n);
-  st.out_opt(d_nano, nano, (size_t)n);
-  st.out_opt(d_dec, decimals, (size_t)n);
-  st.out_opt(d_status, status, (size_t)n);
-  if ((rc = st.upload())) return rc;
-  rc = quantities_parse_launch(ctx, n, lit_off[n], d_off, d_bytes, d_whole, d_nano, d_dec,
-                               d_status, ctx->stream);
-  if (rc) return rc;
-  PAS_HIP(ctx, st.fetch());
-  return PAS_OK;
-}
-
-int pas_quantities_to_wide_device(pas_ctx* ctx, int64_t n, int64_t n_bytes,
-                                  const int64_t* d_lit_off, const char* d_bytes,
-                                  int64_t* d_whole, uint32_t* d_nano, int32_t* d_decimals,
-                                  int32_t* d_status, void* hip_stream) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_quantities_to_wide_device";
-  if (n < 0 || n_bytes < 0) return set_error(ctx, PAS_EINVAL, fn + ": n or n_bytes < 0");
-  if (n == 0) return PAS_OK;
-  if (!d_lit_off || (n_bytes > 0 && !d_bytes))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  int rc = activate(ctx);
-  if (rc) return rc;
-  return quantities_parse_launch(ctx, n, n_bytes, d_lit_off, d_bytes, d_whole, d_nano,
-                                 d_decimals, d_status, pick_stream(ctx, hip_stream));
-}
-
-// The checks both forms of pas_tas_snapshot_update_quantities share: the snapshot and its
-// generation, the columns, and col_off as a CSR of at most INT32_MAX entries.
-static int check_update_quantities(pas_ctx* ctx, uint64_t gen_from, int32_t n_cols,
-                                   const int32_t* cols, const int64_t* col_off,
-                                   const std::string& fn) {
-  int rc = check_update(ctx, gen_from, n_cols, cols, col_off, col_off, fn.c_str());
-  if (rc) return rc;
-  if (n_cols == 0) return PAS_OK;
-  if ((rc = check_offsets(ctx, n_cols, col_off, fn + ": col_off"))) return rc;
-  if (col_off[n_cols] > INT32_MAX)
-    return set_error(ctx, PAS_EINVAL, fn + ": more than INT32_MAX entries");
-  return PAS_OK;
-}
-
-int pas_tas_snapshot_update_quantities_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
-                                              int32_t n_cols, const int32_t* cols,
-                                              const int64_t* col_off, int64_t n_bytes,
-                                              const int32_t* d_entry_node,
-                                              const int64_t* d_lit_off, const char* d_bytes,
-                                              int32_t* kind_out, int32_t* scale_out,
-                                              int64_t* bad_entry, void* hip_stream) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_tas_snapshot_update_quantities_device";
-  if (bad_entry) *bad_entry = -1;
-  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
-  if (rc) return rc;
-  if (n_cols > 0 && col_off[n_cols] > 0 &&
-      (!d_entry_node || !d_lit_off || n_bytes < 0 || (n_bytes > 0 && !d_bytes)))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input or n_bytes < 0");
-  if ((rc = activate(ctx))) return rc;
-  return tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, n_bytes, d_entry_node,
-                                      d_lit_off, d_bytes, kind_out, scale_out, bad_entry,
-                                      pick_stream(ctx, hip_stream));
-}
-
-int pas_tas_snapshot_update_quantities(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
-                                       int32_t n_cols, const int32_t* cols,
-                                       const int64_t* col_off, const int32_t* entry_node,
-                                       const int64_t* lit_off, const char* bytes,
-                                       int32_t* kind_out, int32_t* scale_out,
-                                       int64_t* bad_entry) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_tas_snapshot_update_quantities";
-  if (bad_entry) *bad_entry = -1;
-  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
-  if (rc) return rc;
-  const int64_t T = n_cols > 0 ? col_off[n_cols] : 0;
-  int64_t n_bytes = 0;
-  if (T > 0) {
-    if (!entry_node) return set_error(ctx, PAS_EINVAL, fn + ": null input");
-    if ((rc = check_offsets(ctx, T, lit_off, fn + ": lit_off"))) return rc;
-    n_bytes = lit_off[T];
-    if (n_bytes > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
-    // updateMetric replaces a node map: a node listed twice in one column is no map
-    const int32_t N = ctx->tas.n_nodes;
-    std::vector<uint64_t> seen((size_t)w64(N));
-    for (int32_t c = 0; c < n_cols; ++c) {
-      std::fill(seen.begin(), seen.end(), 0);
-      for (int64_t i = col_off[c]; i < col_off[c + 1]; ++i) {
-        const int32_t nd = entry_node[i];
-        if (nd < 0 || nd >= N) continue;
-        uint64_t& w = seen[(size_t)(nd >> 6)];
-        if ((w >> (nd & 63)) & 1ull)
-          return set_error(ctx, PAS_EINVAL, fn + ": column " + std::to_string(cols[c]) +
-                                                " lists node " + std::to_string(nd) + " twice");
-        w |= 1ull << (nd & 63);
-      }
-    }
-  }
-  if ((rc = activate(ctx))) return rc;
-  Staging st(ctx);
-  int32_t* d_node;
-  int64_t* d_off;
-  char* d_bytes;
-  st.in(d_node, entry_node, (size_t)T);
-  st.in(d_off, lit_off, T > 0 ? (size_t)T + 1 : 0);
-  st.in(d_bytes, bytes, (size_t)n_bytes);
-  if ((rc = st.upload())) return rc;
-  rc = tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, n_bytes, d_node, d_off,
-                                    d_bytes, kind_out, scale_out, bad_entry, ctx->stream);
-  if (rc) return rc;
-  PAS_HIP(ctx, st.fetch());
-  return PAS_OK;
-}
-
-// The refresh with each entry's node given by name (name_table.hip): the names are resolved,
-// lookup only, into a buffer of the stream's slot and the refresh above runs on it.  The count
-// of entries without a slot comes back on s before that launch's own synchronize.
-static int update_quantities_names_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
-                                          const int32_t* cols, const int64_t* col_off,
-                                          int64_t n_name_bytes, const int64_t* d_name_off,
-                                          const char* d_name_bytes, int64_t n_bytes,
-                                          const int64_t* d_lit_off, const char* d_bytes,
-                                          int32_t* kind_out, int32_t* scale_out,
-                                          int64_t* bad_entry, int64_t* n_unknown_out,
-                                          hipStream_t s) {
-  const int64_t T = n_cols > 0 ? col_off[n_cols] : 0;
-  if (n_unknown_out) *n_unknown_out = 0;
-  int rc = PAS_OK;
-  SlotScope scope(ctx, s, 0, &rc);
-  if (!scope.slot) return rc;
-  int32_t* d_node = nullptr;
-  uint32_t unknown = 0;
-  if (T > 0) {
-    const size_t total = carve_size({sizeof(uint32_t), sizeof(int32_t) * (size_t)T});
-    char* base = static_cast<char*>(slot_buf(ctx, scope.slot, kBufNames, total, s, &rc));
-    if (!base) return rc;
-    Carve cv{base};
-    uint32_t* d_ctr = cv.take<uint32_t>(1);
-    d_node = cv.take<int32_t>((size_t)T);
-    PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(uint32_t), s));
-    rc = names_resolve_launch(ctx, T, n_name_bytes, d_name_off, d_name_bytes, d_node, nullptr,
-                              d_ctr, true, s);
-    if (rc) return rc;
-    PAS_HIP(ctx, hipMemcpyAsync(&unknown, d_ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  }
-  rc = tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, n_bytes, d_node,
-                                    d_lit_off, d_bytes, kind_out, scale_out, bad_entry, s);
-  if (T > 0 && rc) (void)hipStreamSynchronize(s);  // (an early error: `unknown` is a local)
-  if (n_unknown_out) *n_unknown_out = unknown;
-  return rc;
-}
-
-int pas_tas_snapshot_update_quantities_names_device(
-    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_cols, const int32_t* cols,
-    const int64_t* col_off, int64_t n_name_bytes, const int64_t* d_name_off,
-    const char* d_name_bytes, int64_t n_bytes, const int64_t* d_lit_off, const char* d_bytes,
-    int32_t* kind_out, int32_t* scale_out, int64_t* bad_entry, int64_t* n_unknown_out,
-    void* hip_stream) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_tas_snapshot_update_quantities_names_device";
-  if (bad_entry) *bad_entry = -1;
-  if (n_unknown_out) *n_unknown_out = 0;
-  if (!ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
-  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
-  if (rc) return rc;
-  if (n_cols > 0 && col_off[n_cols] > 0 &&
-      (!d_name_off || !d_lit_off || n_bytes < 0 || n_name_bytes < 0 || (n_bytes > 0 && !d_bytes) ||
-       (n_name_bytes > 0 && !d_name_bytes)))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input or a byte count < 0");
-  if ((rc = activate(ctx))) return rc;
-  return update_quantities_names_launch(ctx, gen_to, n_cols, cols, col_off, n_name_bytes,
-                                        d_name_off, d_name_bytes, n_bytes, d_lit_off, d_bytes,
-                                        kind_out, scale_out, bad_entry, n_unknown_out,
-                                        pick_stream(ctx, hip_stream));
-}
-
-int pas_tas_snapshot_update_quantities_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
-                                             int32_t n_cols, const int32_t* cols,
-                                             const int64_t* col_off, const int64_t* name_off,
-                                             const char* name_bytes, const int64_t* lit_off,
-                                             const char* bytes, int32_t* kind_out,
-                                             int32_t* scale_out, int64_t* bad_entry,
-                                             int64_t* n_unknown_out) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_tas_snapshot_update_quantities_names";
-  if (bad_entry) *bad_entry = -1;
-  if (n_unknown_out) *n_unknown_out = 0;
-  if (!ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
-  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, fn);
-  if (rc) return rc;
-  const int64_t T = n_cols > 0 ? col_off[n_cols] : 0;
-  int64_t n_bytes = 0, n_name_bytes = 0;
-  if (T > 0) {
-    if ((rc = check_offsets(ctx, T, lit_off, fn + ": lit_off"))) return rc;
-    if ((rc = check_offsets(ctx, T, name_off, fn + ": name_off"))) return rc;
-    n_bytes = lit_off[T];
-    n_name_bytes = name_off[T];
-    if ((n_bytes > 0 && !bytes) || (n_name_bytes > 0 && !name_bytes))
-      return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  }
-  if ((rc = activate(ctx))) return rc;
-  Staging st(ctx);
-  int64_t *d_name_off, *d_off;
-  char *d_name_bytes, *d_bytes;
-  st.in(d_name_off, name_off, T > 0 ? (size_t)T + 1 : 0);
-  st.in(d_name_bytes, name_bytes, (size_t)n_name_bytes);
-  st.in(d_off, lit_off, T > 0 ? (size_t)T + 1 : 0);
-  st.in(d_bytes, bytes, (size_t)n_bytes);
-  if ((rc = st.upload())) return rc;
-  rc = update_quantities_names_launch(ctx, gen_to, n_cols, cols, col_off, n_name_bytes,
-                                      d_name_off, d_name_bytes, n_bytes, d_off, d_bytes, kind_out,
-                                      scale_out, bad_entry, n_unknown_out, ctx->stream);
-  if (rc) return rc;
-  PAS_HIP(ctx, st.fetch());
-  return PAS_OK;
 }
 
 int pas_tas_snapshot_drop(pas_ctx* ctx) {
@@ -1642,64 +1431,6 @@ int pas_gas_snapshot_set_device(pas_ctx* ctx, uint64_t gen, int32_t n_nodes, int
   return PAS_OK;
 }
 
-static int check_gas_gen(pas_ctx* ctx, uint64_t gen) {
-  if (!ctx->gas.valid) return set_error(ctx, PAS_ENOSNAP, "no GAS snapshot uploaded");
-  if (ctx->gas.gen != gen) return set_error(ctx, PAS_ESTALE, "GAS snapshot generation mismatch");
-  return PAS_OK;
-}
-
-// Pod p of a host batch: n_containers[p] within [0, max_containers] and no mask bit at or
-// above n_res.  Bind / release and apply check the pods their operations name, place and fit
-// check every pod.
-static int gas_pod_check(pas_ctx* ctx, int32_t p, int32_t max_containers,
-                         const uint32_t* req_mask, const int32_t* n_containers,
-                         const char* fn) {
-  if (n_containers[p] < 0 || n_containers[p] > max_containers)
-    return set_error(ctx, PAS_EINVAL, std::string(fn) + ": n_containers out of range");
-  for (int32_t c = 0; c < n_containers[p]; ++c)
-    if ((req_mask[(int64_t)p * max_containers + c] & ~PAS_REQ_UNKNOWN_KIND) >> ctx->gas.n_res)
-      return set_error(ctx, PAS_EINVAL, std::string(fn) + ": mask bit >= n_res");
-  return PAS_OK;
-}
-
-// The pod batch of a GAS host form on the device: req [P][C][Q], req_mask [P][C] and
-// n_containers [P], stated to st.  The pointers are valid at P == 0 or C == 0 too (nothing is
-// copied then): the kernels read no request of a pod without containers.
-struct PodBatch {
-  int64_t* req;
-  uint32_t* mask;
-  int32_t* nc;
-};
-static void stage_pods(Staging& st, PodBatch& d, int32_t n_pods, int32_t max_containers,
-                       const int64_t* req, const uint32_t* req_mask,
-                       const int32_t* n_containers) {
-  const size_t P = (size_t)n_pods, C = (size_t)max_containers;
-  st.in(d.req, req, P * C * (size_t)st.ctx()->gas.n_res);
-  st.in(d.mask, req_mask, P * C);
-  st.in(d.nc, n_containers, P);
-}
-
-// A call that wrote the resident snapshot has succeeded: the generation step.
-static int gas_stepped(pas_ctx* ctx, uint64_t gen_to) {
-  ctx->gas.gen = gen_to;
-  ++ctx->gas.epoch;
-  return PAS_OK;
-}
-
-// The tail of the host forms that write the resident usage (bind / release, apply, nodes
-// update).  enqueued = their kernel is on the context's stream: st's outputs are fetched, and
-// a failure of that leaves a snapshot of unknown content, which is invalidated.  Otherwise the
-// generation steps.
-static int gas_write_finish(pas_ctx* ctx, uint64_t gen_to, bool enqueued, Staging& st,
-                            const std::string& fn) {
-  const hipError_t e = enqueued ? st.fetch() : hipSuccess;
-  if (e != hipSuccess) {
-    ctx->gas.valid = false;
-    return check_hip(ctx, e, (fn + ": copy of the results").c_str());
-  }
-  return gas_stepped(ctx, gen_to);
-}
-
 // Shared host path of pas_gas_bind / pas_gas_release: validates, groups the operations by
 // node (stable), uploads everything in one scratch carve and runs the walker kernel.
 static int gas_commit(pas_ctx* ctx, bool release, uint64_t gen_from, uint64_t gen_to,
@@ -1781,12 +1512,13 @@ static int gas_commit(pas_ctx* ctx, bool release, uint64_t gen_from, uint64_t ge
   st.out(d_status, status_out, ops);
   if (n_ops > 0) {
     if ((rc = st.upload())) return rc;
-    if ((rc = gas_commit_launch(ctx, release, n_ops, max_containers, i915_index, d_order, d_key,
-                                d_pod, d.req, d.mask, d.nc, d_cpc, d_cards, cards_stride, d_res,
-                                d_status, d_sel, d_nsel, d_cnt_out, d_cnt_in, ctx->stream)))
+    if ((rc = gas_commit_launch(ctx, release, n_ops, i915_index, d_order, d_key, d_pod, d, d_cpc,
+                                d_cards, cards_stride, d_res, d_status, d_sel, d_nsel, d_cnt_out,
+                                d_cnt_in, ctx->stream)))
       return rc;
   }
-  return gas_write_finish(ctx, gen_to, n_ops > 0, st, fn);
+  rc = n_ops > 0 ? st.fetch_results(fn) : PAS_OK;
+  return gas_finish(ctx, rc, rc != PAS_OK, gen_to);
 }
 
 int pas_gas_bind(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_binds,
@@ -1898,12 +1630,11 @@ int pas_gas_apply_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
                            "pas_gas_apply_device");
   if (rc) return rc;
   if ((rc = activate(ctx))) return rc;
-  if ((rc = gas_apply_launch(ctx, n_events, d_ev_kind, d_ev_pod, d_ev_node, n_pods,
-                             max_containers, d_req, d_req_mask, d_n_containers,
-                             d_cards_per_container, d_cards, cards_ld, d_status_out,
-                             pick_stream(ctx, hip_stream))))
-    return rc;
-  return gas_stepped(ctx, gen_to);
+  const PodBatch pods{n_pods, max_containers, d_req, d_req_mask, d_n_containers};
+  rc = gas_apply_launch(ctx, n_events, d_ev_kind, d_ev_pod, d_ev_node, pods,
+                        d_cards_per_container, d_cards, cards_ld, d_status_out,
+                        pick_stream(ctx, hip_stream));
+  return gas_finish(ctx, rc, false, gen_to);
 }
 
 int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
@@ -1951,263 +1682,12 @@ int pas_gas_apply(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_ev
   if (n_events > 0) {
     if ((rc = st.upload())) return rc;
     // the _device form's path: grouping and commit on the device
-    if ((rc = gas_apply_launch(ctx, n_events, d_kind, d_pod, d_node, n_pods, max_containers,
-                               d.req, d.mask, d.nc, d_cpc, d_cards, cards_ld, d_status,
-                               ctx->stream)))
+    if ((rc = gas_apply_launch(ctx, n_events, d_kind, d_pod, d_node, d, d_cpc, d_cards, cards_ld,
+                               d_status, ctx->stream)))
       return rc;
   }
-  return gas_write_finish(ctx, gen_to, n_events > 0, st, fn);
-}
-
-// offsets [n + 1] of a host form's byte spans: from 0, non-decreasing, bytes when any
-static int check_spans(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
-                       const std::string& what) {
-  int rc = check_offsets(ctx, n, off, what);
-  if (rc) return rc;
-  if (off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, what + ": null bytes");
-  return PAS_OK;
-}
-
-int pas_gas_annotations_resolve_device(pas_ctx* ctx, int32_t n_events, const int32_t* d_ev_pod,
-                                       const int32_t* d_ev_node, int32_t n_pods,
-                                       const int32_t* d_n_containers, int32_t max_containers,
-                                       int64_t n_ann_bytes, const int64_t* d_ann_off,
-                                       const char* d_ann_bytes, int32_t cards_ld,
-                                       int32_t* d_verdict_out, int32_t* d_n_listed_out,
-                                       int32_t* d_cards_per_container_out, int32_t* d_cards_out,
-                                       void* hip_stream) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_gas_annotations_resolve_device";
-  if (!ctx->gas.valid) return set_error(ctx, PAS_ENOSNAP, "no GAS snapshot uploaded");
-  int rc = gas_annotations_tables(ctx, false, fn);
-  if (rc) return rc;
-  if (n_events < 0 || n_pods < 0 || max_containers < 0 || cards_ld < 1 || n_ann_bytes < 0)
-    return set_error(ctx, PAS_EINVAL, fn + ": bad shape");
-  if (n_events > 0 &&
-      (!d_ev_pod || !d_ev_node || !d_ann_off || (n_ann_bytes > 0 && !d_ann_bytes) ||
-       (n_pods > 0 && !d_n_containers) || !d_verdict_out || !d_n_listed_out || !d_cards_out ||
-       (max_containers > 0 && !d_cards_per_container_out)))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  if ((rc = activate(ctx))) return rc;
-  return annotations_resolve_launch(ctx, n_events, nullptr, d_ev_pod, d_ev_node, 0, nullptr, n_pods,
-                                    d_n_containers, max_containers, n_ann_bytes, d_ann_off,
-                                    d_ann_bytes, cards_ld, d_verdict_out, d_n_listed_out,
-                                    d_cards_per_container_out, d_cards_out,
-                                    pick_stream(ctx, hip_stream));
-}
-
-int pas_gas_annotations_resolve(pas_ctx* ctx, int32_t n_events, const int32_t* ev_pod,
-                                const int32_t* ev_node, int32_t n_pods,
-                                const int32_t* n_containers, int32_t max_containers,
-                                const int64_t* ann_off, const char* ann_bytes, int32_t cards_ld,
-                                int32_t* verdict_out, int32_t* n_listed_out,
-                                int32_t* cards_per_container_out, int32_t* cards_out) {
-  if (!ctx) return PAS_EINVAL;
-  const std::string fn = "pas_gas_annotations_resolve";
-  if (!ctx->gas.valid) return set_error(ctx, PAS_ENOSNAP, "no GAS snapshot uploaded");
-  int rc = gas_annotations_tables(ctx, false, fn);
-  if (rc) return rc;
-  if (n_events < 0 || n_pods < 0 || max_containers < 0 || cards_ld < 1)
-    return set_error(ctx, PAS_EINVAL, fn + ": bad shape");
-  if (n_events == 0) return PAS_OK;
-  if (!ev_pod || !ev_node || (n_pods > 0 && !n_containers) || !verdict_out || !n_listed_out ||
-      !cards_out || (max_containers > 0 && !cards_per_container_out))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  if ((rc = check_spans(ctx, n_events, ann_off, ann_bytes, fn + ": ann_off"))) return rc;
-  if ((rc = activate(ctx))) return rc;
-  const size_t E = (size_t)n_events;
-  Staging st(ctx);
-  int32_t *d_pod, *d_node, *d_nc, *d_verdict, *d_listed, *d_cpc, *d_cards;
-  int64_t* d_off;
-  char* d_bytes;
-  st.in(d_pod, ev_pod, E);
-  st.in(d_node, ev_node, E);
-  st.in(d_nc, n_containers, (size_t)n_pods);
-  st.in(d_off, ann_off, E + 1);
-  st.in(d_bytes, ann_bytes, (size_t)ann_off[E]);
-  st.out(d_verdict, verdict_out, E);
-  st.out(d_listed, n_listed_out, E);
-  st.out(d_cpc, cards_per_container_out, E * (size_t)max_containers);
-  st.out(d_cards, cards_out, E * (size_t)cards_ld);
-  if ((rc = st.upload())) return rc;
-  rc = annotations_resolve_launch(ctx, n_events, nullptr, d_pod, d_node, 0, nullptr, n_pods, d_nc,
-                                  max_containers, ann_off[E], d_off, d_bytes, cards_ld, d_verdict,
-                                  d_listed, d_cpc, d_cards, ctx->stream);
-  if (rc) return rc;
-  PAS_HIP(ctx, st.fetch());
-  return PAS_OK;
-}
-
-// What the four apply forms share: the snapshot, its generation and the tables, then the checks
-// a host can make on either form's scalars and pointers (by_name: the nodes by name).
-static int gas_apply_annotations_check(pas_ctx* ctx, bool by_name, uint64_t gen_from,
-                                       int32_t n_events, const void* ev_kind, const void* ev_pod,
-                                       const void* ev_node, const void* node_name_off,
-                                       int32_t n_pods, int32_t max_containers, const void* req,
-                                       const void* req_mask, const void* n_containers,
-                                       const void* ann_off, const void* status_out,
-                                       const std::string& fn) {
-  int rc = check_gas_gen(ctx, gen_from);
-  if (rc) return rc;
-  if ((rc = gas_annotations_tables(ctx, by_name, fn))) return rc;
-  if (n_events < 0 || n_pods < 0 || max_containers < 0)
-    return set_error(ctx, PAS_EINVAL, fn + ": bad shape");
-  if (n_events > 0 && (!ev_kind || !ev_pod || !(by_name ? node_name_off : ev_node) || !ann_off ||
-                       !status_out || (n_pods > 0 && !n_containers) ||
-                       (max_containers > 0 && n_pods > 0 && (!req || !req_mask))))
-    return set_error(ctx, PAS_EINVAL, fn + ": null input");
-  return PAS_OK;
-}
-
-static int gas_apply_annotations_device(pas_ctx* ctx, bool by_name, uint64_t gen_from,
-                                        uint64_t gen_to, int32_t n_events,
-                                        const int32_t* d_ev_kind,
-                                        const int32_t* d_ev_pod, const int32_t* d_ev_node,
-                                        int64_t n_name_bytes, const int64_t* d_node_name_off,
-                                        const char* d_node_name_bytes, int32_t n_pods,
-                                        int32_t max_containers, const int64_t* d_req,
-                                        const uint32_t* d_req_mask, const int32_t* d_n_containers,
-                                        int64_t n_ann_bytes, const int64_t* d_ann_off,
-                                        const char* d_ann_bytes, int32_t* d_status_out,
-                                        void* hip_stream, const std::string& fn) {
-  if (!ctx) return PAS_EINVAL;
-  int rc = gas_apply_annotations_check(ctx, by_name, gen_from, n_events, d_ev_kind, d_ev_pod,
-                                       d_ev_node, d_node_name_off, n_pods, max_containers, d_req, d_req_mask,
-                                       d_n_containers, d_ann_off, d_status_out, fn);
-  if (rc) return rc;
-  if (n_ann_bytes < 0 || n_name_bytes < 0 || (n_events > 0 && n_ann_bytes > 0 && !d_ann_bytes) ||
-      (n_events > 0 && by_name && n_name_bytes > 0 && !d_node_name_bytes))
-    return set_error(ctx, PAS_EINVAL, fn + ": null bytes or a byte count < 0");
-  if ((rc = activate(ctx))) return rc;
-  if ((rc = gas_apply_annotations_launch(ctx, n_events, d_ev_kind, d_ev_pod,
-                                         by_name ? nullptr : d_ev_node, n_name_bytes, d_node_name_off, d_node_name_bytes, n_pods,
-                                         max_containers, d_req, d_req_mask, d_n_containers,
-                                         n_ann_bytes, d_ann_off, d_ann_bytes, d_status_out,
-                                         pick_stream(ctx, hip_stream))))
-    return rc;
-  return gas_stepped(ctx, gen_to);
-}
-
-int pas_gas_apply_annotations_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
-                                     int32_t n_events, const int32_t* d_ev_kind,
-                                     const int32_t* d_ev_pod, const int32_t* d_ev_node,
-                                     int32_t n_pods, int32_t max_containers, const int64_t* d_req,
-                                     const uint32_t* d_req_mask, const int32_t* d_n_containers,
-                                     int64_t n_ann_bytes, const int64_t* d_ann_off,
-                                     const char* d_ann_bytes, int32_t* d_status_out,
-                                     void* hip_stream) {
-  return gas_apply_annotations_device(ctx, false, gen_from, gen_to, n_events, d_ev_kind, d_ev_pod,
-                                      d_ev_node, 0, nullptr, nullptr, n_pods, max_containers,
-                                      d_req, d_req_mask, d_n_containers, n_ann_bytes, d_ann_off,
-                                      d_ann_bytes, d_status_out, hip_stream,
-                                      "pas_gas_apply_annotations_device");
-}
-
-int pas_gas_apply_annotations_names_device(
-    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events, const int32_t* d_ev_kind,
-    const int32_t* d_ev_pod, int64_t n_name_bytes, const int64_t* d_node_name_off,
-    const char* d_node_name_bytes, int32_t n_pods, int32_t max_containers, const int64_t* d_req,
-    const uint32_t* d_req_mask, const int32_t* d_n_containers, int64_t n_ann_bytes,
-    const int64_t* d_ann_off, const char* d_ann_bytes, int32_t* d_status_out, void* hip_stream) {
-  return gas_apply_annotations_device(ctx, true, gen_from, gen_to, n_events, d_ev_kind, d_ev_pod,
-                                      nullptr, n_name_bytes, d_node_name_off, d_node_name_bytes,
-                                      n_pods, max_containers, d_req, d_req_mask, d_n_containers,
-                                      n_ann_bytes, d_ann_off, d_ann_bytes, d_status_out,
-                                      hip_stream, "pas_gas_apply_annotations_names_device");
-}
-
-// The host forms: validate (rules 1 and 3 are PAS_EINVAL for the call), upload, run the
-// _device forms' path, wait and copy status_out back.
-static int gas_apply_annotations_host(pas_ctx* ctx, bool by_name, uint64_t gen_from,
-                                      uint64_t gen_to, int32_t n_events, const int32_t* ev_kind,
-                                      const int32_t* ev_pod, const int32_t* ev_node,
-                                      const int64_t* node_name_off, const char* node_name_bytes,
-                                      int32_t n_pods, int32_t max_containers, const int64_t* req,
-                                      const uint32_t* req_mask, const int32_t* n_containers,
-                                      const int64_t* ann_off, const char* ann_bytes,
-                                      int32_t* status_out, const std::string& fn) {
-  if (!ctx) return PAS_EINVAL;
-  int rc = gas_apply_annotations_check(ctx, by_name, gen_from, n_events, ev_kind, ev_pod, ev_node,
-                                       node_name_off, n_pods, max_containers, req, req_mask,
-                                       n_containers, ann_off, status_out, fn);
-  if (rc) return rc;
-  const int32_t N = ctx->gas.n_nodes;
-  const size_t E = (size_t)n_events;
-  int64_t n_ann_bytes = 0, n_name_bytes = 0;
-  if (n_events > 0) {
-    if ((rc = check_spans(ctx, n_events, ann_off, ann_bytes, fn + ": ann_off"))) return rc;
-    n_ann_bytes = ann_off[E];
-    if (by_name) {
-      if ((rc = check_spans(ctx, n_events, node_name_off, node_name_bytes,
-                            fn + ": node_name_off")))
-        return rc;
-      n_name_bytes = node_name_off[E];
-    }
-  }
-  for (int32_t e = 0; e < n_events; ++e) {
-    if (ev_kind[e] != PAS_GAS_EV_ADD && ev_kind[e] != PAS_GAS_EV_REMOVE)
-      return set_error(ctx, PAS_EINVAL, fn + ": event kind out of range");
-    if (ev_pod[e] < 0 || ev_pod[e] >= n_pods)
-      return set_error(ctx, PAS_EINVAL, fn + ": pod index out of range");
-    if (!by_name && ev_node[e] != -1 && (ev_node[e] < 0 || ev_node[e] >= N))
-      return set_error(ctx, PAS_EINVAL, fn + ": node neither -1 nor a slot of the snapshot");
-    if ((rc = gas_pod_check(ctx, ev_pod[e], max_containers, req_mask, n_containers, fn.c_str())))
-      return rc;
-  }
-  if ((rc = activate(ctx))) return rc;
-  Staging st(ctx);
-  PodBatch d;
-  int32_t *d_kind, *d_pod, *d_node, *d_status;
-  int64_t *d_name_off, *d_ann_off;
-  char *d_name_bytes, *d_ann_bytes;
-  stage_pods(st, d, n_pods, max_containers, req, req_mask, n_containers);
-  st.in(d_kind, ev_kind, E);
-  st.in(d_pod, ev_pod, E);
-  d_node = nullptr, d_name_off = nullptr, d_name_bytes = nullptr;
-  if (by_name) {
-    st.in(d_name_off, node_name_off, E + 1);
-    st.in(d_name_bytes, node_name_bytes, (size_t)n_name_bytes);
-  } else {
-    st.in(d_node, ev_node, E);
-  }
-  st.in(d_ann_off, ann_off, n_events > 0 ? E + 1 : 0);
-  st.in(d_ann_bytes, ann_bytes, (size_t)n_ann_bytes);
-  st.out(d_status, status_out, E);
-  if (n_events > 0) {
-    if ((rc = st.upload())) return rc;
-    if ((rc = gas_apply_annotations_launch(ctx, n_events, d_kind, d_pod, d_node, n_name_bytes,
-                                           d_name_off, d_name_bytes, n_pods, max_containers, d.req,
-                                           d.mask, d.nc, n_ann_bytes, d_ann_off, d_ann_bytes,
-                                           d_status, ctx->stream)))
-      return rc;
-  }
-  return gas_write_finish(ctx, gen_to, n_events > 0, st, fn);
-}
-
-int pas_gas_apply_annotations(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_events,
-                              const int32_t* ev_kind, const int32_t* ev_pod,
-                              const int32_t* ev_node, int32_t n_pods, int32_t max_containers,
-                              const int64_t* req, const uint32_t* req_mask,
-                              const int32_t* n_containers, const int64_t* ann_off,
-                              const char* ann_bytes, int32_t* status_out) {
-  return gas_apply_annotations_host(ctx, false, gen_from, gen_to, n_events, ev_kind, ev_pod,
-                                    ev_node, nullptr, nullptr, n_pods, max_containers, req,
-                                    req_mask, n_containers, ann_off, ann_bytes, status_out,
-                                    "pas_gas_apply_annotations");
-}
-
-int pas_gas_apply_annotations_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
-                                    int32_t n_events, const int32_t* ev_kind,
-                                    const int32_t* ev_pod, const int64_t* node_name_off,
-                                    const char* node_name_bytes, int32_t n_pods,
-                                    int32_t max_containers, const int64_t* req,
-                                    const uint32_t* req_mask, const int32_t* n_containers,
-                                    const int64_t* ann_off, const char* ann_bytes,
-                                    int32_t* status_out) {
-  return gas_apply_annotations_host(ctx, true, gen_from, gen_to, n_events, ev_kind, ev_pod,
-                                    nullptr, node_name_off, node_name_bytes, n_pods, max_containers, req,
-                                    req_mask, n_containers, ann_off, ann_bytes, status_out,
-                                    "pas_gas_apply_annotations_names");
+  rc = n_events > 0 ? st.fetch_results(fn) : PAS_OK;
+  return gas_finish(ctx, rc, rc != PAS_OK, gen_to);
 }
 
 // What pas_gas_place and pas_gas_place_device share: the checks a host can make on either
@@ -2231,19 +1711,6 @@ static int gas_place_check(pas_ctx* ctx, uint64_t gen_from, int32_t n_pods,
   return PAS_OK;
 }
 
-// The rounds, then the generation step; a failure after commits began leaves no valid
-// snapshot behind.
-static int gas_place_finish(pas_ctx* ctx, int rc, bool began, uint64_t gen_to) {
-  if (rc) {
-    if (began) {
-      ctx->gas.valid = false;
-      if (rc != PAS_EDEVICE) rc = set_error(ctx, PAS_EDEVICE, ctx->err);
-    }
-    return rc;
-  }
-  return gas_stepped(ctx, gen_to);
-}
-
 int pas_gas_place_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_pods,
                          int32_t max_containers, int32_t i915_index, const int64_t* d_req,
                          const uint32_t* d_req_mask, const int32_t* d_n_containers, int32_t k,
@@ -2259,11 +1726,13 @@ int pas_gas_place_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
   if (rc) return rc;
   if ((rc = activate(ctx))) return rc;
   bool began = false;
-  rc = gas_place_launch(ctx, n_pods, max_containers, i915_index, d_req, d_req_mask,
-                        d_n_containers, k, ld, node_base, d_cand_node, d_cand_len, d_place_node,
-                        d_place_rank, d_res_out, d_cards_out, d_n_sel_out, d_counts_out,
-                        n_placed, n_rounds, &began, pick_stream(ctx, hip_stream));
-  return gas_place_finish(ctx, rc, began, gen_to);
+  const PodBatch pods{n_pods, max_containers, d_req, d_req_mask, d_n_containers};
+  rc = gas_place_launch(ctx, i915_index, pods, k, ld, node_base, d_cand_node, d_cand_len,
+                        d_place_node, d_place_rank, d_res_out, d_cards_out, d_n_sel_out,
+                        d_counts_out, n_placed, n_rounds, &began, pick_stream(ctx, hip_stream));
+  // (a failure after commits began leaves no valid snapshot behind: a device error)
+  if (rc && began && rc != PAS_EDEVICE) rc = set_error(ctx, PAS_EDEVICE, ctx->err);
+  return gas_finish(ctx, rc, began, gen_to);
 }
 
 int pas_gas_place(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_pods,
@@ -2300,14 +1769,11 @@ int pas_gas_place(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_po
   st.out_opt(d_cnt, C > 0 ? counts_out : nullptr, P * C * (size_t)ctx->gas.max_cards);
   if ((rc = st.upload())) return rc;
   bool began = false;
-  rc = gas_place_launch(ctx, n_pods, max_containers, i915_index, d.req, d.mask, d.nc, k, ld,
-                        node_base, d_cand, d_len, d_node, d_rank, d_res, d_sel, d_nsel, d_cnt,
-                        n_placed, n_rounds, &began, ctx->stream);
-  if (!rc && n_pods > 0) {
-    const hipError_t e = st.fetch();
-    if (e != hipSuccess) rc = check_hip(ctx, e, "pas_gas_place: copy of the results");
-  }
-  return gas_place_finish(ctx, rc, began, gen_to);
+  rc = gas_place_launch(ctx, i915_index, d, k, ld, node_base, d_cand, d_len, d_node, d_rank,
+                        d_res, d_sel, d_nsel, d_cnt, n_placed, n_rounds, &began, ctx->stream);
+  if (!rc && n_pods > 0) rc = st.fetch_results(fn);
+  if (rc && began && rc != PAS_EDEVICE) rc = set_error(ctx, PAS_EDEVICE, ctx->err);
+  return gas_finish(ctx, rc, began, gen_to);
 }
 
 int pas_gas_snapshot_get(pas_ctx* ctx, uint64_t* gen, int64_t* used_out) {
@@ -2380,10 +1846,9 @@ int pas_gas_nodes_update_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to
                            d_upd_src, d_status_out, "pas_gas_nodes_update_device");
   if (rc) return rc;
   if ((rc = activate(ctx))) return rc;
-  if ((rc = gas_nodes_update_launch(ctx, n_updates, d_upd_node, d_upd_n_cards, d_upd_cap,
-                                    d_upd_src, d_status_out, pick_stream(ctx, hip_stream))))
-    return rc;
-  return gas_stepped(ctx, gen_to);
+  rc = gas_nodes_update_launch(ctx, n_updates, d_upd_node, d_upd_n_cards, d_upd_cap, d_upd_src,
+                               d_status_out, pick_stream(ctx, hip_stream));
+  return gas_finish(ctx, rc, false, gen_to);
 }
 
 int pas_gas_nodes_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_updates,
@@ -2426,7 +1891,8 @@ int pas_gas_nodes_update(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32
                                       ctx->stream)))
       return rc;
   }
-  return gas_write_finish(ctx, gen_to, n_updates > 0, st, fn);
+  rc = n_updates > 0 ? st.fetch_results(fn) : PAS_OK;
+  return gas_finish(ctx, rc, rc != PAS_OK, gen_to);
 }
 
 // The resident snapshot moved into new storage of n_nodes_new x max_cards_new, for the calls
@@ -2561,8 +2027,8 @@ static int gas_fit_host(pas_ctx* ctx, uint64_t gen, int32_t n_pods, int32_t max_
   st.work(d_side, (size_t)side_cap);  // (fetched below, once the count is known)
   st.out_opt(d_count, side_count ? &count : nullptr, 1);
   if ((rc = st.upload())) return rc;
-  rc = gas_fit_launch(ctx, n_pods, max_containers, i915_index, d.req, d.mask, d.nc, d_res, N,
-                      nullptr, side_cap > 0 ? d_side : nullptr, side_cap, d_count, ctx->stream);
+  rc = gas_fit_launch(ctx, i915_index, d, d_res, N, nullptr, side_cap > 0 ? d_side : nullptr,
+                      side_cap, d_count, ctx->stream);
   if (rc) return rc;
   PAS_HIP(ctx, st.fetch());
   // a side-stream wait of this fit that gave up: its words are incomplete
@@ -2613,8 +2079,8 @@ static int gas_fit_device_common(pas_ctx* ctx, uint64_t gen, int32_t n_pods,
                      (max_containers > 0 && (!d_req || !d_req_mask)) || (side_cap > 0 && !d_side)))
     return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null input");
   if ((rc = activate(ctx))) return rc;
-  return gas_fit_launch(ctx, n_pods, max_containers, i915_index, d_req, d_req_mask,
-                        d_n_containers, d_res_out, ld_res, d_fit_out,
+  const PodBatch pods{n_pods, max_containers, d_req, d_req_mask, d_n_containers};
+  return gas_fit_launch(ctx, i915_index, pods, d_res_out, ld_res, d_fit_out,
                         side_cap > 0 ? d_side : nullptr, side_cap, d_side_count,
                         pick_stream(ctx, hip_stream));
 }
@@ -2728,9 +2194,8 @@ int pas_gas_fit_requests(pas_ctx* ctx, uint64_t gen, int32_t n_requests, const i
   if ((rc = st.upload())) return rc;
   hipStream_t s = ctx->stream;
   HostStage stage;  // (req_off is the caller's until fetch_request_rows has synchronized)
-  if ((rc = gas_fit_requests_launch(ctx, n_requests, req_off, d_node, max_containers,
-                                    i915_index, d.req, d.mask, d.nc, d_rows, ld_dev, &stage,
-                                    s))) {
+  if ((rc = gas_fit_requests_launch(ctx, n_requests, req_off, d_node, i915_index, d, d_rows,
+                                    ld_dev, &stage, s))) {
     (void)hipStreamSynchronize(s);  // the copy of req_off may be in flight
     return rc;
   }
@@ -2749,9 +2214,9 @@ int pas_gas_fit_requests_device(pas_ctx* ctx, uint64_t gen, int32_t n_requests,
                               "pas_gas_fit_requests_device", &longest);
   if (rc || n_requests == 0) return rc;
   if ((rc = activate(ctx))) return rc;
-  return gas_fit_requests_launch(ctx, n_requests, req_off, d_req_node, max_containers,
-                                 i915_index, d_req, d_req_mask, d_n_containers, d_fit_out,
-                                 ld_words, nullptr, pick_stream(ctx, hip_stream));
+  const PodBatch pods{n_requests, max_containers, d_req, d_req_mask, d_n_containers};
+  return gas_fit_requests_launch(ctx, n_requests, req_off, d_req_node, i915_index, pods,
+                                 d_fit_out, ld_words, nullptr, pick_stream(ctx, hip_stream));
 }
 
 // --------------------------------------------------------------------------- deschedule labels
@@ -3067,9 +2532,9 @@ static int tas_gas_topk_api(pas_ctx* ctx, const char* fn, bool wide, uint64_t ta
       (after && (!d_after_key || !d_after_node || (wide && !d_after_sub))))
     return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
   if ((rc = activate(ctx))) return rc;
-  return tas_gas_topk_launch(ctx, n_pods, n_rules, d_rules, d_rule_off, d_prio, d_cand,
-                             max_containers, i915_index, d_req, d_req_mask, d_n_containers, k,
-                             node_base, d_top_key, wide ? d_top_sub : nullptr, d_top_node,
+  const PodBatch pods{n_pods, max_containers, d_req, d_req_mask, d_n_containers};
+  return tas_gas_topk_launch(ctx, n_rules, d_rules, d_rule_off, d_prio, d_cand, i915_index, pods,
+                             k, node_base, d_top_key, wide ? d_top_sub : nullptr, d_top_node,
                              d_top_len, after ? d_after_key : nullptr,
                              wide ? d_after_sub : nullptr, d_after_node,
                              pick_stream(ctx, hip_stream));
@@ -3173,8 +2638,8 @@ static int topk_policies_api(pas_ctx* ctx, const char* fn, bool gas, bool wide, 
       (after && (!d_after_key || !d_after_node || (wide && !d_after_sub))))
     return set_error(ctx, PAS_EINVAL, std::string(fn) + ": null argument");
   if ((rc = activate(ctx))) return rc;
-  return tas_gas_topk_policies_launch(ctx, n_pods, d_pod_policy, d_cand, gas, max_containers,
-                                      i915_index, d_req, d_req_mask, d_n_containers, k,
+  const PodBatch pods{n_pods, max_containers, d_req, d_req_mask, d_n_containers};
+  return tas_gas_topk_policies_launch(ctx, d_pod_policy, d_cand, gas, i915_index, pods, k,
                                       node_base, d_top_key, wide ? d_top_sub : nullptr,
                                       d_top_node, d_top_len, after ? d_after_key : nullptr,
                                       wide ? d_after_sub : nullptr, d_after_node,

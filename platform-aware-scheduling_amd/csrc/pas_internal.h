@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "csr_entry.h"
 #include "pas.h"
 
 namespace pas {
@@ -455,6 +456,35 @@ struct SlotScope {
 int activate(pas_ctx* ctx);  // hipSetDevice(ctx->device)
 hipStream_t pick_stream(pas_ctx* ctx, void* s);
 
+// Checks of pas_api.hip that the entry points of other files share.  check_update: the TAS
+// snapshot, its generation and the columns of a column update (distinct, below n_metrics).
+// check_gas_gen: the GAS snapshot and its generation.  gas_pod_check: pod p of a host batch has
+// n_containers[p] within [0, max_containers] and no mask bit at or above n_res.
+int check_update(pas_ctx* ctx, uint64_t gen_from, int32_t n_cols, const int32_t* cols,
+                 const void* vals, const void* present, const char* fn);
+int check_gas_gen(pas_ctx* ctx, uint64_t gen);
+int gas_pod_check(pas_ctx* ctx, int32_t p, int32_t max_containers, const uint32_t* req_mask,
+                  const int32_t* n_containers, const char* fn);
+
+// A GAS pod batch on the device: req [P][C][Q], mask [P][C], n_containers [P].  The host forms
+// fill it through stage_pods (host_staging.h), the _device forms from their arguments; the
+// pointers of a staged batch are valid at P == 0 or C == 0 too (nothing is copied then): the
+// kernels read no request of a pod without containers.
+struct PodBatch {
+  int32_t n_pods;
+  int32_t max_containers;
+  const int64_t* req;
+  const uint32_t* mask;
+  const int32_t* n_containers;
+};
+
+// The end of a call that writes the resident GAS snapshot.  rc == PAS_OK: the generation steps
+// to gen_to and the epoch advances.  Otherwise rc comes back as it is, and when the error came
+// after the call's first resident write (`wrote`) the snapshot is of unknown content:
+// ctx->gas.valid is cleared, and ctx->gas_cards.valid with it when the call writes that table
+// too (`cards`).
+int gas_finish(pas_ctx* ctx, int rc, bool wrote, uint64_t gen_to, bool cards = false);
+
 // Bracket a launch with timing events when ctx->timing is on.
 void timing_begin(pas_ctx* ctx, hipStream_t s, int kernel, TimedLaunch* tl);
 void timing_end(pas_ctx* ctx, hipStream_t s, TimedLaunch* tl);
@@ -489,64 +519,21 @@ int tas_snapshot_update_mixed(pas_ctx* ctx, uint64_t gen, int32_t n_narrow,
                               const int32_t* cols_narrow, int32_t n_wide,
                               const int32_t* cols_wide, const int64_t* d_vals,
                               const uint32_t* d_nano, const uint64_t* d_present, hipStream_t s);
-// Quantity literals (tas_ingest.hip).  The parse of n literals bytes[off[i] .. off[i + 1]) on
-// device arrays, enqueued on s: offsets are read clamped into [0, n_bytes]; an output may be
-// null.
-int quantities_parse_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_lit_off,
-                            const char* d_bytes, int64_t* d_whole, uint32_t* d_nano,
-                            int32_t* d_decimals, int32_t* d_status, hipStream_t s);
-// pas_tas_snapshot_update_quantities_device past its argument checks (cols distinct and in
-// range, col_off a CSR from 0 with at most INT32_MAX entries): synchronous on s, workspace
-// from the slot of s.  A literal that does not parse: its status, *bad_entry its index,
-// nothing changed.
-int tas_update_quantities_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
-                                 const int32_t* cols, const int64_t* col_off, int64_t n_bytes,
-                                 const int32_t* d_entry_node, const int64_t* d_lit_off,
-                                 const char* d_bytes, int32_t* kind_out, int32_t* scale_out,
-                                 int64_t* bad_entry, hipStream_t s);
 // free_pool (span_pool.hip): the span arrays and the pool of sp, which is empty afterwards.
 void free_pool(SpanPool& sp);
 // Name table (name_table.hip).  free_names: every array of the table (pas_destroy).
-// names_resolve_launch: d_slot[i] = the slot of name i = d_bytes[d_off[i] .. d_off[i + 1])
-// (offsets read clamped into [0, n_bytes]) or -1, enqueued on s after the last table change;
-// d_hash (the names' hashes) and d_unknown (a zeroed counter: + the entries without a slot,
-// the empty ones only when count_empty) may be null.  The caller has checked ctx->names.valid.
+// names_resolve_launch: d_slot[i] = the slot of entry i of `names` (offsets read clamped into
+// [0, n_bytes]) or -1, enqueued on s after the last table change; d_hash (the names' hashes) and
+// d_unknown (a zeroed counter: + the entries without a slot, the empty ones only when
+// count_empty) may be null.  The caller has checked ctx->names.valid.
 void free_names(NameTable& t);
-int names_resolve_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_off,
-                         const char* d_bytes, int32_t* d_slot, uint64_t* d_hash,
-                         uint32_t* d_unknown, bool count_empty, hipStream_t s);
+int names_resolve_launch(pas_ctx* ctx, int64_t n, ByteSpans names, int32_t* d_slot,
+                         uint64_t* d_hash, uint32_t* d_unknown, bool count_empty, hipStream_t s);
 // What the annotation forms share (pas_gas_annotations_resolve*, pas_gas_apply_annotations*,
 // pas_gas_annotations_render*): the card-name table is there and has the resident snapshot's
 // shape, and the name table is there when the nodes come by name.  The caller has checked the
 // snapshot.
 int gas_annotations_tables(pas_ctx* ctx, bool by_name, const std::string& fn);
-// Pod events from annotation strings (gas_annotations.hip).  annotations_resolve_launch: the
-// parse-alone form on device arrays, enqueued on s: per event the verdict of the rules of
-// pas_gas_apply_annotations (d_kind null: no kind is checked; d_name_off non-null: d_node holds
-// the slots of the nodes given by those names, and an empty name is bad args), the listed count,
-// the cards per container and the ranks of the first cards_ld listed cards of every event.
-// The caller has checked the snapshot and the card-name table.
-int annotations_resolve_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
-                               const int32_t* d_pod, const int32_t* d_node, int64_t n_name_bytes,
-                               const int64_t* d_name_off, int32_t n_pods, const int32_t* d_ncont,
-                               int32_t max_containers, int64_t n_ann_bytes,
-                               const int64_t* d_ann_off, const char* d_ann_bytes, int32_t cards_ld,
-                               int32_t* d_verdict, int32_t* d_n_listed, int32_t* d_cpc,
-                               int32_t* d_cards, hipStream_t s);
-// pas_gas_apply_annotations[_names][_device] on device arrays: the count pass, the call's one
-// read-back (s is synchronized), the rank pass into the slot's workspace, gas_apply_launch and
-// the status fix-up.  d_node: the events' slots, or null with the nodes given by name (d_name_off
-// / d_name_bytes, resolved through the name table, which the caller has checked like the
-// snapshot and the card-name table).  Nothing of the snapshot has changed when it returns an
-// error.
-int gas_apply_annotations_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
-                                 const int32_t* d_pod, const int32_t* d_node,
-                                 int64_t n_name_bytes, const int64_t* d_name_off,
-                                 const char* d_name_bytes, int32_t n_pods, int32_t max_containers,
-                                 const int64_t* d_req, const uint32_t* d_mask,
-                                 const int32_t* d_ncont, int64_t n_ann_bytes,
-                                 const int64_t* d_ann_off, const char* d_ann_bytes,
-                                 int32_t* d_status, hipStream_t s);
 // The card-name table's pool gathered on s when its dead bytes have passed the live ones
 // (gas_cards.hip: the rule of pas_gas_card_names_update), for a caller that appended rows on the
 // device and kept row_bytes / live_bytes / pool_used in step (gas_node_strings.hip).
@@ -593,10 +580,8 @@ int filter_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_
                            const int32_t* d_req, uint64_t* d_pass, int64_t ld_words,
                            HostStage* stage, hipStream_t s);
 int gas_fit_requests_launch(pas_ctx* ctx, int32_t n_requests, const int32_t* req_off,
-                            const int32_t* d_req_node, int32_t max_containers,
-                            int32_t i915_index, const int64_t* d_req, const uint32_t* d_mask,
-                            const int32_t* d_ncont, uint64_t* d_fit, int64_t ld_words,
-                            HostStage* stage, hipStream_t s);
+                            const int32_t* d_req_node, int32_t i915_index, const PodBatch& pods,
+                            uint64_t* d_fit, int64_t ld_words, HostStage* stage, hipStream_t s);
 // (n_rules bounds the device rule_off: offsets are clamped into [0, n_rules], rule_span)
 int tas_violations_launch(pas_ctx* ctx, int32_t n_strat, int32_t n_rules,
                           const pas_rule* d_rules, const int32_t* d_rule_off, uint64_t* d_viol,
@@ -624,10 +609,8 @@ int filter_requests_policy_launch(pas_ctx* ctx, int32_t n_requests, const int32_
 // stream was synchronized, PAS_EDEVICE (and the side streams drained) if a wait gave up since
 // the last report, else PAS_OK.
 int gas_fault_check(pas_ctx* ctx);
-int gas_fit_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t i915_index,
-                   const int64_t* d_req, const uint32_t* d_req_mask,
-                   const int32_t* d_n_containers, uint32_t* d_res, int64_t ld_res,
-                   uint64_t* d_fit, pas_gas_selection* d_side, int64_t side_cap,
+int gas_fit_launch(pas_ctx* ctx, int32_t i915_index, const PodBatch& pods, uint32_t* d_res,
+                   int64_t ld_res, uint64_t* d_fit, pas_gas_selection* d_side, int64_t side_cap,
                    int64_t* d_side_count, hipStream_t s);
 // (d_sub / d_subs of the top-k and merge launches: the wide records' third array, pas.h;
 // null = the 64-bit records)
@@ -637,25 +620,21 @@ int tas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rul
                     int32_t* d_node, int32_t* d_len, hipStream_t s);
 // d_after_key / d_after_sub (wide records) / d_after_node: the pods' cursors, the lists resume
 // strictly after them (pas.h); null d_after_key = the lists from their beginning.
-int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_rules, const pas_rule* d_rules,
                         const int32_t* d_rule_off, const pas_rule* d_prio,
-                        const uint64_t* d_cand, int32_t max_containers, int32_t i915_index,
-                        const int64_t* d_req, const uint32_t* d_req_mask,
-                        const int32_t* d_n_containers, int32_t k, int32_t node_base,
-                        int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
-                        const int64_t* d_after_key, const uint32_t* d_after_sub,
-                        const int32_t* d_after_node, hipStream_t s);
+                        const uint64_t* d_cand, int32_t i915_index, const PodBatch& pods,
+                        int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
+                        int32_t* d_node, int32_t* d_len, const int64_t* d_after_key,
+                        const uint32_t* d_after_sub, const int32_t* d_after_node, hipStream_t s);
 // The same walk by policy id over the resident table (valid and current: the caller has
-// checked) and its cached violating sets; fit = false: TAS only (no GAS snapshot, the GAS and
-// cursor arguments unused).  Neither builds nor reads the node-major copies.
-int tas_gas_topk_policies_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy,
-                                 const uint64_t* d_cand, bool fit, int32_t max_containers,
-                                 int32_t i915_index, const int64_t* d_req,
-                                 const uint32_t* d_req_mask, const int32_t* d_n_containers,
-                                 int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
-                                 int32_t* d_node, int32_t* d_len, const int64_t* d_after_key,
-                                 const uint32_t* d_after_sub, const int32_t* d_after_node,
-                                 hipStream_t s);
+// checked) and its cached violating sets; fit = false: TAS only (no GAS snapshot; of pods only
+// n_pods is read, and no cursor argument).  Neither builds nor reads the node-major copies.
+int tas_gas_topk_policies_launch(pas_ctx* ctx, const int32_t* d_pod_policy,
+                                 const uint64_t* d_cand, bool fit, int32_t i915_index,
+                                 const PodBatch& pods, int32_t k, int32_t node_base,
+                                 int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
+                                 const int64_t* d_after_key, const uint32_t* d_after_sub,
+                                 const int32_t* d_after_node, hipStream_t s);
 int list_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_shards, int32_t width,
                       const int64_t* d_keys, const uint32_t* d_subs, const int32_t* d_nodes,
                       int32_t* d_out_node, int64_t out_ld, int32_t* d_out_len, hipStream_t s);
@@ -665,10 +644,9 @@ int topk_merge_launch(pas_ctx* ctx, int32_t n_pods, int32_t k, int32_t n_shards,
 // Bind (fit + commit, release = false) or release of n_ops operations the host grouped by
 // node: order = the operation indices sorted by node (stable), key[i] = the node of operation
 // order[i] (all in range).  The walker kernel of the event path applies them (gas_commit.hip).
-int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_ops, int32_t max_containers,
-                      int32_t i915_index, const int32_t* d_order, const uint32_t* d_key,
-                      const int32_t* d_pod, const int64_t* d_req, const uint32_t* d_mask,
-                      const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
+int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_ops, int32_t i915_index,
+                      const int32_t* d_order, const uint32_t* d_key, const int32_t* d_pod,
+                      const PodBatch& pods, const int32_t* d_cpc, const int32_t* d_cards,
                       int32_t cards_stride, uint32_t* d_res, int32_t* d_status,
                       uint8_t* d_cards_out, int32_t* d_nsel_out, int64_t* d_counts_out,
                       const int64_t* d_counts, hipStream_t s);
@@ -677,9 +655,8 @@ int gas_commit_launch(pas_ctx* ctx, bool release, int32_t n_ops, int32_t max_con
 // walker kernel, all enqueued on s.  Nothing of the snapshot has changed when it returns an
 // error.
 int gas_apply_launch(pas_ctx* ctx, int32_t n_events, const int32_t* d_kind,
-                     const int32_t* d_pod, const int32_t* d_node, int32_t n_pods,
-                     int32_t max_containers, const int64_t* d_req, const uint32_t* d_mask,
-                     const int32_t* d_ncont, const int32_t* d_cpc, const int32_t* d_cards,
+                     const int32_t* d_pod, const int32_t* d_node, const PodBatch& pods,
+                     const int32_t* d_cpc, const int32_t* d_cards,
                      int32_t cards_ld, int32_t* d_status, hipStream_t s);
 // Node updates (pas_gas_nodes_update[_device], gas_nodes.hip) on device arrays: grouped by node
 // on the device (NodeRuns, gas_group.h) and applied in call order, all enqueued on s.  Nothing
@@ -701,9 +678,8 @@ int gas_compact_launch(pas_ctx* ctx, int32_t n_nodes_new, const int32_t* d_src_n
 // Batch placement (gas_place.hip): the rounds of pas_gas_place_device on s, returning when the
 // placement is complete.  *began: commits were launched (an error past that point leaves
 // the resident usage half committed: the caller invalidates the snapshot).
-int gas_place_launch(pas_ctx* ctx, int32_t n_pods, int32_t max_containers, int32_t i915_index,
-                     const int64_t* d_req, const uint32_t* d_mask, const int32_t* d_ncont,
-                     int32_t k, int32_t ld, int32_t node_base, const int32_t* d_cand,
+int gas_place_launch(pas_ctx* ctx, int32_t i915_index, const PodBatch& pods, int32_t k,
+                     int32_t ld, int32_t node_base, const int32_t* d_cand,
                      const int32_t* d_cand_len, int32_t* d_place_node, int32_t* d_place_rank,
                      uint32_t* d_res, uint8_t* d_cards_out, int32_t* d_nsel_out,
                      int64_t* d_counts_out, int32_t* n_placed, int32_t* n_rounds,

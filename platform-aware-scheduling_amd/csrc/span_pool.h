@@ -1,7 +1,8 @@
 // span_pool.h — the layer under the two resident name tables (name_table.hip: node names,
 // gas_cards.hip: card names): a SpanPool (pas_internal.h) is spans (beg, len) into one byte
-// pool that only grows.  Here: the scans, the CSR check of the host forms, and what
-// span_pool.hip builds on them.  `table` names the table in an error ("name table"), `fn` the
+// pool that only grows.  Here: the scans, the two checks of a call's byte spans (ByteSpans,
+// csr_entry.h: every string verb's, not only the tables'), and what span_pool.hip builds on the
+// scans.  `table` names the table in an error ("name table"), `fn` the
 // entry point.
 #pragma once
 
@@ -40,9 +41,15 @@ inline void free_dev(void* p) {
 
 int no_table(pas_ctx* ctx, const std::string& fn, const char* table);
 
-// offsets [n + 1] of a host form: from 0 and non-decreasing
-int check_csr(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
-              const std::string& fn);
+// The n byte spans of a host form: offsets [n + 1] from 0 and non-decreasing, bytes when the
+// total is above 0.  `what` names the entry point, and the argument when it has several.
+// has_bytes = false: offsets that count something other than bytes (the col_off of a quantity
+// refresh counts entries), so no byte array goes with them and `bytes` is not looked at.
+int check_host_spans(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
+                     const std::string& what, bool has_bytes = true);
+// The n byte spans of a _device form, of which the host sees the count and the pointers only:
+// n_bytes >= 0 whatever n is, and with n > 0 offsets, and bytes when n_bytes > 0.
+int check_device_spans(pas_ctx* ctx, int64_t n, const ByteSpans& sp, const std::string& what);
 
 // A compact map of n_new rows over n_old: every entry is -1 or a row above the entries before
 // it.

@@ -109,12 +109,19 @@ int no_table(pas_ctx* ctx, const std::string& fn, const char* table) {
   return set_error(ctx, PAS_ENOSNAP, fn + ": no " + table);
 }
 
-int check_csr(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
-              const std::string& fn) {
-  if (!off || off[0] != 0) return set_error(ctx, PAS_EINVAL, fn + ": offsets must start at 0");
+int check_host_spans(pas_ctx* ctx, int64_t n, const int64_t* off, const char* bytes,
+                     const std::string& what, bool has_bytes) {
+  if (!off || off[0] != 0) return set_error(ctx, PAS_EINVAL, what + ": offsets must start at 0");
   for (int64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return set_error(ctx, PAS_EINVAL, fn + ": offsets decrease");
-  if (off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, fn + ": null input");
+    if (off[i + 1] < off[i]) return set_error(ctx, PAS_EINVAL, what + ": offsets decrease");
+  if (has_bytes && off[n] > 0 && !bytes) return set_error(ctx, PAS_EINVAL, what + ": null bytes");
+  return PAS_OK;
+}
+
+int check_device_spans(pas_ctx* ctx, int64_t n, const ByteSpans& sp, const std::string& what) {
+  if (sp.n_bytes < 0) return set_error(ctx, PAS_EINVAL, what + ": a byte count < 0");
+  if (n > 0 && (!sp.off || (sp.n_bytes > 0 && !sp.bytes)))
+    return set_error(ctx, PAS_EINVAL, what + ": null offsets or bytes");
   return PAS_OK;
 }
 

@@ -859,19 +859,18 @@ LazyTopkParams topk_params(const TasSnapshot& t, int32_t n_pods, const uint64_t*
   return a;
 }
 
-void topk_gas_params(LazyTopkParams& a, const GasSnapshot& g, int32_t max_containers,
-                     int32_t i915_index, const int64_t* d_req, const uint32_t* d_req_mask,
-                     const int32_t* d_n_containers) {
+void topk_gas_params(LazyTopkParams& a, const GasSnapshot& g, int32_t i915_index,
+                     const PodBatch& pods) {
   a.K = g.max_cards;
   a.Q = g.n_res;
-  a.C = max_containers;
+  a.C = pods.max_containers;
   a.i915 = i915_index;
   a.n_cards = g.n_cards;
   a.cap = g.cap;
   a.used = g.used;
-  a.req = d_req;
-  a.mask = d_req_mask;
-  a.ncont = d_n_containers;
+  a.req = pods.req;
+  a.mask = pods.mask;
+  a.ncont = pods.n_containers;
 }
 
 // The walk on s, timed as PAS_K_TAS_GAS_TOPK: from the lists' beginning, or (d_after_key)
@@ -934,14 +933,13 @@ int topk_walk(pas_ctx* ctx, const LazyTopkParams& a, bool fit, const pas_rule* d
 
 }  // namespace
 
-int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas_rule* d_rules,
+int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_rules, const pas_rule* d_rules,
                         const int32_t* d_rule_off, const pas_rule* d_prio,
-                        const uint64_t* d_cand, int32_t max_containers, int32_t i915_index,
-                        const int64_t* d_req, const uint32_t* d_req_mask,
-                        const int32_t* d_n_containers, int32_t k, int32_t node_base,
-                        int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
-                        const int64_t* d_after_key, const uint32_t* d_after_sub,
-                        const int32_t* d_after_node, hipStream_t s) {
+                        const uint64_t* d_cand, int32_t i915_index, const PodBatch& pods,
+                        int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
+                        int32_t* d_node, int32_t* d_len, const int64_t* d_after_key,
+                        const uint32_t* d_after_sub, const int32_t* d_after_node, hipStream_t s) {
+  const int32_t n_pods = pods.n_pods;
   if (n_pods == 0) return PAS_OK;
   TasSnapshot& t = ctx->tas;
   const int32_t N = t.n_nodes, M = t.n_metrics;
@@ -981,21 +979,20 @@ int tas_gas_topk_launch(pas_ctx* ctx, int32_t n_pods, int32_t n_rules, const pas
   a.prio = d_prio;
   a.vals_t = t.vals_t;
   a.pres_t = t.pres_t;
-  topk_gas_params(a, ctx->gas, max_containers, i915_index, d_req, d_req_mask, d_n_containers);
+  topk_gas_params(a, ctx->gas, i915_index, pods);
   return topk_walk<false>(ctx, a, true, d_prio, d_after_key, d_after_sub, d_after_node, s);
 }
 
 // The policy form: the walk over the resident table and its cached violating sets.  Neither
 // builds nor reads the node-major copies (vals_t / pres_t): a context that only ever calls
 // this form never allocates them.
-int tas_gas_topk_policies_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_pod_policy,
-                                 const uint64_t* d_cand, bool fit, int32_t max_containers,
-                                 int32_t i915_index, const int64_t* d_req,
-                                 const uint32_t* d_req_mask, const int32_t* d_n_containers,
-                                 int32_t k, int32_t node_base, int64_t* d_key, uint32_t* d_sub,
-                                 int32_t* d_node, int32_t* d_len, const int64_t* d_after_key,
-                                 const uint32_t* d_after_sub, const int32_t* d_after_node,
-                                 hipStream_t s) {
+int tas_gas_topk_policies_launch(pas_ctx* ctx, const int32_t* d_pod_policy,
+                                 const uint64_t* d_cand, bool fit, int32_t i915_index,
+                                 const PodBatch& pods, int32_t k, int32_t node_base,
+                                 int64_t* d_key, uint32_t* d_sub, int32_t* d_node, int32_t* d_len,
+                                 const int64_t* d_after_key, const uint32_t* d_after_sub,
+                                 const int32_t* d_after_node, hipStream_t s) {
+  const int32_t n_pods = pods.n_pods;
   if (n_pods == 0) return PAS_OK;
   const TasPolicies& pt = ctx->policies;
   // built on s if the snapshot or the table changed, else s waits for the build's event
@@ -1012,7 +1009,7 @@ int tas_gas_topk_policies_launch(pas_ctx* ctx, int32_t n_pods, const int32_t* d_
   a.n_policies = pt.n_policies;
   a.viol = viol;
   if (!fit) return topk_walk<true>(ctx, a, false, nullptr, nullptr, nullptr, nullptr, s);
-  topk_gas_params(a, ctx->gas, max_containers, i915_index, d_req, d_req_mask, d_n_containers);
+  topk_gas_params(a, ctx->gas, i915_index, pods);
   if (!d_after_key) return topk_walk<true>(ctx, a, true, nullptr, nullptr, nullptr, nullptr, s);
   // the start kernel takes per-pod prio rules: gathered out of the table into the stream's
   // slot, which stays this call's until the walk is enqueued

@@ -21,10 +21,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
+#include "host_staging.h"
 #include "pas_internal.h"
 #include "quantity_fixed.h"
+#include "span_pool.h"
 
 namespace pas {
 namespace {
@@ -41,22 +44,16 @@ __device__ __forceinline__ int32_t meta_status(int32_t m) { return (int32_t)(int
 __device__ __forceinline__ int32_t meta_decimals(int32_t m) { return (m >> 8) & 0xff; }
 __device__ __forceinline__ int32_t meta_fit(int32_t m) { return ((m >> 16) & 0xff) - 1; }
 
-__device__ __forceinline__ int64_t clamp_off(int64_t v, int64_t n) {
-  return v < 0 ? 0 : v > n ? n : v;
-}
-
-// Literal i is bytes[off[i] .. off[i + 1]), both ends clamped into [0, n_bytes] and the end
-// not before the begin: no offset takes a read outside the blob.  Any output may be null.
-__global__ void parse_literals(int64_t n, int64_t n_bytes, const int64_t* __restrict__ off,
-                               const char* __restrict__ bytes, int64_t* __restrict__ whole,
+// Literal i is entry i of lit, its offsets read clamped (csr_entry.h): no offset takes a read
+// outside the blob.  Any output may be null.
+__global__ void parse_literals(int64_t n, ByteSpans lit, int64_t* __restrict__ whole,
                                uint32_t* __restrict__ nano, int32_t* __restrict__ decimals,
                                int32_t* __restrict__ status, int32_t* __restrict__ meta) {
   const int64_t i = (int64_t)blockIdx.x * kTpb + threadIdx.x;
   if (i >= n) return;
-  const int64_t b = clamp_off(off[i], n_bytes);
-  const int64_t e1 = clamp_off(off[i + 1], n_bytes);
-  const int64_t e = e1 < b ? b : e1;
-  const QuantityFixed r = parse_quantity_fixed(bytes + b, e - b);
+  int64_t b;
+  const int64_t len = lit.span(i, &b);
+  const QuantityFixed r = parse_quantity_fixed(lit.bytes + b, len);
   if (whole) whole[i] = r.whole;
   if (nano) nano[i] = r.nano;
   if (decimals) decimals[i] = r.decimals;
@@ -178,23 +175,25 @@ __global__ void ingest_encode(int64_t T, int32_t n_cols, int32_t N, int64_t W,
   atomicOr(&present[row * W + (nd >> 6)], 1ull << (nd & 63));
 }
 
-}  // namespace
-
-int quantities_parse_launch(pas_ctx* ctx, int64_t n, int64_t n_bytes, const int64_t* d_lit_off,
-                            const char* d_bytes, int64_t* d_whole, uint32_t* d_nano,
-                            int32_t* d_decimals, int32_t* d_status, hipStream_t s) {
+// The parse of the n literals of lit on device arrays, enqueued on s; an output may be null.
+int quantities_parse_launch(pas_ctx* ctx, int64_t n, ByteSpans lit, int64_t* d_whole,
+                            uint32_t* d_nano, int32_t* d_decimals, int32_t* d_status,
+                            hipStream_t s) {
   if (n <= 0) return PAS_OK;
-  parse_literals<<<blocks_for(n), kTpb, 0, s>>>(n, n_bytes, d_lit_off, d_bytes, d_whole, d_nano,
-                                                d_decimals, d_status, nullptr);
+  parse_literals<<<blocks_for(n), kTpb, 0, s>>>(n, lit, d_whole, d_nano, d_decimals, d_status,
+                                                nullptr);
   PAS_HIP(ctx, hipGetLastError());
   return PAS_OK;
 }
 
+// pas_tas_snapshot_update_quantities_device past its argument checks (cols distinct and in
+// range, col_off a CSR from 0 with at most INT32_MAX entries): synchronous on s, workspace
+// from the slot of s.  A literal that does not parse: its status, *bad_entry its index,
+// nothing changed.
 int tas_update_quantities_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
-                                 const int32_t* cols, const int64_t* col_off, int64_t n_bytes,
-                                 const int32_t* d_entry_node, const int64_t* d_lit_off,
-                                 const char* d_bytes, int32_t* kind_out, int32_t* scale_out,
-                                 int64_t* bad_entry, hipStream_t s) {
+                                 const int32_t* cols, const int64_t* col_off,
+                                 const int32_t* d_entry_node, ByteSpans lit, int32_t* kind_out,
+                                 int32_t* scale_out, int64_t* bad_entry, hipStream_t s) {
   TasSnapshot& t = ctx->tas;
   const int32_t N = t.n_nodes;
   const int64_t W = w64(N);
@@ -239,8 +238,8 @@ int tas_update_quantities_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
   summary_init<<<blocks_for(n_cols), kTpb, 0, s>>>(n_cols, d_bad, d_max_dec, d_min_fit);
   PAS_HIP(ctx, hipGetLastError());
   if (T > 0) {
-    parse_literals<<<blocks_for(T), kTpb, 0, s>>>(T, n_bytes, d_lit_off, d_bytes, d_whole, d_nano,
-                                                  nullptr, nullptr, d_meta);
+    parse_literals<<<blocks_for(T), kTpb, 0, s>>>(T, lit, d_whole, d_nano, nullptr, nullptr,
+                                                  d_meta);
     PAS_HIP(ctx, hipGetLastError());
     ingest_summary<<<blocks_for(T), kTpb, 0, s>>>(T, n_cols, N, d_col_off, d_entry_node, d_meta,
                                                   d_bad, d_max_dec, d_min_fit);
@@ -319,4 +318,222 @@ int tas_update_quantities_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
   return PAS_OK;
 }
 
+// The refresh with each entry's node given by name (name_table.hip): the names are resolved,
+// lookup only, into a buffer of the stream's slot and the refresh above runs on it.  The count
+// of entries without a slot comes back on s before that launch's own synchronize.
+int update_quantities_names_launch(pas_ctx* ctx, uint64_t gen_to, int32_t n_cols,
+                                   const int32_t* cols, const int64_t* col_off, ByteSpans names,
+                                   ByteSpans lit, int32_t* kind_out, int32_t* scale_out,
+                                   int64_t* bad_entry, int64_t* n_unknown_out, hipStream_t s) {
+  const int64_t T = n_cols > 0 ? col_off[n_cols] : 0;
+  if (n_unknown_out) *n_unknown_out = 0;
+  int rc = PAS_OK;
+  SlotScope scope(ctx, s, 0, &rc);
+  if (!scope.slot) return rc;
+  int32_t* d_node = nullptr;
+  uint32_t unknown = 0;
+  if (T > 0) {
+    const size_t total = carve_size({sizeof(uint32_t), sizeof(int32_t) * (size_t)T});
+    char* base = static_cast<char*>(slot_buf(ctx, scope.slot, kBufNames, total, s, &rc));
+    if (!base) return rc;
+    Carve cv{base};
+    uint32_t* d_ctr = cv.take<uint32_t>(1);
+    d_node = cv.take<int32_t>((size_t)T);
+    PAS_HIP(ctx, hipMemsetAsync(d_ctr, 0, sizeof(uint32_t), s));
+    rc = names_resolve_launch(ctx, T, names, d_node, nullptr, d_ctr, true, s);
+    if (rc) return rc;
+    PAS_HIP(ctx, hipMemcpyAsync(&unknown, d_ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  }
+  rc = tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, d_node, lit, kind_out,
+                                    scale_out, bad_entry, s);
+  if (T > 0 && rc) (void)hipStreamSynchronize(s);  // (an early error: `unknown` is a local)
+  if (n_unknown_out) *n_unknown_out = unknown;
+  return rc;
+}
+
+// The checks every form of pas_tas_snapshot_update_quantities shares: the snapshot and its
+// generation, the columns, and col_off as a CSR of at most INT32_MAX entries; *T = the entries.
+int check_update_quantities(pas_ctx* ctx, uint64_t gen_from, int32_t n_cols, const int32_t* cols,
+                            const int64_t* col_off, int64_t* T, const std::string& fn) {
+  *T = 0;
+  int rc = check_update(ctx, gen_from, n_cols, cols, col_off, col_off, fn.c_str());
+  if (rc) return rc;
+  if (n_cols == 0) return PAS_OK;
+  if ((rc = check_host_spans(ctx, n_cols, col_off, nullptr, fn + ": col_off", false))) return rc;
+  if (col_off[n_cols] > INT32_MAX)
+    return set_error(ctx, PAS_EINVAL, fn + ": more than INT32_MAX entries");
+  *T = col_off[n_cols];
+  return PAS_OK;
+}
+
+}  // namespace
 }  // namespace pas
+
+using namespace pas;
+
+extern "C" {
+
+int pas_quantities_to_wide(pas_ctx* ctx, int64_t n, const int64_t* lit_off, const char* bytes,
+                           int64_t* whole, uint32_t* nano, int32_t* decimals, int32_t* status) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_quantities_to_wide";
+  if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
+  if (n == 0) return PAS_OK;
+  int rc = check_host_spans(ctx, n, lit_off, bytes, fn);
+  if (rc) return rc;
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  ByteSpans lit;
+  int64_t* d_whole;
+  uint32_t* d_nano;
+  int32_t *d_dec, *d_status;
+  st.in_spans(lit, n, lit_off, bytes);
+  st.out_opt(d_whole, whole, (size_t)n);
+  st.out_opt(d_nano, nano, (size_t)n);
+  st.out_opt(d_dec, decimals, (size_t)n);
+  st.out_opt(d_status, status, (size_t)n);
+  if ((rc = st.upload())) return rc;
+  if ((rc = quantities_parse_launch(ctx, n, lit, d_whole, d_nano, d_dec, d_status, ctx->stream)))
+    return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+int pas_quantities_to_wide_device(pas_ctx* ctx, int64_t n, int64_t n_bytes,
+                                  const int64_t* d_lit_off, const char* d_bytes,
+                                  int64_t* d_whole, uint32_t* d_nano, int32_t* d_decimals,
+                                  int32_t* d_status, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_quantities_to_wide_device";
+  const ByteSpans lit{n_bytes, d_lit_off, d_bytes};
+  if (n < 0) return set_error(ctx, PAS_EINVAL, fn + ": n < 0");
+  int rc = check_device_spans(ctx, n, lit, fn);
+  if (rc || n == 0) return rc;
+  if ((rc = activate(ctx))) return rc;
+  return quantities_parse_launch(ctx, n, lit, d_whole, d_nano, d_decimals, d_status,
+                                 pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_snapshot_update_quantities_device(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                              int32_t n_cols, const int32_t* cols,
+                                              const int64_t* col_off, int64_t n_bytes,
+                                              const int32_t* d_entry_node,
+                                              const int64_t* d_lit_off, const char* d_bytes,
+                                              int32_t* kind_out, int32_t* scale_out,
+                                              int64_t* bad_entry, void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities_device";
+  const ByteSpans lit{n_bytes, d_lit_off, d_bytes};
+  if (bad_entry) *bad_entry = -1;
+  int64_t T;
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, &T, fn);
+  if (rc) return rc;
+  if (T > 0 && !d_entry_node) return set_error(ctx, PAS_EINVAL, fn + ": null input");
+  if (T > 0 && (rc = check_device_spans(ctx, T, lit, fn + ": lit_off"))) return rc;
+  if ((rc = activate(ctx))) return rc;
+  return tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, d_entry_node, lit,
+                                      kind_out, scale_out, bad_entry,
+                                      pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_snapshot_update_quantities(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                       int32_t n_cols, const int32_t* cols,
+                                       const int64_t* col_off, const int32_t* entry_node,
+                                       const int64_t* lit_off, const char* bytes,
+                                       int32_t* kind_out, int32_t* scale_out,
+                                       int64_t* bad_entry) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities";
+  if (bad_entry) *bad_entry = -1;
+  int64_t T;
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, &T, fn);
+  if (rc) return rc;
+  if (T > 0) {
+    if (!entry_node) return set_error(ctx, PAS_EINVAL, fn + ": null input");
+    if ((rc = check_host_spans(ctx, T, lit_off, bytes, fn + ": lit_off"))) return rc;
+    // updateMetric replaces a node map: a node listed twice in one column is no map
+    const int32_t N = ctx->tas.n_nodes;
+    std::vector<uint64_t> seen((size_t)w64(N));
+    for (int32_t c = 0; c < n_cols; ++c) {
+      std::fill(seen.begin(), seen.end(), 0);
+      for (int64_t i = col_off[c]; i < col_off[c + 1]; ++i) {
+        const int32_t nd = entry_node[i];
+        if (nd < 0 || nd >= N) continue;
+        uint64_t& w = seen[(size_t)(nd >> 6)];
+        if ((w >> (nd & 63)) & 1ull)
+          return set_error(ctx, PAS_EINVAL, fn + ": column " + std::to_string(cols[c]) +
+                                                " lists node " + std::to_string(nd) + " twice");
+        w |= 1ull << (nd & 63);
+      }
+    }
+  }
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  int32_t* d_node;
+  ByteSpans lit;
+  st.in(d_node, entry_node, (size_t)T);
+  st.in_spans(lit, T, lit_off, bytes);
+  if ((rc = st.upload())) return rc;
+  rc = tas_update_quantities_launch(ctx, gen_to, n_cols, cols, col_off, d_node, lit, kind_out,
+                                    scale_out, bad_entry, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+int pas_tas_snapshot_update_quantities_names_device(
+    pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to, int32_t n_cols, const int32_t* cols,
+    const int64_t* col_off, int64_t n_name_bytes, const int64_t* d_name_off,
+    const char* d_name_bytes, int64_t n_bytes, const int64_t* d_lit_off, const char* d_bytes,
+    int32_t* kind_out, int32_t* scale_out, int64_t* bad_entry, int64_t* n_unknown_out,
+    void* hip_stream) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities_names_device";
+  const ByteSpans names{n_name_bytes, d_name_off, d_name_bytes}, lit{n_bytes, d_lit_off, d_bytes};
+  if (bad_entry) *bad_entry = -1;
+  if (n_unknown_out) *n_unknown_out = 0;
+  if (!ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
+  int64_t T;
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, &T, fn);
+  if (rc) return rc;
+  if (T > 0 && ((rc = check_device_spans(ctx, T, names, fn + ": name_off")) ||
+                (rc = check_device_spans(ctx, T, lit, fn + ": lit_off"))))
+    return rc;
+  if ((rc = activate(ctx))) return rc;
+  return update_quantities_names_launch(ctx, gen_to, n_cols, cols, col_off, names, lit, kind_out,
+                                        scale_out, bad_entry, n_unknown_out,
+                                        pick_stream(ctx, hip_stream));
+}
+
+int pas_tas_snapshot_update_quantities_names(pas_ctx* ctx, uint64_t gen_from, uint64_t gen_to,
+                                             int32_t n_cols, const int32_t* cols,
+                                             const int64_t* col_off, const int64_t* name_off,
+                                             const char* name_bytes, const int64_t* lit_off,
+                                             const char* bytes, int32_t* kind_out,
+                                             int32_t* scale_out, int64_t* bad_entry,
+                                             int64_t* n_unknown_out) {
+  if (!ctx) return PAS_EINVAL;
+  const std::string fn = "pas_tas_snapshot_update_quantities_names";
+  if (bad_entry) *bad_entry = -1;
+  if (n_unknown_out) *n_unknown_out = 0;
+  if (!ctx->names.valid) return set_error(ctx, PAS_ENOSNAP, fn + ": no name table");
+  int64_t T;
+  int rc = check_update_quantities(ctx, gen_from, n_cols, cols, col_off, &T, fn);
+  if (rc) return rc;
+  if (T > 0 && ((rc = check_host_spans(ctx, T, lit_off, bytes, fn + ": lit_off")) ||
+                (rc = check_host_spans(ctx, T, name_off, name_bytes, fn + ": name_off"))))
+    return rc;
+  if ((rc = activate(ctx))) return rc;
+  Staging st(ctx);
+  ByteSpans names, lit;
+  st.in_spans(names, T, name_off, name_bytes);
+  st.in_spans(lit, T, lit_off, bytes);
+  if ((rc = st.upload())) return rc;
+  rc = update_quantities_names_launch(ctx, gen_to, n_cols, cols, col_off, names, lit, kind_out,
+                                      scale_out, bad_entry, n_unknown_out, ctx->stream);
+  if (rc) return rc;
+  PAS_HIP(ctx, st.fetch());
+  return PAS_OK;
+}
+
+}  // extern "C"
